@@ -15,7 +15,10 @@ tests/test_gpu_full_parity.py).  One process per GPU, frames sharded across GPUs
 per-frame boxes are gathered to rank 0 with one RCCL all-gather inside the timed region.
 value = frames/s over all GPUs.  Prints ONE JSON line on rank 0.
 
-Besides the headline the default single-GPU run measures, into the same JSON line (each a few seconds; --no-aux skips):
+A plain run sets up, warms up, times the --steps steps and prints the line; --dump-outputs DIR also writes the boxes and counts of
+the last timed step as DIR/*.npy (inputs are seeded: two builds compare output for output).  Everything else is measured only
+with --full: the roofline of the dominant kernel (per-launch profile), the CPU baseline (the oracle on this host's cores), and
+on a single GPU the following legs, into the same JSON line (each a few seconds; --no-aux skips them):
   fp32       the same workload with every convolution in exact fp32 (--fp32-batch frames per step), with its own roofline
   ref_batch  the headline arithmetic at the reference's BATCH_SIZE_PER_GPU = 8 (centerpoint_1sweep.yaml:88)
   batch16    ... at 16 frames per pass, the default of rounds 1-3 (the default is 32 since round 4: DESIGN.md section 4, batch sweep)
@@ -35,7 +38,7 @@ Besides the headline the default single-GPU run measures, into the same JSON lin
 The exact-fp32 leg is also promoted to the top-level keys value_fp32 / roofline_fp32 (the precision-equivalent number next to
 `value`, whose arithmetic carries 22 significant bits).
 
-N > 1: `python bench.py --gpus N` starts the N ranks itself (re-executes under torch.distributed.run on 127.0.0.1) when it is not
+N > 1: `python bench.py --gpus N` starts the N ranks itself (a child process under torch.distributed.run on 127.0.0.1) when it is not
 already running under a launcher, and fails if the node has fewer than N GPUs; the line carries ranks_seen (all-reduced) and the
 time of the box gather.
 """
@@ -141,12 +144,20 @@ def parse():
     ap.add_argument('--stub', action='store_true',
                     help='launch-structure test without a GPU: gloo ranks on CPU, a no-op step; exercises the self-spawn, the barrier / '
                          'gather / max-over-ranks timed region and the JSON line (tests/test_bench_contract.py), measures nothing')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the per-kernel roofline, the auxiliary legs (fp32, ref_batch, '
+                         'ragged, f16, multisweep, with_h2d, stages, gather, refine, pdv) and the CPU baseline; the --no-* / --profile-frames '
+                         'options select among them')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the boxes (frames, NMS_POST_MAXSIZE, 9: box, score, label; rows past a frame\'s '
+                         'count zeroed) and counts (frames,) of the last timed step as DIR/boxes.npy and DIR/counts.npy (float32)')
     return ap.parse_args()
 
 
 def spawn_ranks(args):
     """`python bench.py --gpus N` outside a launcher: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1)
-    by re-executing under torch.distributed.run - the same command line the driver uses.  Fails loudly when the node has fewer GPUs."""
+    in a child process under torch.distributed.run - the same command line the driver uses - and exit with its status (a fresh
+    child, not exec: this process has opened the GPU runtime to count the devices).  Fails loudly when the node has fewer GPUs."""
     import socket
     if not args.stub:
         have = torch.cuda.device_count()
@@ -158,7 +169,9 @@ def spawn_ranks(args):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     log('starting %d ranks: %s' % (args.gpus, ' '.join(cmd[1:9])))
-    os.execvp(cmd[0], cmd)
+    import subprocess
+    sys.stdout.flush()
+    sys.exit(subprocess.call(cmd))
 
 
 class Case:
@@ -529,6 +542,21 @@ def main():
     case.check_overflow()
     n_boxes = case.counts.float().mean().item()
     log('timed region: %d steps x %d frames in %.3f s' % (K, B, dt))
+    if args.dump_outputs and rank == 0:
+        # the last timed step is i = W + K (W + 1 untimed steps first); streaming mode lands its results one step later, in slot i - 1
+        last = (W + K - (1 if streamer is not None else 0)) % K
+        if all_b is not None:              # N > 1: every rank's last step, from the boxes gathered inside the timed region
+            boxes = all_b.view(world, K, B, *all_b.shape[2:])[:, last].reshape(world * B, *all_b.shape[2:])
+            counts = all_c.view(world, K, B)[:, last].reshape(world * B)
+        else:
+            boxes, counts = case.results[last], case.counts[last]
+        boxes, counts = boxes.float().cpu().numpy().copy(), counts.cpu().numpy()
+        for j, n in enumerate(counts):
+            boxes[j, int(n):] = 0.0                                     # rows past a frame's count are not part of its result
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'boxes.npy'), boxes.astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, 'counts.npy'), counts.astype(np.float32))
+        log('outputs of step %d written to %s: boxes %s, counts %s' % (W + K, args.dump_outputs, boxes.shape, counts.shape))
 
     out = None
     dtype_names = {'f32': 'f32', 'f16x2': 'f32 as f16 pairs (hi+lo, 22-bit significand; 3 f16 MFMA per product, f32 accumulate)',
@@ -558,8 +586,9 @@ def main():
                        'mean_boxes_per_frame': round(n_boxes, 1), 'boxes_per_frame_min_max': [int(case.counts.min().item()), int(case.counts.max().item())]},
         }
 
+    # ---- --full only from here on (the headline line above is complete without it)
     # ---- roofline of the dominant kernel: HIP events around every conv launch, on the launch stream
-    if rank == 0 and args.profile_frames > 0:
+    if rank == 0 and args.full and args.profile_frames > 0:
         kern, roof, _ = case.kernel_profile(args.profile_frames)
         if roof:
             roof['frames_per_step'] = case.PB               # frames of the profiled pass (one sub-pass of the step)
@@ -570,7 +599,7 @@ def main():
         out['profiled_pass_frames'] = case.PB
 
     # ---- auxiliary legs (single GPU only): what the headline does not show
-    if rank == 0 and world == 1 and not args.no_aux and streamer is None:
+    if rank == 0 and world == 1 and args.full and not args.no_aux and streamer is None:
         sec = args.aux_seconds
         try:
             out['stages'] = case.stage_profile()
@@ -797,7 +826,7 @@ def main():
             torch.cuda.empty_cache()
 
     # ---- CPU baseline: the oracle (reference-semantics restatement) on this host's cores, bounded sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from tests.util import cpu_state_dict, oracle_detect       # oracle = checker/baseline only
         cores = min(usable_cores(), 32)
         torch.set_num_threads(cores)

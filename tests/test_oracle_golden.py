@@ -63,32 +63,37 @@ def test_rotated_iou_matches_reference_cpp(golden_dir):
     assert (iou > 0.7).sum() >= 20 and (iou > 0).sum() > 40
 
 
-def test_rotated_iou_against_live_reference_build():
+def test_rotated_iou_against_live_reference_build(golden_dir):
+    """oracle.c's rotated IoU and NMS sweep vs the reference's own iou3d_cpu.cpp: against its stored outputs on these seeded boxes
+    (tests/golden/gen_refbuild_golden.py) always, and against the live build (oracle/refbuild.py) where it exists."""
     from oracle import refbuild
-    if not os.path.isdir(refbuild.REF_SRC_DIR) and not os.path.exists(refbuild._SO):
-        pytest.skip('reference sources / prebuilt oracle/_ref not present')
-    from detzero_amd.synth import synth_boxes
-    a, b = synth_boxes(21, 120), synth_boxes(22, 90)
-    b[:25] = a[:25]
-    assert np.array_equal(refbuild.boxes_iou_bev_reference(a, b), cref.boxes_iou_bev(a, b))
-    keep_ref = refbuild.nms_with_reference_iou(a, 0.7)
-    keep = cref.nms_sorted(a, 0.7)
-    assert np.array_equal(keep, keep_ref)
+    from tests.golden.gen_refbuild_golden import iou_inputs
+    a, b = iou_inputs()
+    z = np.load(os.path.join(golden_dir, 'refbuild_golden.npz'))
+    iou, keep = cref.boxes_iou_bev(a, b), cref.nms_sorted(a, 0.7)
+    assert np.array_equal(iou, z['iou'])
+    assert np.array_equal(keep, z['keep'])
+    if os.path.isdir(refbuild.REF_SRC_DIR) or os.path.exists(refbuild._SO):
+        assert np.array_equal(refbuild.boxes_iou_bev_reference(a, b), iou)
+        keep_ref = refbuild.nms_with_reference_iou(a, 0.7)
+        assert np.array_equal(keep, keep_ref)
 
 
-def test_points_in_boxes_against_live_reference_build():
+def test_points_in_boxes_against_live_reference_build(golden_dir):
     """The inside test of oracle.c against the reference's own host implementation (roiaware_pool3d.cpp:248-295, compiled by
-    oracle/refbuild.py): identical flags when given the host twin's margin (1e-2); the GPU kernel's margin (1e-5,
+    oracle/refbuild.py; its stored flags on these seeded frames always, tests/golden/gen_refbuild_golden.py, and the live build where
+    it exists): identical flags when given the host twin's margin (1e-2); the GPU kernel's margin (1e-5,
     roiaware_pool3d_kernel.cu:26), which the product follows, keeps a subset."""
     from oracle import refbuild
-    if not os.path.isdir(refbuild.ROI_SRC_DIR) and not os.path.exists(refbuild._ROI_SO):
-        pytest.skip('reference sources / prebuilt oracle/_ref not present')
-    from detzero_amd.synth import synth_boxes, synth_waymo_frame
-    for seed, n, t in ((3, 60000, 80), (5, 5000, 7)):
-        pts = synth_waymo_frame(seed, n)[:, :3]
-        boxes = synth_boxes(seed + 2, t, 60.0)
-        boxes[:, 2] = np.random.default_rng(seed).uniform(-0.5, 1.5, t)
-        ref = refbuild.points_in_boxes_cpu_reference(pts, boxes)
+    from tests.golden.gen_refbuild_golden import PIB_CASES, pib_inputs
+    z = np.load(os.path.join(golden_dir, 'refbuild_golden.npz'))
+    live = os.path.isdir(refbuild.ROI_SRC_DIR) or os.path.exists(refbuild._ROI_SO)
+    for seed, n, t in PIB_CASES:
+        pts, boxes = pib_inputs(seed, n, t)
+        ref = np.zeros(tuple(z['pib%d_shape' % seed]), np.int32)
+        ref[tuple(z['pib%d_nonzero' % seed])] = 1
+        if live:
+            assert np.array_equal(refbuild.points_in_boxes_cpu_reference(pts, boxes), ref)
         assert ref.sum() > 0
         assert np.array_equal(cref.points_in_boxes_margin(pts, boxes, 1e-2), ref)
         tight = cref.points_in_boxes_v2(pts, boxes)

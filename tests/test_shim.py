@@ -206,25 +206,37 @@ def _stub_cfg():
     return cfg
 
 
-@pytest.mark.skipif(not has_ref, reason='reference tree not present')
-def test_reference_eval_loop_equals_restated_loop(tmp_path):
-    """The reference's eval_utils.eval_one_epoch (by path) and tests/eval_loop.py over the same loader and model:
-    identical result.pkl, identical recall dictionary."""
-    ref_eval = _reference_eval_utils()
+def _golden_eval_loop(golden_dir):
+    """The reference's eval_one_epoch over _StubDataset / _StubModel as tests/golden/gen_eval_loop_golden.py stored it:
+    (recall dictionary, result.pkl records)."""
+    g = np.load(os.path.join(golden_dir, 'eval_loop_golden.npz'))
+    ret = {str(k): v for k, v in zip(g['ret_keys'], g['ret_vals'].tolist())}
+    recs = [{str(k): g['rec%d_%s' % (i, k)] for k in g['rec%d_keys' % i]} for i in range(int(g['n_records']))]
+    return ret, recs
+
+
+def test_reference_eval_loop_equals_restated_loop(tmp_path, golden_dir):
+    """The reference's eval_utils.eval_one_epoch and tests/eval_loop.py over the same loader and model: identical result.pkl,
+    identical recall dictionary - against the reference's stored output (tests/golden/gen_eval_loop_golden.py) always, and
+    against the reference's file run by path where the tree exists."""
     from tests import eval_loop as my_eval
     ds = _StubDataset()
     loader = torch.utils.data.DataLoader(ds, batch_size=2, collate_fn=ds.collate_batch)
     logger = logging.getLogger('shim-eval')
-    r1 = ref_eval.eval_one_epoch(_stub_cfg(), _StubModel(), loader, 'x', logger, result_dir=Path(tmp_path / 'ref'), save_tb=True)
     r2 = my_eval.eval_one_epoch(_stub_cfg(), _StubModel(), loader, 'x', logger, result_dir=Path(tmp_path / 'mine'))
-    assert r1 == r2 and r1['n'] == 5 and r1['recall/rcnn_0.3'] == 0.5
-    a = pickle.load(open(tmp_path / 'ref' / 'result.pkl', 'rb'))
     b = pickle.load(open(tmp_path / 'mine' / 'result.pkl', 'rb'))
-    assert len(a) == len(b) == 5
-    for x, y in zip(a, b):
-        assert sorted(x) == sorted(y)
-        for k in x:
-            assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), k
+    runs = [_golden_eval_loop(golden_dir)]
+    if has_ref:
+        ref_eval = _reference_eval_utils()
+        r1 = ref_eval.eval_one_epoch(_stub_cfg(), _StubModel(), loader, 'x', logger, result_dir=Path(tmp_path / 'ref'), save_tb=True)
+        runs.append((r1, pickle.load(open(tmp_path / 'ref' / 'result.pkl', 'rb'))))
+    for r1, a in runs:
+        assert r1 == r2 and r1['n'] == 5 and r1['recall/rcnn_0.3'] == 0.5
+        assert len(a) == len(b) == 5
+        for x, y in zip(a, b):
+            assert sorted(x) == sorted(y)
+            for k in x:
+                assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), k
 
 
 # ------------------------------------------------------------------------------------------------ GPU

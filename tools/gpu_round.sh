@@ -1,6 +1,6 @@
 #!/bin/bash
 # The evidence set of a round on ONE GPU box (replaces gpu_round2/3/4.sh, gpu_profiles.sh, gpu_pmc*.sh, gpu_trace*.sh, gpu_x_diag.sh,
-# gpu_pdv_prof.sh of earlier rounds): gpu test-suite, smoke, the default bench line (all legs), rocprofv3 kernel trace of the headline
+# gpu_pdv_prof.sh of earlier rounds): gpu test-suite, smoke, the full bench line (bench.py --full: all legs), rocprofv3 kernel trace of the headline
 # command, HBM-side PMC passes (FETCH_SIZE / WRITE_SIZE, separate passes - never together with a trace domain) and the SQ matrix-pipe
 # counters of the same command, the per-layer sparse benchmark of both engines, the x-run kernel's in-kernel cycle accounting
 # (diag build), the refiner and two-stage (PDV) benches with their traces.
@@ -31,7 +31,7 @@ if has tests; then
   echo "==== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -4 | tee $O/${TAG}_smoke.txt
 fi
 if has bench; then
-  echo "==== bench (default command)"; timeout 900 python bench.py 2> $O/${TAG}_bench.err > $O/${TAG}_bench_graph.json; tail -14 $O/${TAG}_bench.err
+  echo "==== bench (--full)"; timeout 900 python bench.py --full 2> $O/${TAG}_bench.err > $O/${TAG}_bench_graph.json; tail -14 $O/${TAG}_bench.err
 fi
 if has trace; then trace bench_eager20 python $ROOT/bench.py $COMMON; fi
 if has pmc; then
