@@ -187,6 +187,10 @@ typedef struct dz_conv2d_desc {
     int groups, cout_pad;
     int g_cout[8];        /* valid output channels of each group                               */
     int g_ooff[8];        /* output channel offset of each group (added to out_coff)           */
+    /* A launch writes exactly channels [out_coff + g_ooff[g], + g_cout[g]) of the output pixels it enumerates, in every engine
+     * and output format: never the zero border, other channels of the pixel, the pad channels g_cout .. cout_pad - 1 of a group
+     * (pair16 included: pair16 output has g_cout % 8 == 0, so a written 8-channel group is always a whole one), the pixels of
+     * other phases, or - with in_tiles on the resident-tile kernel - the pixels of tiles not listed (tests/test_gpu_dense_conv.py) */
     int relu;
     const float *group_shift; /* optional (n_row_groups, cout_pad): added to the accumulator BEFORE scale/shift, */
     int group_rows;           /* row group = output row / group_rows (per-object bias of the PointNet concat)   */
