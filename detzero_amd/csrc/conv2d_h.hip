@@ -5,15 +5,13 @@
 // Reference: detection/detzero_det/models/centerpoint_modules/backbone2d.py:33-120, center_head.py:14-48, :81-102.
 // Input image and weights are pair16; the output image is pair16 (feeds the next layer) or plain fp32 (the
 // last head convolution, which feeds the decoder).
-#include <stdlib.h>
-
 #include "hgemm.h"
 
 namespace dz {
 
 // conv3x3_h.hip: 3x3 stride-1 layers with enough tiles run on the image-tile-resident kernel
 int conv3x3_h_variant(const dz_conv2d_desc &p);
-int conv3x3_h_launch(const dz_conv2d_desc &p, int math, int out_f32, size_t w_bytes, hipStream_t stream);
+int conv3x3_h_launch(const dz_conv2d_desc &p, int bc, int math, int out_f32, size_t w_bytes, hipStream_t stream);
 
 template <class T, class M, bool OUT_F32, int NS>
 __global__ __launch_bounds__(256) void k_conv2d_h(dz_conv2d_desc p, long m_total, unsigned int in_bytes, unsigned int w_bytes) {
@@ -241,18 +239,16 @@ static int launch_conv_h(const dz_conv2d_desc &p, size_t w_bytes, hipStream_t st
     return DZ_OK;
 }
 
-// variant ids: BP (pixels) x BC (channels) x KC
-enum ConvHVariant { CH_NONE = 0, CH_128_128, CH_128_64, CH_64_128, CH_64_64, CH_128_32 };
-static const char *kConvHVariantName[] = {"none", "k_conv2d_h<128x128x32>", "k_conv2d_h<128x64x32>", "k_conv2d_h<64x128x32>",
-                                          "k_conv2d_h<64x64x32>", "k_conv2d_h<128x32x32>"};
+// variants of the split path: BP (pixels) x BC (channels) x KC of k_conv2d_h, tile rows x 32 x BC of k_conv3x3_h
+enum ConvHVariant { CH_NONE = 0, CH_128_128, CH_128_64, CH_64_128, CH_64_64, CH_128_32, CH_C3_128, CH_C3_64, CH_C3_32 };
+static const char *const kConvHVariantName[] = {"none", "k_conv2d_h<128x128x32>", "k_conv2d_h<128x64x32>", "k_conv2d_h<64x128x32>",
+                                                "k_conv2d_h<64x64x32>", "k_conv2d_h<128x32x32>", "k_conv3x3_h<8x32x128>",
+                                                "k_conv3x3_h<8x32x64>", "k_conv3x3_h<16x32x32>"};
 
 static ConvHVariant conv2d_h_select(const dz_conv2d_desc &p) {
     if (p.cin % 32 != 0) return CH_NONE;
     const long m_total = (long)p.batch * p.ho * p.wo;
     if (p.cout_pad % 64 != 0) return p.cout_pad % 32 == 0 ? CH_128_32 : CH_NONE;
-    // development knob: force a tile shape (1 = 128 x 128, 2 = 128 x 64, 3 = 64 x 128, 4 = 64 x 64) for the layers it divides
-    static const int forced = getenv("DZ_TUNE_CONV2D_H") ? atoi(getenv("DZ_TUNE_CONV2D_H")) : 0;
-    if (forced >= 1 && forced <= 4 && p.cout_pad % (forced == 1 || forced == 3 ? 128 : 64) == 0 && m_total >= 4096) return (ConvHVariant)forced;
     // chip fill: two workgroups are resident per CU; prefer the largest tile that keeps >= ~90 % of the slots busy
     struct Cand { ConvHVariant v; int bp, bc; double eff; };
     static const Cand cands[4] = {{CH_128_128, 128, 128, 1.00}, {CH_128_64, 128, 64, 0.90}, {CH_64_128, 64, 128, 0.88}, {CH_64_64, 64, 64, 0.78}};
@@ -270,18 +266,36 @@ static ConvHVariant conv2d_h_select(const dz_conv2d_desc &p) {
     return pick;
 }
 
+// The one decision of the split path: which kernel and tile runs a layer, or why none does (`why`: a printf format of cin and
+// cout_pad, set when v == CH_NONE).  dz_conv2d_forward_split launches what it returns and dz_conv2d_variant_split reports it.
+struct ConvHChoice { ConvHVariant v; const char *why; };
+
+static ConvHChoice conv_h_select(const dz_conv2d_desc &p, int out_f32) {
+    const int bc3 = conv3x3_h_variant(p);
+    if (p.in_rowidx && (!bc3 || out_f32))
+        return {CH_NONE, "dz_conv2d_forward_split: in_rowidx (sparse input) is implemented for 3 x 3 stride-1 layers with 128-channel output tiles, "
+                         "two z slabs (cin == 2 * in_row_channels) and pair16 output"};
+    // in_tiles lists 8 x 32-pixel tiles (dz_bev_tile_list): only the 64 / 128-channel variants of k_conv3x3_h walk that grid.  The
+    // 32-channel variant has 16 x 32 tiles - a list there would be decoded on the wrong grid (wrong pixels): refused.  A layer
+    // that no tile variant takes (small images, strided layers) runs on the generic kernel, which computes EVERY pixel: the list is
+    // ignored there (results stay correct; the caller's fill of the skipped tiles rewrites what was computed).
+    if (p.in_tiles && bc3 && !((bc3 == 64 || bc3 == 128) && !out_f32))
+        return {CH_NONE, "dz_conv2d_forward_split: in_tiles lists 8 x 32 pixel tiles; this layer runs on the 32-channel tile kernel (16 x 32 tiles) - pass no list"};
+    // fp32 output: 32-channel tiles only (the 64 / 128-channel fp32 instances were never launched and spilled: round-4 review)
+    if (bc3 && (!out_f32 || bc3 == 32)) return {bc3 == 128 ? CH_C3_128 : bc3 == 64 ? CH_C3_64 : CH_C3_32, nullptr};
+    const ConvHVariant v = conv2d_h_select(p);
+    return {v, v != CH_NONE ? nullptr : "dz_conv2d_forward_split: unsupported channels cin=%d cout_pad=%d (cin %% 32, cout_pad %% 32 required)"};
+}
+
 template <class M, bool OUT_F32>
-static int conv2d_h_dispatch(const dz_conv2d_desc &p, size_t w_bytes, hipStream_t stream) {
-    switch (conv2d_h_select(p)) {
+static int conv2d_h_launch(ConvHVariant v, const dz_conv2d_desc &p, size_t w_bytes, hipStream_t stream) {
+    switch (v) {
         case CH_128_128: return launch_conv_h<HTile<128, 128, 32, 2, 2>, M, OUT_F32, 2>(p, w_bytes, stream);
         case CH_128_64: return launch_conv_h<HTile<128, 64, 32, 2, 2>, M, OUT_F32, 3>(p, w_bytes, stream);
         case CH_64_128: return launch_conv_h<HTile<64, 128, 32, 2, 2>, M, OUT_F32, 3>(p, w_bytes, stream);
         case CH_64_64: return launch_conv_h<HTile<64, 64, 32, 2, 2>, M, OUT_F32, 3>(p, w_bytes, stream);
-        case CH_128_32: return launch_conv_h<HTile<128, 32, 32, 4, 1>, M, OUT_F32, 3>(p, w_bytes, stream);
-        default: break;
+        default: return launch_conv_h<HTile<128, 32, 32, 4, 1>, M, OUT_F32, 3>(p, w_bytes, stream);     // CH_128_32
     }
-    set_error("dz_conv2d_forward_split: unsupported channels cin=%d cout_pad=%d (cin %% 32, cout_pad %% 32 required)", p.cin, p.cout_pad);
-    return DZ_ERR_UNSUPPORTED;
 }
 
 }  // namespace dz
@@ -318,31 +332,20 @@ int dz_conv2d_forward_split(const dz_conv2d_desc *d, int math, int out_f32, void
                  "dz_conv2d_forward_split: output leaves the output image");
     if ((long)d->batch * d->ho * d->wo == 0) return DZ_OK;
     const size_t w_bytes = (size_t)d->groups * d->kh * d->kw * d->cout_pad * d->cin * sizeof(float);
-    if (d->in_rowidx) {
-        DZ_CHECK_ARG(d->in_row_channels >= 32 && d->in_rows >= 0, "dz_conv2d_forward_split: in_rowidx needs in_row_channels / in_rows");
-        if (!conv3x3_h_variant(*d) || out_f32) {
-            set_error("dz_conv2d_forward_split: in_rowidx (sparse input) is implemented for 3 x 3 stride-1 layers with 128-channel output tiles, "
-                      "two z slabs (cin == 2 * in_row_channels) and pair16 output");
-            return DZ_ERR_UNSUPPORTED;
-        }
-    }
-    {
-        const int bc3 = conv3x3_h_variant(*d);
-        // in_tiles lists 8 x 32-pixel tiles (dz_bev_tile_list): only the 64 / 128-channel variants of k_conv3x3_h walk that grid.  The
-        // 32-channel variant has 16 x 32 tiles - a list there would be decoded on the wrong grid (wrong pixels): refused.  A layer
-        // that no tile variant takes (small images, strided layers) runs on the generic kernel, which computes EVERY pixel: the list is
-        // ignored there (results stay correct; the caller's fill of the skipped tiles rewrites what was computed).
-        if (d->in_tiles && bc3 && !((bc3 == 64 || bc3 == 128) && !out_f32)) {
-            set_error("dz_conv2d_forward_split: in_tiles lists 8 x 32 pixel tiles; this layer runs on the 32-channel tile kernel (16 x 32 tiles) - pass no list");
-            return DZ_ERR_UNSUPPORTED;
-        }
-        if (bc3 && (!out_f32 || bc3 == 32)) return conv3x3_h_launch(*d, math, out_f32, w_bytes, stream);      // (fp32 output: 32-channel tiles only)
+    DZ_CHECK_ARG(!d->in_rowidx || (d->in_row_channels >= 32 && d->in_rows >= 0), "dz_conv2d_forward_split: in_rowidx needs in_row_channels / in_rows");
+    const ConvHChoice c = conv_h_select(*d, out_f32);
+    switch (c.v) {
+        case CH_NONE: set_error(c.why, d->cin, d->cout_pad); return DZ_ERR_UNSUPPORTED;
+        case CH_C3_128: return conv3x3_h_launch(*d, 128, math, out_f32, w_bytes, stream);
+        case CH_C3_64: return conv3x3_h_launch(*d, 64, math, out_f32, w_bytes, stream);
+        case CH_C3_32: return conv3x3_h_launch(*d, 32, math, out_f32, w_bytes, stream);
+        default: break;
     }
     if (math == DZ_MATH_F16X2)
-        return out_f32 ? conv2d_h_dispatch<MathF16, true>(*d, w_bytes, stream) : conv2d_h_dispatch<MathF16, false>(*d, w_bytes, stream);
+        return out_f32 ? conv2d_h_launch<MathF16, true>(c.v, *d, w_bytes, stream) : conv2d_h_launch<MathF16, false>(c.v, *d, w_bytes, stream);
     if (math == DZ_MATH_F16)
-        return out_f32 ? conv2d_h_dispatch<MathF16H, true>(*d, w_bytes, stream) : conv2d_h_dispatch<MathF16H, false>(*d, w_bytes, stream);
-    return out_f32 ? conv2d_h_dispatch<MathBF16, true>(*d, w_bytes, stream) : conv2d_h_dispatch<MathBF16, false>(*d, w_bytes, stream);
+        return out_f32 ? conv2d_h_launch<MathF16H, true>(c.v, *d, w_bytes, stream) : conv2d_h_launch<MathF16H, false>(c.v, *d, w_bytes, stream);
+    return out_f32 ? conv2d_h_launch<MathBF16, true>(c.v, *d, w_bytes, stream) : conv2d_h_launch<MathBF16, false>(c.v, *d, w_bytes, stream);
 }
 
 int dz_linear_forward_split(const float *x, long rows, int cin, int x_stride, const float *w, int cout, int cout_pad, const float *scale,
@@ -381,11 +384,8 @@ int dz_linear_forward_split(const float *x, long rows, int cin, int x_stride, co
     return DZ_OK;
 }
 
-const char *dz_conv2d_variant_split(const dz_conv2d_desc *d) {
-    if (!d) return "none";
-    const int bc = conv3x3_h_variant(*d);
-    if (bc) return bc == 128 ? "k_conv3x3_h<8x32x128>" : bc == 64 ? "k_conv3x3_h<8x32x64>" : "k_conv3x3_h<16x32x32>";
-    return kConvHVariantName[conv2d_h_select(*d)];
+const char *dz_conv2d_variant_split(const dz_conv2d_desc *d, int out_f32) {
+    return d ? kConvHVariantName[conv_h_select(*d, out_f32).v] : "none";
 }
 
 }  // extern "C"

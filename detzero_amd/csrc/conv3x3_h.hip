@@ -12,10 +12,6 @@
 //   waves: 4 (pairs of image rows) x 2 (halves of BC); wave tile = 2 x 32 pixels x BC/2 channels.
 //   per channel chunk: 9 taps, fully unrolled (stage indices, LDS offsets and vmcnt counts are static);
 //   the next chunk's input tile is prefetched into registers during the taps and swapped in at the chunk boundary.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "hgemm.h"
 
 namespace dz {
@@ -26,38 +22,36 @@ constexpr int C3_PXW = C3_TW + 2;
 constexpr int C3_NS = 3;                                          // weight stages in flight (9 taps % 3 == 0)
 using v2u = __attribute__((ext_vector_type(2))) unsigned int;
 
-// NT threads: 512 = 4 (pairs of image rows) x 2 (halves of BC) waves, one workgroup per CU; 256 = 4 x 1 waves, TWO workgroups
-// per CU whose barrier phases and epilogues interleave on the matrix pipe
-// PT = image rows per wave: 2 at two waves per SIMD; 3 (with NT = 256 and all BC channels in every wave: 3 x 4 fragments, 12
-// accumulators) at ONE wave per SIMD with the whole register file - fewer LDS fragment reads and staged bytes per MFMA
+// C3_NT = 512 threads: 4 (pairs of image rows) x 2 (halves of BC) waves, one workgroup per CU, two waves per SIMD; PT = 2 image
+// rows per wave.  Measured and not adopted (the code was last in c5e05cd): two 256-thread workgroups per CU, one wave
+// per SIMD with 3 x 4 fragments, and the direct-to-LDS 2 x 4-fragment variant.
 // BC = 32 (WC = 1, 8 row pairs: 16 x 32-pixel tiles): grouped convolutions with few output channels per group - the head's output
 // layer (6 groups of 64 -> 1..3 channels): memory-bound, every group reads its 64-channel slice of the input exactly once
-template <int BC, int NT, int PT_>
+constexpr int C3_NT = 512;
+template <int BC>
 struct C3Cfg {
-    static constexpr int PT = PT_;
-    static constexpr int WC = (PT == 2 && BC >= 64) ? NT / 256 : 1;             // channel splits over waves
-    static constexpr int WP = NT / 64 / WC;                       // row groups
+    static constexpr int PT = 2;
+    static constexpr int WC = BC >= 64 ? 2 : 1;                   // channel splits over waves
+    static constexpr int WP = C3_NT / 64 / WC;                    // row groups
     static constexpr int TH = WP * PT;                            // tile height
     static constexpr int CT = BC / (32 * WC);                     // 32-channel fragments per wave
     static constexpr int PXH = TH + 2, PX_ROWS = C3_PXW * PXH, PX_PIECES = PX_ROWS * (C3_KC / 4);
-    static constexpr int PXPT = (PX_PIECES + NT - 1) / NT;        // input pieces per thread (last partly idle)
+    static constexpr int PXPT = (PX_PIECES + C3_NT - 1) / C3_NT;  // input pieces per thread (last partly idle)
     static constexpr int W_PIECES = BC * (C3_KC / 4);
-    static constexpr int WPT = (W_PIECES + NT - 1) / NT;          // weight pieces per thread per tap (2 or 1; BC = 32: 1, half the threads idle)
+    static constexpr int WPT = (W_PIECES + C3_NT - 1) / C3_NT;    // weight pieces per thread per tap (2 or 1; BC = 32: 1, half the threads idle)
     static constexpr int W_U4 = BC * C3_ROW_U4;                   // one weight buffer
     static constexpr int LDS_MAIN_BYTES = (PX_ROWS * C3_ROW_U4 + 2 * W_U4) * 16;
     // epilogue staging window of a wave: 32 pixels x SG 8-channel groups (32 bytes each) + 16 bytes of padding
-    static constexpr int SG = (NT == 512 && PT == 2) ? 4 : 2;
+    static constexpr int SG = 4;
     static constexpr int STG_ROW = SG * 32 + 16, STG_BYTES = 32 * STG_ROW;
-    static constexpr int LDS_STG_END = LDS_MAIN_BYTES + (NT / 64) * STG_BYTES;
+    static constexpr int LDS_STG_END = LDS_MAIN_BYTES + (C3_NT / 64) * STG_BYTES;
     static constexpr int LDS_BYTES = LDS_STG_END + 2 * BC * 4;                 // + BatchNorm scale / shift of the channel tile
     static_assert(BC == 32 || BC == 64 || BC == 128, "BC is 32, 64 or 128");
     static_assert(CT == 1 || CT == 2 || CT == 4, "1, 2 or 4 channel fragments per wave");
     static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit the LDS of a CU");
-    static_assert(W_PIECES % NT == 0 || W_PIECES < NT, "weight slice must split evenly over the threads");
+    static_assert(W_PIECES % C3_NT == 0 || W_PIECES < C3_NT, "weight slice must split evenly over the threads");
 };
 
-// DIAG (-DDZ_C3_DIAG builds only, timing experiments, results are garbage): bit 0 = no per-tap barriers, 1 = no weight LDS
-// stores, 2 = no fragment LDS reads, 3 = no global loads, 4 = no MFMAs, 5 = no epilogue
 // SPARSE (dz_conv2d_desc.in_rowidx, round 5): the input image is never materialised.  `in` holds the rows of a sparse level
 // (in_row_channels pair16 channels each) and in_rowidx the row of every (pixel, z slab) of the zero-bordered image, -1 = empty:
 // input channel chunk kc of a pixel is chunk kc % (nk / 2) of the row of slab kc / (nk / 2).  A thread keeps the two row indices of
@@ -65,12 +59,12 @@ struct C3Cfg {
 // needs the current tile's indices, one channel chunk before the next tile's first prefetch reads them); everything downstream of
 // the input prefetch - LDS tile, fragments, MFMAs, epilogue - is the dense kernel.  This is HeightCompression
 // (height_compression.py:20-24) + the ZeroPad2d of the first BEV block (backbone2d.py:41-46) fused into that block's convolution.
-template <int BC, class M, bool OUT_F32, int NT = 512, int DIAG = 0, int PT = 2, bool SPARSE = false>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 : 1, PT == 2 ? 2 : 1))) void k_conv3x3_h(dz_conv2d_desc p, int tiles_x, int tiles_y, unsigned int in_bytes,
-                                                          unsigned int w_bytes, int skew_ticks, int q_sa, int q_sb, float q_act, int pair0, int ny) {
-    using C = C3Cfg<BC, NT, PT>;
-    constexpr int CT = C::CT, WPT = C::WPT, C3_THREADS = NT, C3_PXPT = C::PXPT, WC = C::WC, C3_TH = C::TH, C3_PX_ROWS = C::PX_ROWS,
-                  C3_PX_PIECES = C::PX_PIECES;
+template <int BC, class M, bool OUT_F32, bool SPARSE = false>
+__global__ __launch_bounds__(C3_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_conv3x3_h(dz_conv2d_desc p, int tiles_x, int tiles_y, unsigned int in_bytes,
+                                                                                                unsigned int w_bytes, int pair0, int ny) {
+    using C = C3Cfg<BC>;
+    constexpr int CT = C::CT, PT = C::PT, WPT = C::WPT, C3_PXPT = C::PXPT, WC = C::WC, C3_TH = C::TH,
+                  C3_PX_ROWS = C::PX_ROWS, C3_PX_PIECES = C::PX_PIECES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     v4u *const px_s = reinterpret_cast<v4u *>(smem_raw);                     // [340][ROW_U4]
     v4u *const w_s = px_s + C3_PX_ROWS * C3_ROW_U4;                          // [2][BC][ROW_U4]
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
     // A workgroup keeps ONE channel tile (its weight stream simply wraps around from tile to tile) and the load pipeline
     // never drains between tiles: the next tile's input is prefetched during the last channel chunk of the current one.
     // this launch covers the (group, channel tile) pairs pair0 .. pair0 + ny - 1 of the layer's ntn * groups (all of them unless their
-    // number does not divide the 32 workgroups of an XCD: launch_c3_nt)
+    // number does not divide the 32 workgroups of an XCD: launch_c3)
     const int ntn = p.cout_pad / BC, nty = ny;                  // channel tiles per group; pairs of this launch
     // pixel tiles: all of them, or - with a tile list (dz_bev_tile_list) - the tiles to run; the others' result (the layer's zero-input
     // response) is written by dz_bev_fill_empty_tiles
@@ -96,10 +90,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
     const int tstep = nj / nty;                                   // workgroups of this XCD that share my channel tile
     int tile = band_lo + jloc / nty;
     if (tstep == 0 || tile >= band_hi) return;
-    if (NT == 256 && skew_ticks > 0 && jloc >= nj / 2) {          // second workgroup of a CU: start out of phase with the first
-        const unsigned long long t0 = wall_clock64();
-        while (wall_clock64() - t0 < (unsigned long long)skew_ticks) __builtin_amdgcn_s_sleep(32);
-    }
 
     const srsrc_t prsrc = make_srsrc(p.in, in_bytes);
     const srsrc_t crsrc = make_srsrc(p.w, w_bytes);
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
     unsigned int cvoff[WPT];
 #pragma unroll
     for (int i = 0; i < WPT; ++i) {
-        const int idx = tid + i * C3_THREADS;
+        const int idx = tid + i * C3_NT;
         cvoff[i] = idx < C::W_PIECES ? (unsigned int)((((long)grp * 9 * p.cout_pad + n0 + idx / (C3_KC / 4)) * p.cin + (idx % (C3_KC / 4)) * 4) * 4)
                                      : OOB_OFFSET;
     }
@@ -155,7 +145,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
         // chunk = kc * 9 + tap of the current tile; past its end the stream wraps to the next tile's chunks (same
         // weights), or - after the last tile - to out-of-range offsets (zeros come back, nothing is fetched; the
         // per-wave load counts stay uniform)
-        if constexpr (DIAG & 8) return;
         if (chunk >= nchunks) chunk = has_next ? chunk - nchunks : -1;
         const int kc = chunk / 9, tap = chunk - kc * 9;
         const unsigned int add = chunk >= 0 ? (unsigned int)tap * tap_bytes + (unsigned int)(kc * C3_KC * 4) : OOB_OFFSET;
@@ -176,7 +165,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
             unsigned int okm = 0u;
 #pragma unroll
             for (int i = 0; i < C3_PXPT; ++i) {
-                const int r = pr + i * (C3_THREADS / (C3_KC / 4));
+                const int r = pr + i * (C3_NT / (C3_KC / 4));
                 const int ry = r / C3_PXW, rx = r - ry * C3_PXW;
                 const bool ok = live && r < C3_PX_ROWS && ry < g.rows && rx < g.cols;
                 const unsigned int off = ok ? (g.base + (unsigned int)(ry * p.in_wp + rx)) * 8u : OOB_OFFSET;
@@ -197,7 +186,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
     };
     auto issue_px = [&](int kc) {
         // input tile of channel chunk kc; kc == nk: chunk 0 of the next tile
-        if constexpr (DIAG & 8) return;
         if constexpr (SPARSE) {
             const bool cur = kc < nk;
             const bool any = cur || has_next;
@@ -221,13 +209,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
         asm volatile("" : "+v"(pr));             // keeps the per-piece offsets from being hoisted into registers for the whole loop
 #pragma unroll
         for (int i = 0; i < C3_PXPT; ++i) {
-            const int r = pr + i * (C3_THREADS / (C3_KC / 4));
+            const int r = pr + i * (C3_NT / (C3_KC / 4));
             const int ry = r / C3_PXW, rx = r - ry * C3_PXW;
             const bool ok = any && r < C3_PX_ROWS && ry < g.rows && rx < g.cols;
             const unsigned int off = ok ? (unsigned int)(((ry * p.in_wp + rx) * p.in_cstride + pq * 4) * 4) : OOB_OFFSET;
-            // one wave per SIMD (PT == 3): the prefetched tile waits in the accumulation registers the 12 accumulators leave free
-            if constexpr (PT == 2) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(pst[i]) : "v"(off), "s"(prsrc), "s"(sbase));
-            else asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=a"(pst[i]) : "v"(off), "s"(prsrc), "s"(sbase));
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(pst[i]) : "v"(off), "s"(prsrc), "s"(sbase));
         }
     };
     auto own_w = [&](v4u (&st)[WPT]) {
@@ -235,19 +221,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
         for (int i = 0; i < WPT; ++i) asm volatile("" : "+v"(st[i]));
     };
     auto store_w = [&](const v4u (&st)[WPT], int buf) {
-        if constexpr (DIAG & 2) return;
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
-            const int idx = tid + i * C3_THREADS;
-            if (C::W_PIECES % NT == 0 || idx < C::W_PIECES) w_s[buf * C::W_U4 + (idx / (C3_KC / 4)) * C3_ROW_U4 + idx % (C3_KC / 4)] = st[i];
+            const int idx = tid + i * C3_NT;
+            if (C::W_PIECES % C3_NT == 0 || idx < C::W_PIECES) w_s[buf * C::W_U4 + (idx / (C3_KC / 4)) * C3_ROW_U4 + idx % (C3_KC / 4)] = st[i];
         }
     };
     auto store_px = [&]() {
 #pragma unroll
         for (int i = 0; i < C3_PXPT; ++i) {
-            if constexpr (PT == 2) asm volatile("" : "+v"(pst[i]));
-            else asm volatile("" : "+a"(pst[i]));
-            const int idx = tid + i * C3_THREADS;
+            asm volatile("" : "+v"(pst[i]));
+            const int idx = tid + i * C3_NT;
             if (idx < C3_PX_PIECES) px_s[(idx / (C3_KC / 4)) * C3_ROW_U4 + idx % (C3_KC / 4)] = pst[i];
         }
     };
@@ -264,41 +248,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
     const int kg2 = (lane >> 5) * 2;
     const int pbase = ((PT * wp) * C3_PXW + (lane & 31)) * C3_ROW_U4 + kg2;
     const int wbase = (wc * CT * 32 + (lane & 31)) * C3_ROW_U4 + kg2;
-    struct Frag { v4u p_hi[PT], p_lo[PT], c_hi[CT], c_lo[CT], p_x[PT], c_x[CT]; };        // (p_x, c_x: second fp8 piece, q16 prototype)
+    struct Frag { v4u p_hi[PT], p_lo[PT], c_hi[CT], c_lo[CT]; };
     auto load_frag = [&](Frag &f, int tap, int buf, int q) {
-        if constexpr (DIAG & 4) {
-#pragma unroll
-            for (int i = 0; i < PT; ++i) asm volatile("" : "+v"(f.p_hi[i]), "+v"(f.p_lo[i]));
-#pragma unroll
-            for (int i = 0; i < CT; ++i) asm volatile("" : "+v"(f.c_hi[i]), "+v"(f.c_lo[i]));
-            return;
-        }
         const int ky = tap / 3, kx = tap - ky * 3;
-        if constexpr (M::Q16) {
-            // q16 chunk row (128 bytes = 8 pieces): fp16 hi of channels 8i..8i+7 in piece i (0..3), hi8 in pieces 4-5, lo8 in 6-7.
-            // k-step q of the fp16 MFMA: piece 2q + kg.  The fp8 MFMA (issued with k-step 1) covers the 32 channels twice: its
-            // k-block 0 (lanes 0-31) multiplies lo8(x) by hi8(w), block 1 (lanes 32-63) hi8(x) by lo8(w).
-            const int kb = lane >> 5;
-            const v4u *pp = px_s + (pbase - kg2) + (ky * C3_PXW + kx) * C3_ROW_U4;
-            const v4u *cp = w_s + buf * C::W_U4 + (wbase - kg2);
-#pragma unroll
-            for (int pt = 0; pt < PT; ++pt) {
-                f.p_hi[pt] = pp[pt * C3_PXW * C3_ROW_U4 + 2 * q + kb];
-                if (q == 1) {
-                    f.p_lo[pt] = pp[pt * C3_PXW * C3_ROW_U4 + (kb ? 4 : 6)];
-                    f.p_x[pt] = pp[pt * C3_PXW * C3_ROW_U4 + (kb ? 5 : 7)];
-                }
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                f.c_hi[ct] = cp[ct * 32 * C3_ROW_U4 + 2 * q + kb];
-                if (q == 1) {
-                    f.c_lo[ct] = cp[ct * 32 * C3_ROW_U4 + (kb ? 6 : 4)];
-                    f.c_x[ct] = cp[ct * 32 * C3_ROW_U4 + (kb ? 7 : 5)];
-                }
-            }
-            return;
-        }
         const v4u *pp = px_s + pbase + (ky * C3_PXW + kx) * C3_ROW_U4 + q * 4;
 #pragma unroll
         for (int pt = 0; pt < PT; ++pt) {
@@ -312,27 +264,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
             f.c_lo[ct] = cp[ct * 32 * C3_ROW_U4 + 1];
         }
     };
-    auto mma = [&](const Frag &f, int q = 0) {
-        if constexpr (M::Q16) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = M::mma(f.c_hi[ct], f.p_hi[pt], acc[ct][pt]);
-            if (q == 1) {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = mma_f8(f.c_lo[ct], f.c_x[ct], f.p_lo[pt], f.p_x[pt], acc[ct][pt], q_sa, q_sb);
-            }
-            return;
-        }
-        if constexpr (DIAG & 16) {
-#pragma unroll
-            for (int i = 0; i < PT; ++i) asm volatile("" ::"v"(f.p_hi[i]), "v"(f.p_lo[i]));
-#pragma unroll
-            for (int i = 0; i < CT; ++i) asm volatile("" ::"v"(f.c_hi[i]), "v"(f.c_lo[i]));
-            return;
-        }
+    auto mma = [&](const Frag &f) {
         // term-major: consecutive MFMAs go to different accumulators (measured 1.7 % faster than three in a row into the same
         // one); each accumulator still receives lo.hi, hi.lo, hi.hi in that order, so the result does not depend on it
 #pragma unroll
@@ -384,13 +316,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
             // ---- phase 1: k-step-1 fragments, weights of chunk c+1 to the other LDS buffer, MFMAs of k-step 0
             load_frag(f1, t, buf, 1);
             // loads younger than chunk c+1's: chunks c+2, c+3, plus this chunk's input prefetch while it is the youngest
-            if constexpr (!(DIAG & 8)) {
-                if (t >= 1 && t <= 3) {
-                    // (SPARSE: in chunk nk - 2 the next tile's PXPT index loads are in flight too, younger than the input prefetch)
-                    if (SPARSE && kc == nk - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW2 + 2 * C3_PXPT));
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW2 + C3_PXPT));
-                } else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW2));
-            }
+            if (t >= 1 && t <= 3) {
+                // (SPARSE: in chunk nk - 2 the next tile's PXPT index loads are in flight too, younger than the input prefetch)
+                if (SPARSE && kc == nk - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW2 + 2 * C3_PXPT));
+                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW2 + C3_PXPT));
+            } else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW2));
             if constexpr (SPARSE) {
                 if (t == 0) own_idx();           // (the indices issued a chunk ago are covered by the wait above)
             }
@@ -401,7 +331,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
             // per tap), so memory instructions issued in a block of their own would leave the matrix pipe idle
             interleave_hint<0x100, M::TERMS == 1 ? (PT + CT) : 2 * (PT + CT), 1>();
             interleave_hint<0x200, WPT, 1>();
-            if constexpr (!(DIAG & 1)) __syncthreads();
+            __syncthreads();
             if (t == 8) {
                 // channel-chunk boundary: every wave has finished reading the old input tile (its last reads were the
                 // k-step-1 fragments above, complete before the barrier); swap in the prefetched tile
@@ -418,23 +348,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
                     if (kc == nk - 2) issue_idx(geo_next, has_next);
                 }
             }
-            mma(f1, 1);
+            mma(f1);
             interleave_hint<0x100, M::TERMS == 1 ? (PT + CT) : 2 * (PT + CT), 1>();
         }
     }
     tile_origin(id_cur, x0, y0, b);
 
     // ---- epilogue: 32x32 accumulator: pixel column = lane & 31, channel = 8*(reg>>2) + 4*(lane>>5) + (reg&3)
-    if constexpr (DIAG & 32) {                                   // no epilogue: the accumulators only have to stay alive
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < CT; ++i)
-#pragma unroll
-            for (int j = 0; j < PT; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) asm volatile("" ::"v"(acc[i][j][e]));
-        if (sacc == 12345.f) p.out[0] = sacc;
-    } else {
+    {       // (a scope of its own: where its variables end shapes the loop exit, and with it the register allocation of the kernel)
     const int h = lane >> 5;
     const int gcout = p.g_cout[grp];
     const int ooff = p.out_coff + p.g_ooff[grp];
@@ -466,39 +387,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
 #pragma unroll
                             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
                         }
-                        if constexpr (M::Q16) {
-                            // q16 out (SG == 4: the staged row is the whole 128-byte chunk of the fragment's 32 channels): fp16 hi of
-                            // channel c at byte 2c, hi8 at 64 + c, lo8 at 96 + c; c = 8j + 4h + e
-                            const int c0 = 8 * j + 4 * h;
-                            unsigned int hh[2], h8 = 0u, l8 = 0u;
-                            float r[4];
-#pragma unroll
-                            for (int e2 = 0; e2 < 2; ++e2) {
-                                const float a0 = v[2 * e2], a1 = v[2 * e2 + 1];
-                                const h2_t hp = __builtin_convertvector(f32x2v{__builtin_amdgcn_fmed3f(a0, -65504.f, 65504.f),
-                                                                               __builtin_amdgcn_fmed3f(a1, -65504.f, 65504.f)}, h2_t);
-                                hh[e2] = __builtin_bit_cast(unsigned int, hp);
-                                const f32x2v hb = __builtin_convertvector(hp, f32x2v);
-                                r[2 * e2] = a0 - hb.x; r[2 * e2 + 1] = a1 - hb.y;
-                                v[2 * e2] = hb.x; v[2 * e2 + 1] = hb.y;
-                            }
-                            const float s8 = q_act, sl = q_act * 2048.f;
-                            auto clamp8 = [](float x) { return __builtin_amdgcn_fmed3f(x, -448.f, 448.f); };
-                            h8 = (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(clamp8(v[0] * s8), clamp8(v[1] * s8), (int)h8, false);
-                            h8 = (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(clamp8(v[2] * s8), clamp8(v[3] * s8), (int)h8, true);
-                            l8 = (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(clamp8(r[0] * sl), clamp8(r[1] * sl), (int)l8, false);
-                            l8 = (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(clamp8(r[2] * sl), clamp8(r[3] * sl), (int)l8, true);
-                            unsigned char *w = stg + (lane & 31) * STG_ROW;
-                            *reinterpret_cast<uint2 *>(w + 2 * c0) = make_uint2(hh[0], hh[1]);
-                            *reinterpret_cast<unsigned int *>(w + 64 + c0) = h8;
-                            *reinterpret_cast<unsigned int *>(w + 96 + c0) = l8;
-                        } else {
                         uint2 hi, lo;
                         split4<M>(v, hi, lo);
                         unsigned char *w = stg + (lane & 31) * STG_ROW + jj * 32 + h * 8;
                         *reinterpret_cast<uint2 *>(w) = hi;
                         *reinterpret_cast<uint2 *>(w + 16) = lo;
-                        }
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
@@ -508,10 +401,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
                     for (int i = 0; i < 32 / RPI; ++i) {
                         const int r = srow + RPI * i, x = x0 + r;
                         const v4u d = *reinterpret_cast<const v4u *>(stg + r * STG_ROW + spiece * 16);
-                        if constexpr (DIAG & 64) {                        // no global stores
-                            asm volatile("" ::"v"(d));
-                            continue;
-                        }
                         if (y < p.ho && x < p.wo && gcol < gcout) {
                             const size_t op = ((size_t)b * p.out_hp + (size_t)y * p.out_sy + p.out_dy) * p.out_wp + (size_t)x * p.out_sx + p.out_dx;
                             unsigned char *g = reinterpret_cast<unsigned char *>(p.out) + (op * p.out_cstride + ooff + gcol) * 4 + (spiece & 1) * 16;
@@ -565,16 +454,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PT == 2 ? 2 
     asm volatile("s_waitcnt vmcnt(0)");      // nothing of this file's asm loads may stay in flight at exit
 }
 
-// q16 prototype (diag builds): tensor exponents from the environment (read once): activations scaled by 2^-DZ_TUNE_Q16_EA, weights by
-// 2^-DZ_TUNE_Q16_EW; the kernels of every other math type ignore the three arguments
-static int q16_env(const char *n, int d) { const char *v = getenv(n); return v ? atoi(v) : d; }
-static int q16_sa() { static const int v = 127 + q16_env("DZ_TUNE_Q16_EW", -4); return v; }               // weights are the A operand
-static int q16_sb() { static const int v = 127 + q16_env("DZ_TUNE_Q16_EA", 2) - 11; return v; }           // activations the B operand; both correction terms carry 2^-11
-static float q16_act() { static const float v = ldexpf(1.f, -q16_env("DZ_TUNE_Q16_EA", 2)); return v; }
-
-template <int BC, class M, bool OUT_F32, int NT, int DIAG = 0, int PT = 2, bool SPARSE = false>
-static int launch_c3_nt(const dz_conv2d_desc &p, size_t w_bytes, hipStream_t stream) {
-    using C = C3Cfg<BC, NT, PT>;
+template <int BC, class M, bool OUT_F32, bool SPARSE = false>
+static int launch_c3(const dz_conv2d_desc &p, size_t w_bytes, hipStream_t stream) {
+    using C = C3Cfg<BC>;
     const int tiles_x = ceil_div(p.wo, C3_TW), tiles_y = ceil_div(p.ho, C::TH);
     // (SPARSE: `in` is the level's rows - in_rows of them, in_row_channels channels each)
     const size_t in_bytes = SPARSE ? (size_t)p.in_rows * p.in_row_channels * sizeof(float) : (size_t)p.batch * p.in_hp * p.in_wp * p.in_cstride * sizeof(float);
@@ -587,20 +469,18 @@ static int launch_c3_nt(const dz_conv2d_desc &p, size_t w_bytes, hipStream_t str
         return DZ_ERR_UNSUPPORTED;
     }
     static PerDeviceFlags lds_done;
-    if (int rc_ = reserve_lds(reinterpret_cast<const void *>(&k_conv3x3_h<BC, M, OUT_F32, NT, DIAG, PT, SPARSE>), C::LDS_BYTES, lds_done, "dz_conv2d_forward_split")) return rc_;
-    // persistent: 512 / NT workgroups per CU, a multiple of 8 x channel tiles so that every XCD gets the same number of
-    // workgroups of every channel tile
+    if (int rc_ = reserve_lds(reinterpret_cast<const void *>(&k_conv3x3_h<BC, M, OUT_F32, SPARSE>), C::LDS_BYTES, lds_done, "dz_conv2d_forward_split")) return rc_;
+    // persistent: one workgroup per CU, a multiple of 8 x channel tiles so that every XCD gets the same number of workgroups of
+    // every channel tile
     const int nty = p.cout_pad / BC * p.groups;
-    const int slots = 32 * (PT == 2 ? 512 / NT : 1);            // workgroups of an XCD
-    static const int skew = getenv("DZ_TUNE_C3_SKEW") ? atoi(getenv("DZ_TUNE_C3_SKEW")) : 0;     // 10 ns ticks
-    static const int split = getenv("DZ_TUNE_C3_SPLIT") ? atoi(getenv("DZ_TUNE_C3_SPLIT")) : 1;  // development knob: 0 = one launch (r01-r04)
+    const int slots = 32;                                         // workgroups of an XCD
     // A workgroup keeps ONE (group, channel tile) pair, so an XCD runs a multiple of their number: with 3 or 6 pairs (the head's
     // 64 -> 384 layer and its grouped output layer) that is 30 of 32 workgroups - 16 CUs idle for the whole launch.  Such a layer runs
     // as two launches over 2 + 1 / 4 + 2 of its pairs, each on all 256 CUs (round 5: 27 rounds of tiles instead of 28.8)
     int parts[2][2] = {{0, nty}, {0, 0}};
     // (only where the launch is long enough to pay for a second one: at 8 frames per pass - 14 rounds - one launch measured 1.4 % faster)
     const long pair_tiles = (long)p.batch * tiles_x * tiles_y * nty;
-    if (split && slots % nty != 0 && nty < slots && pair_tiles >= 5000) {
+    if (slots % nty != 0 && nty < slots && pair_tiles >= 5000) {
         int a = 1;
         while (a * 2 <= nty) a *= 2;                            // largest power of two below nty
         if (slots % a == 0 && slots % (nty - a) == 0) { parts[0][1] = a; parts[1][0] = a; parts[1][1] = nty - a; }
@@ -610,51 +490,16 @@ static int launch_c3_nt(const dz_conv2d_desc &p, size_t w_bytes, hipStream_t str
         int per_xcd = slots / ny * ny;
         if (per_xcd < ny) per_xcd = ny;
         const long grid = 8L * per_xcd;
-        hipLaunchKernelGGL((k_conv3x3_h<BC, M, OUT_F32, NT, DIAG, PT, SPARSE>), dim3((unsigned int)grid), dim3(NT), C::LDS_BYTES, stream, p, tiles_x,
-                           tiles_y, (unsigned int)in_bytes, (unsigned int)w_bytes, skew, q16_sa(), q16_sb(), q16_act(), parts[k][0], ny);
+        hipLaunchKernelGGL((k_conv3x3_h<BC, M, OUT_F32, SPARSE>), dim3((unsigned int)grid), dim3(C3_NT), C::LDS_BYTES, stream, p, tiles_x,
+                           tiles_y, (unsigned int)in_bytes, (unsigned int)w_bytes, parts[k][0], ny);
         DZ_LAUNCH_CHECK();
     }
     return DZ_OK;
 }
 
-// Shipped configuration: 512 threads (4 row pairs x 2 channel halves), one workgroup per CU.  Built and measured on the MI355X, all
-// slower, kept behind -DDZ_C3_DIAG for the record: two 256-thread workgroups per CU (DZ_TUNE_C3_NT=256: their phases
-// do not de-synchronise, and a start skew changes nothing - the CU is throughput-bound), one wave per SIMD with 3 x 4 fragments
-// (DZ_TUNE_C3_PT=3: fewer LDS reads per MFMA, but every barrier and wait is exposed: 543 vs 471 us), and the diag switches.
-template <int BC, class M, bool OUT_F32>
-static int launch_c3(const dz_conv2d_desc &p, size_t w_bytes, hipStream_t stream) {
-#ifdef DZ_C3_DIAG
-    static const int nt = getenv("DZ_TUNE_C3_NT") ? atoi(getenv("DZ_TUNE_C3_NT")) : 512;
-    if constexpr (BC == 128 && !OUT_F32 && std::is_same<M, MathF16>::value) {
-        static const int diag = getenv("DZ_TUNE_C3_DIAG") ? atoi(getenv("DZ_TUNE_C3_DIAG")) : 0;
-        switch (diag) {
-            case 1: return launch_c3_nt<BC, M, OUT_F32, 512, 1>(p, w_bytes, stream);
-            case 2: return launch_c3_nt<BC, M, OUT_F32, 512, 2>(p, w_bytes, stream);
-            case 4: return launch_c3_nt<BC, M, OUT_F32, 512, 4>(p, w_bytes, stream);
-            case 8: return launch_c3_nt<BC, M, OUT_F32, 512, 8>(p, w_bytes, stream);
-            case 15: return launch_c3_nt<BC, M, OUT_F32, 512, 15>(p, w_bytes, stream);
-            case 16: return launch_c3_nt<BC, M, OUT_F32, 512, 16>(p, w_bytes, stream);
-            case 32: return launch_c3_nt<BC, M, OUT_F32, 512, 32>(p, w_bytes, stream);
-            case 47: return launch_c3_nt<BC, M, OUT_F32, 512, 47>(p, w_bytes, stream);
-            case 64: return launch_c3_nt<BC, M, OUT_F32, 512, 64>(p, w_bytes, stream);
-            default: break;
-        }
-        static const int pt = getenv("DZ_TUNE_C3_PT") ? atoi(getenv("DZ_TUNE_C3_PT")) : 2;
-        if (pt == 3) return launch_c3_nt<BC, M, OUT_F32, 256, 0, 3>(p, w_bytes, stream);
-        static const int q16 = getenv("DZ_TUNE_C3_Q16") ? atoi(getenv("DZ_TUNE_C3_Q16")) : 0;
-        if (q16) return launch_c3_nt<BC, MathF16Q, OUT_F32, 512>(p, w_bytes, stream);
-    }
-    if constexpr (BC == 64) {
-        if (nt == 256) return launch_c3_nt<BC, M, OUT_F32, 256>(p, w_bytes, stream);
-    }
-#endif
-    return launch_c3_nt<BC, M, OUT_F32, 512>(p, w_bytes, stream);
-}
-
-// 0 = not eligible, 64 / 128 = channel tile of the resident-tile kernel
+// 0 = the layer is not for this kernel, 32 / 64 / 128 = its channel tile.  The routing and the refusals built on it are
+// conv_h_select's (conv2d_h.hip).
 int conv3x3_h_variant(const dz_conv2d_desc &p) {
-    static const int off = getenv("DZ_TUNE_NO_CONV3X3") ? atoi(getenv("DZ_TUNE_NO_CONV3X3")) : 0;
-    if (off) return 0;
     if (p.kh != 3 || p.kw != 3 || p.stride != 1 || p.group_shift) return 0;
     if (p.cin % C3_KC != 0) return 0;
     // sparse input (in_rowidx): two z slabs of in_row_channels channels each, 128 output channels per tile, pair16 out
@@ -664,54 +509,26 @@ int conv3x3_h_variant(const dz_conv2d_desc &p) {
         return t32 >= 384 ? 32 : 0;
     }
     if (p.groups != 1 || p.cout_pad % 64 != 0) return 0;
-#ifdef DZ_C3_DIAG
-    static const int nt = getenv("DZ_TUNE_C3_NT") ? atoi(getenv("DZ_TUNE_C3_NT")) : 512;
-#else
-    constexpr int nt = 512;
-#endif
-    const int bc = (p.cout_pad % 128 == 0 && nt != 256) ? 128 : 64;
+    const int bc = p.cout_pad % 128 == 0 ? 128 : 64;
     // one 512-thread workgroup per CU: below ~1.5 waves of tiles the 4-wave kernels of conv2d_h.hip fill the chip better
     const long tiles = (long)p.batch * ceil_div(p.wo, C3_TW) * ceil_div(p.ho, 8) * (p.cout_pad / bc);
     if (tiles < 384 && !p.in_rowidx) return 0;        // (the sparse-input form exists in this kernel only)
     return bc;
 }
 
-#ifdef DZ_C3_DIAG
-bool conv3x3_d_eligible(const dz_conv2d_desc &p);      // conv3x3_d.hip: direct-to-LDS 2 x 4-fragment variant (measured equal, not shipped)
-int conv3x3_d_launch(const dz_conv2d_desc &p, int math, size_t w_bytes, hipStream_t stream);
-#endif
-
-int conv3x3_h_launch(const dz_conv2d_desc &p, int math, int out_f32, size_t w_bytes, hipStream_t stream) {
-    const int bc = conv3x3_h_variant(p);
-    if (p.in_rowidx) {
-        if (bc != 128 || out_f32) {
-            set_error("dz_conv2d_forward_split: in_rowidx (sparse input) needs a 3 x 3 stride-1 layer, 128-channel output tiles, two z slabs, pair16 output");
-            return DZ_ERR_UNSUPPORTED;
-        }
-        if (math == DZ_MATH_F16X2) return launch_c3_nt<128, MathF16, false, 512, 0, 2, true>(p, w_bytes, stream);
-        if (math == DZ_MATH_F16) return launch_c3_nt<128, MathF16H, false, 512, 0, 2, true>(p, w_bytes, stream);
-        return launch_c3_nt<128, MathBF16, false, 512, 0, 2, true>(p, w_bytes, stream);
-    }
-#ifdef DZ_C3_DIAG
-    if (bc == 128 && !out_f32 && conv3x3_d_eligible(p)) return conv3x3_d_launch(p, math, w_bytes, stream);
-#endif
-    auto go = [&](auto bc_t, auto m_t) {
-        constexpr int BCV = decltype(bc_t)::value;
-        using MM = typename decltype(m_t)::type;
-        // fp32 output exists for the 32-channel configuration only (the head's grouped output layer - the one layer of the network that
-        // leaves the pair16 domain); the 64 / 128-channel instances were never launched and spilled (round-4 review): the caller
-        // (dz_conv2d_forward_split) sends such a layer to the generic kernel
-        if constexpr (BCV == 32) return out_f32 ? launch_c3<BCV, MM, true>(p, w_bytes, stream) : launch_c3<BCV, MM, false>(p, w_bytes, stream);
-        else return launch_c3<BCV, MM, false>(p, w_bytes, stream);
+// bc: the channel tile conv_h_select chose (conv2d_h.hip); it sends in_rowidx layers here at bc = 128 with pair16 output only, and
+// fp32 output at bc = 32 only (the head's grouped output layer - the one layer of the network that leaves the pair16 domain)
+int conv3x3_h_launch(const dz_conv2d_desc &p, int bc, int math, int out_f32, size_t w_bytes, hipStream_t stream) {
+    auto by_math = [&](auto m_t) {
+        using M = typename decltype(m_t)::type;
+        if (p.in_rowidx) return launch_c3<128, M, false, true>(p, w_bytes, stream);
+        if (bc == 128) return launch_c3<128, M, false>(p, w_bytes, stream);
+        if (bc == 64) return launch_c3<64, M, false>(p, w_bytes, stream);
+        return out_f32 ? launch_c3<32, M, true>(p, w_bytes, stream) : launch_c3<32, M, false>(p, w_bytes, stream);
     };
-    auto by_math = [&](auto bc_t) {
-        if (math == DZ_MATH_F16X2) return go(bc_t, TypeTag<MathF16>{});
-        if (math == DZ_MATH_F16) return go(bc_t, TypeTag<MathF16H>{});
-        return go(bc_t, TypeTag<MathBF16>{});
-    };
-    if (bc == 32) return by_math(std::integral_constant<int, 32>{});
-    if (bc == 128) return by_math(std::integral_constant<int, 128>{});
-    return by_math(std::integral_constant<int, 64>{});
+    if (math == DZ_MATH_F16X2) return by_math(TypeTag<MathF16>{});
+    if (math == DZ_MATH_F16) return by_math(TypeTag<MathF16H>{});
+    return by_math(TypeTag<MathBF16>{});
 }
 
 }  // namespace dz

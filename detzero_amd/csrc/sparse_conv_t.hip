@@ -11,7 +11,8 @@
 //     the 32-row MFMA fragments hold rows with similar neighbourhoods and a fragment can skip the slots none of its rows has
 //     (26 -> ~20 of 27 taps issued per fragment on the 160k-point frames; spconv sorts whole tensors by mask for the same reason
 //     - with a gather kernel that costs more in locality than it saves, with the inputs resident in LDS it is free);
-//   * the convolution is the resident-tile dense 3x3 kernel's design (conv3x3_d.hip) with the image tile replaced by the halo:
+//   * the convolution is the resident-tile dense 3x3 kernel's design (conv3x3_d.hip, removed; last in c5e05cd) with the image
+//     tile replaced by the halo:
 //     nothing is staged in registers (buffer_load_dwordx4 ... lds), 64-byte rows per 16-channel chunk with the XOR swizzle
 //     slot = piece ^ ((row >> 2) & 3), the halo double-buffered (the next chunk arrives during the first steps of the current
 //     one), weights and local-table slices through rings, static vmcnt counts (every step issues the same number of loads; the

@@ -134,7 +134,7 @@ _SIGS = {
     'dz_sparse_to_bev_split_dense': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                              c_void_p]),
     'dz_conv2d_forward_split': (c_int, [ctypes.POINTER(Conv2dDesc), c_int, c_int, c_void_p]),
-    'dz_conv2d_variant_split': (ctypes.c_char_p, [ctypes.POINTER(Conv2dDesc)]),
+    'dz_conv2d_variant_split': (ctypes.c_char_p, [ctypes.POINTER(Conv2dDesc), c_int]),
     'dz_spconv_variant_split': (ctypes.c_char_p, [c_int, c_int]),
     'dz_xattn_folded_supported': (c_int, [c_int, c_int, c_int]),
     'dz_xattn_folded_workspace_bytes': (ctypes.c_size_t, [c_int, c_int]),
@@ -215,6 +215,9 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
+    # out_f32 of the report defaults to 0 (pair16 output, the usual case and the form the report had before it took the flag)
+    variant_split = lib.dz_conv2d_variant_split
+    lib.dz_conv2d_variant_split = lambda desc, out_f32=0: variant_split(desc, out_f32)
     _lib = lib
     return lib
 

@@ -643,7 +643,7 @@ def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None):
         share = n_run / float(max(n_run + n_skip, 1))
         flops *= share
         nbytes = 4.0 * (share * (m * d.cin + m * cout) + taps * d.cin * d.cout_pad * d.groups)
-    name = (lib.dz_conv2d_variant_split if math else lib.dz_conv2d_variant)(ctypes.byref(d)).decode()
+    name = (lib.dz_conv2d_variant_split(ctypes.byref(d), 1 if out_f32 else 0) if math else lib.dz_conv2d_variant(ctypes.byref(d))).decode()
     PROFILER.wrap(name, flops, nbytes, launch)
 
 

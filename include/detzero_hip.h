@@ -346,7 +346,8 @@ int dz_sparse_to_bev_split_dense(const float *feats, int feat_rows, const uint32
 /* dz_conv2d_forward on pair16 images: desc->in pair16, desc->w (groups, kh*kw, cout_pad, cin) pair16
  * (cout_pad % 32 == 0, cin % 32 == 0), desc->out pair16 or, with out_f32 != 0, plain fp32 (last head conv). */
 int dz_conv2d_forward_split(const dz_conv2d_desc *h_desc, int math, int out_f32, void *stream);
-const char *dz_conv2d_variant_split(const dz_conv2d_desc *h_desc);
+/* the kernel and tile dz_conv2d_forward_split runs for this descriptor and out_f32, "none" where it refuses the layer */
+const char *dz_conv2d_variant_split(const dz_conv2d_desc *h_desc, int out_f32);
 /* dz_linear_forward on pair16 rows: x (rows, x_stride words) pair16, w (cout_pad, cin) pair16 (cin, cout_pad % 32 == 0), y pair16
  * rows or, with out_f32 != 0, fp32 rows; group_shift (row groups, cout_pad) fp32 as in dz_linear_forward.
  * group_max != 0 (with out_f32): the torch.max over the points of an object that follows the PointNet encoders

@@ -112,6 +112,10 @@ def _coverage_cases():
             c('resident 32 ragged', m, 64, 37, 45, 64, 32, g_cout=[24], expect='k_conv3x3_h<16x32x32>'),
             c('resident 32 fp32 out grouped g_cout 2/7/3', m, 32, 21, 50, 32, 32, groups=3, g_cout=[2, 7, 3], g_ooff=[0, 2, 9],
               out_pad=0, out_f32=True, relu=False, scale=False, expect='k_conv3x3_h<16x32x32>'),
+            # a layer the 128-channel resident tile takes (384 tiles), with fp32 output: that exists at 32-channel tiles only, so
+            # the generic kernel runs it - and the report must say so
+            c('resident-size 128 fp32 out', m, 16, 61, 70, 64, 128, g_cout=[122], out_pad=0, out_f32=True, relu=False,
+              expect='k_conv2d_h<64x64x32>'),
             # in_tiles: listed 8 x 32 tiles computed, the others untouched
             c('resident 128 tile list', m, 12, 93, 90, 64, 128, tiles=True, expect='k_conv3x3_h<8x32x128>'),
             c('resident 64 tile list', m, 18, 61, 70, 64, 64, tiles=True, expect='k_conv3x3_h<8x32x64>'),
@@ -159,7 +163,9 @@ def selected_variant(case):
     if case.sparse:
         d.in_rowidx, d.in_row_channels, d.in_rows = 16, case.desc['cin'] // 2, case.in_rows
     lib = L.load()
-    return (lib.dz_conv2d_variant_split if ops.math_id(case.mode) else lib.dz_conv2d_variant)(ctypes.byref(d)).decode()
+    if ops.math_id(case.mode):
+        return lib.dz_conv2d_variant_split(ctypes.byref(d), 1 if case.out_f32 else 0).decode()
+    return lib.dz_conv2d_variant(ctypes.byref(d)).decode()
 
 
 def _launch(case, ptrs, math):
@@ -360,6 +366,20 @@ def test_case_table_covers_every_variant():
     for m in MODES:
         print('  %-7s %s' % (m, ' '.join(sorted(reached[m]))))
         assert reached[m] == ALL_VARIANTS[m], (m, sorted(ALL_VARIANTS[m] - reached[m]), sorted(reached[m] - ALL_VARIANTS[m]))
+
+
+def test_refused_descriptors_report_none():
+    """A layer dz_conv2d_forward_split refuses is reported as "none", not as the kernel it would have reached: a tile list on a
+    32-channel tile layer (its tiles are 16 x 32, the list's 8 x 32), and sparse input with fp32 output."""
+    tiled = next(c for c in COVERAGE if c.label == 'resident 32 ragged' and c.mode == 'f16x2')
+    assert selected_variant(tiled) == 'k_conv3x3_h<16x32x32>'
+    d = _cdesc(tiled.desc, dict(in_tiles=16))
+    assert L.load().dz_conv2d_variant_split(ctypes.byref(d), 0).decode() == 'none'
+    sparse = next(c for c in COVERAGE if c.sparse and c.mode == 'f16x2')
+    assert selected_variant(sparse) == 'k_conv3x3_h<8x32x128>'
+    d = _cdesc(sparse.desc)
+    d.in_rowidx, d.in_row_channels, d.in_rows = 16, sparse.desc['cin'] // 2, sparse.in_rows
+    assert L.load().dz_conv2d_variant_split(ctypes.byref(d), 1).decode() == 'none'
 
 
 def test_reference_paths_agree():

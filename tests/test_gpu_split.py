@@ -389,9 +389,11 @@ def test_conv3x3_resident_tile_kernel_vs_torch(device, name, mid, cin, cout, h, 
     out = torch.zeros((b, h + 2, w + 2, cs_out), dtype=torch.float32, device=device)
     kw = dict(cin=cin, in_cstride=cs_in, in_coff=8, ksize=3, stride=1, in_off=0, out_cstride=cs_out, out_coff=16, out_d=(1, 1),
               ho=h, wo=w, batch=b, g_cout=[cout])
-    d = L.Conv2dDesc()          # the dispatcher must pick the resident-tile kernel for this shape
+    d = L.Conv2dDesc()          # the kernel the dispatcher must pick for this shape
     d.batch, d.ho, d.wo, d.kh, d.kw, d.stride, d.groups, d.cin, d.cout_pad = b, h, w, 3, 3, 1, 1, cin, cout
-    assert L.load().dz_conv2d_variant_split(ctypes.byref(d)).decode().startswith('k_conv3x3_h')
+    # (fp32 output: the resident-tile kernel writes it at 32-channel tiles only - this 64-channel layer runs on k_conv2d_h)
+    want = 'k_conv2d_h<' if out_f32 else 'k_conv3x3_h<'
+    assert L.load().dz_conv2d_variant_split(ctypes.byref(d), 1 if out_f32 else 0).decode().startswith(want)
     conv_layer(xin_d, (h + 2, w + 2), w_split, scale.to(device), shift.to(device), True, out, (h + 2, w + 2), math=mid,
                out_f32=out_f32, **kw)
     plain = out if out_f32 else ops.pair16_to_f32(out, mid)
