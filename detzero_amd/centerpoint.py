@@ -229,11 +229,13 @@ def set_math(model, mode):
     return model
 
 
-def set_sparse_engine(model, engine):
+def set_sparse_engine(model, engine, f32_engine=None):
     """Convolution engine of the sparse backbone in the split math modes: 'xrun' (default: the gather kernels plus sparse_conv_x.hip
     for the submanifold convolutions of the 32 / 64 / 128-channel levels), 'gather' (sparse_conv_h.hip / sparse_conv_w.h only; both
-    on rows in the canonical linear-key order) or 'tiles' (sparse_conv_t.hip: tile-resident inputs on rows in the brick order)."""
-    model.backbone3d.set_engine(engine)
+    on rows in the canonical linear-key order) or 'tiles' (sparse_conv_t.hip: tile-resident inputs on rows in the brick order).
+    f32_engine: the engine of the exact-fp32 mode, 'gather' (default: sparse_conv.hip) or 'xrun' (plus sparse_conv_xf.hip for the same
+    submanifold convolutions, from the same index); None leaves it as it is."""
+    model.backbone3d.set_engine(engine, f32_engine)
     return model
 
 

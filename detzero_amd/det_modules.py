@@ -350,21 +350,29 @@ class VoxelResBackBone8x(_Cached):
         #   ops.build_windows); every other convolution as 'gather'.
         self.layout = int(os.environ.get('DZ_TUNE_LAYOUT', ops.LAYOUT_LINEAR))          # (environment: A/B runs on one box)
         self.engine = os.environ.get('DZ_TUNE_SPCONV_ENGINE', 'xrun')
+        # ... and of the exact-fp32 mode: 'gather' (default: sparse_conv.hip for every convolution) or 'xrun' (the submanifold convolutions
+        # of the 32 / 64 / 128-channel levels on sparse_conv_xf.hip, from the same packed tables + windows; everything else as 'gather')
+        self.f32_engine = os.environ.get('DZ_TUNE_SPCONV_F32_ENGINE', 'gather')
         # output widths whose convolutions run on the tile engine when it is selected (the others keep the gather kernels)
         self.tile_couts = tuple(int(c) for c in os.environ.get('DZ_TUNE_SPCONV_TILE_COUTS', '16,32,64,128').split(',') if c)
         self.backbone_channels = {'x_conv1': channels[0], 'x_conv2': channels[1], 'x_conv3': channels[2],
                                   'x_conv4': channels[3]}
         self.channels = channels
 
-    def set_engine(self, engine):
+    def set_engine(self, engine, f32_engine=None):
         """'gather' (rows in the canonical linear-key order), 'xrun' (gather + the z-slab window kernel for the submanifold
-        convolutions of the 32 / 64 / 128-channel levels; same row order) or 'tiles' (tile-resident convolution; rows in brick order)."""
+        convolutions of the 32 / 64 / 128-channel levels; same row order) or 'tiles' (tile-resident convolution; rows in brick order).
+        f32_engine (None = unchanged): the engine of the exact-fp32 mode, 'gather' or 'xrun'."""
         if engine not in ('gather', 'tiles', 'xrun'):
             raise DetZeroHipError('unknown sparse engine %r (gather | xrun | tiles)' % (engine,))
+        if f32_engine is not None and f32_engine not in ('gather', 'xrun'):
+            raise DetZeroHipError('unknown fp32 sparse engine %r (gather | xrun)' % (f32_engine,))
         if engine == 'tiles' and ops.L.load().dz_spconv_tile_rows() == 0:
             raise DetZeroHipError("sparse engine 'tiles' is an experimental build option (measured slower, DESIGN.md 2d): rebuild the library "
                                   'with DZ_BUILD_EXPERIMENTAL=1 (python -m detzero_amd.build --force)')
         self.engine = engine
+        if f32_engine is not None:
+            self.f32_engine = f32_engine
         self.layout = ops.LAYOUT_BRICK if engine == 'tiles' else ops.LAYOUT_LINEAR
 
     # ---- kernel-layout parameters -------------------------------------------------------------
@@ -439,14 +447,15 @@ class VoxelResBackBone8x(_Cached):
         # conv2) built packed - a third of the words; the index chain gains what the decode costs the convolutions
         pack = PACKED_TABLES and self.math != 0 and not tiled and self.layout == 0 and os.environ.get('DZ_TUNE_SPCONV_W', '1') != '0'
 
-        xrun = self.engine == 'xrun' and self.math != 0 and self.layout == 0
+        xrun = (self.engine if self.math != 0 else self.f32_engine) == 'xrun' and self.layout == 0
         xrun_couts = tuple(int(c) for c in os.environ.get('DZ_TUNE_XRUN_COUTS', '32,64,128').split(',') if c)
 
         def table(src, dst, k, s, p, cout):
             # (asked BEFORE the packed table is built: a width / capacity the x-run kernel does not cover would otherwise build the
             # table twice - packed for nothing, then plain)
             if (xrun and src is dst and cout in xrun_couts and tuple(k) == (3, 3, 3) and dst.cap < (1 << 29)
-                    and ops.L.load().dz_spconv_x_tile_rows(int(cout), int(cout)) != 0):
+                    and ops.L.load().dz_spconv_x_tile_rows(int(cout), int(cout)) != 0
+                    and (self.math != 0 or ops.L.load().dz_spconv_x_f32_window_rows(int(cout), int(cout)) != 0)):
                 # submanifold table of a level the x-run kernel covers: packed words + the tiles' windows
                 nbr = ops.neighbors_xrun(dst, cout)          # (one launch: packed table + windows + tap-set order)
                 if getattr(nbr, 'xwin', None) is not None:

@@ -374,9 +374,18 @@ def gather_rows(src, idx, d_n, n_cap):
     return out
 
 
+def _xrun_f32_usable(lib, nbr, w_taps):
+    """The packed table carries x-run windows the exact-fp32 x-run kernel can run this (kvol, cin, cout) fp32 layer from."""
+    xwin = getattr(nbr, 'xwin', None)
+    cin, cout = int(w_taps.shape[1]), int(w_taps.shape[2])
+    return (xwin is not None and cin == cout and lib.dz_spconv_x_f32_window_rows(cin, cout) > 0
+            and xwin[1] == lib.dz_spconv_x_tile_rows(cin, cout))
+
+
 def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None):
     """feats (m_in,cin); nbr (kvol,cap); returns (cap,cout).
-    math == 0: fp32 rows, w_taps (kvol,cin,cout) fp32.
+    math == 0: fp32 rows, w_taps (kvol,cin,cout) fp32; a packed table with x-run windows (neighbors_xrun / build_windows) runs a
+    cin == cout layer of 32 / 64 / 128 channels on the exact-fp32 x-run kernel (dz_spconv_forward_x_f32).
     math != 0: pair16 rows (in, residual, out), w_taps (kvol,cout_pad,cin) pair16 from pack_weight_split."""
     lib = L.load()
     L.require_cuda(feats, nbr, w_taps, scale, shift, residual)
@@ -384,7 +393,8 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
     packed = getattr(nbr, 'packed', False)
     if packed:
         kvol = nbr.kvol
-        if not math:
+        # (fp32: only the x-run kernel of sparse_conv_xf.hip reads a packed table - it needs the table's windows, for a layer it covers)
+        if not math and not _xrun_f32_usable(lib, nbr, w_taps):
             raise L.DetZeroHipError('spconv_forward: a packed neighbour table feeds the split-math kernels only')
     if math:
         # (split weights are padded to 32 output channels: the true count comes from the BatchNorm vector, or `cout=`)
@@ -396,8 +406,8 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         out = torch.empty((cap, cout), dtype=torch.float32, device=feats.device)
 
     tiles = getattr(nbr, 'tiles', None) if (math and kvol >= 3) else None
-    xwin = getattr(nbr, 'xwin', None) if (math and packed and cin == cout) else None
-    if xwin is not None and lib.dz_spconv_x_tile_rows(cin, cout) != xwin[1]:
+    xwin = getattr(nbr, 'xwin', None) if (packed and cin == cout) else None
+    if math and xwin is not None and lib.dz_spconv_x_tile_rows(cin, cout) != xwin[1]:
         # (windows built for another tile size - e.g. DZ_TUNE_X32 changed after the index was built: the packed gather kernel runs instead)
         global _XWIN_MISMATCH_LOGGED
         if not _XWIN_MISMATCH_LOGGED:
@@ -408,7 +418,11 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         xwin = None
 
     def launch():
-        if xwin is not None:
+        if xwin is not None and not math:
+            rc = lib.dz_spconv_forward_x_f32(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
+                                             L.ptr(xwin[0]), xwin[1], cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift),
+                                             L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, L.stream())
+        elif xwin is not None:
             rc = lib.dz_spconv_forward_split_x(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
                                                L.ptr(xwin[0]), xwin[1], cap,
                                                L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift), L.ptr(residual),
@@ -440,7 +454,7 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         flops = 2.0 * pairs * cin * cout
         n_in = in_level.num_active() if in_level is not None else m
         nbytes = 4.0 * (n_in * cin + m * cout + kvol * cin * cout + (m * cout if residual is not None else 0)) + 8.0 * pairs
-        name = (lib.dz_spconv_x_variant(cin, cout) if xwin is not None else lib.dz_spconv_tiles_variant(cin, cout) if tiles is not None else
+        name = (lib.dz_spconv_x_f32_variant(cin, cout) if xwin is not None and not math else lib.dz_spconv_x_variant(cin, cout) if xwin is not None else lib.dz_spconv_tiles_variant(cin, cout) if tiles is not None else
                 lib.dz_spconv_variant_split(cin, cout) if math else lib.dz_spconv_variant(cin, cout))
         PROFILER.wrap(name.decode(), flops, nbytes, launch)
     return out

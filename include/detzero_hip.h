@@ -313,6 +313,23 @@ int dz_spconv_forward_split_x(const float *in, int in_rows, int cin, const int *
                               const float *residual, int relu, float *out, int cout, int math, void *stream);
 /* (nbr_packed = the level's packed table and perm = NULL, or nbr_sorted and its perm) */
 const char *dz_spconv_x_variant(int cin, int cout);
+/* The x-run engine in EXACT fp32 (csrc/sparse_conv_xf.hip): the same layers, the same index (packed table or nbr_sorted + perm, the
+ * windows of units of dz_spconv_x_tile_rows(cin, cout) rows - one index serves both arithmetics), fp32 rows and fp32 MFMA.
+ *   in (in_rows, cin), residual / out (cap_out, cout) fp32 rows; w (27, cin, cout) fp32, the layout dz_spconv_forward takes;
+ *   out = relu?((sum) * scale + shift (+ residual)), scale / shift / residual each optional (NULL); rows at or beyond *d_m_out are
+ *   not written.  The 16 queue words behind the windows are not used and stay zero.
+ *   Per output element the products are accumulated in the order (tz, 16-channel chunk kc, ty, tx, then channels kc*16 + s and
+ *   kc*16 + 8 + s for s = 0..7), one fmaf each, whatever unit the row falls into and whether the slab's window was staged or
+ *   gathered: launches agree bit for bit with each other, and with dz_spconv_forward to fp32 summation-order noise, not bit for bit.
+ *   DZ_ERR_UNSUPPORTED for layers it does not cover (cin != cout, widths other than 32 / 64 / 128) and for in_rows * cin * 4 or
+ *   cap_out * cout * 4 at or beyond 2 GiB; DZ_ERR_INVALID for windows built for another tile_rows or null pointers.
+ *   dz_spconv_x_f32_window_rows: rows of a z-slab window the kernel stages in LDS (longer windows run in gather mode), 0 = layer not
+ *   covered.  dz_spconv_x_f32_variant: kernel instance name, "none" if not covered. */
+int dz_spconv_forward_x_f32(const float *in, int in_rows, int cin, const int *nbr_packed, const int *perm, int *windows, int tile_rows,
+                            int cap_out, const int *d_m_out, const float *w, const float *scale, const float *shift,
+                            const float *residual, int relu, float *out, int cout, void *stream);
+int dz_spconv_x_f32_window_rows(int cin, int cout);
+const char *dz_spconv_x_f32_variant(int cin, int cout);
 /* HeightCompression WITHOUT the dense image (round 5): idx (batch, h + 2 pad, w + 2 pad, 2) int32 = the feature row of every
  * (pixel, z slab) of a two-slab level, -1 = empty cell / border / rank >= feat_rows (overflowed capacity).  The first block of
  * BaseBEVBackbone reads the level's rows through it (dz_conv2d_desc.in_rowidx): height_compression.py:20-24 and the ZeroPad2d of

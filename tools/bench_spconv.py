@@ -58,6 +58,10 @@ def main():
         kvol = w.shape[0]
         variant = 'x' if getattr(nbr, 'xwin', None) is not None and w.shape[1] == w.shape[2] else 'g'
         cin, cout = (w.shape[2], scale.shape[0]) if mm else (w.shape[1], w.shape[2])
+        kname = ''
+        if variant == 'x':          # the x-run kernel instance that ran (pair16 or exact fp32)
+            from detzero_amd import lib as L
+            kname = '  ' + (L.load().dz_spconv_x_variant(cin, cout) if mm else L.load().dz_spconv_x_f32_variant(cin, cout)).decode()
         key = (kvol, cin, cout, lvl.cap, residual is not None, id(nbr))
         if args.only and '%d-%d' % (cin, cout) not in args.only.split(','):
             continue
@@ -101,7 +105,7 @@ def main():
         flop = 2.0 * pairs * cin * cout
         print(variant + ' k%-2d %3d->%-3d rows %8d pairs/row %5.2f taps/tile[16|32|64|128] %5.2f %5.2f %5.2f %5.2f  %8.1f us  alg %6.2f TF/s  '
               'dense64 %6.2f TF/s%s' % (kvol, cin, cout, m, pairs / max(m, 1), t16, t32, t64, t128, us, flop / us / 1e6,
-                                        2.0 * m * t64 * cin * cout / us / 1e6, ('  +res' if residual is not None else '') + halo))
+                                        2.0 * m * t64 * cin * cout / us / 1e6, ('  +res' if residual is not None else '') + halo + kname))
     print('sum over the %d sparse convs: %.1f us per step (%.1f us per frame)' % (len(calls), total, total / args.batch))
 
 
