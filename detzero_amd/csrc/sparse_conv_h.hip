@@ -224,6 +224,15 @@ static int launch_spconv_h(const SpConvHArgs &a, hipStream_t stream, bool ring_o
     return launch_spconv_h_impl<T, M, NS, false, OCC>(a, stream);
 }
 
+// Row tile of the 64- / 128-channel gather kernel for a value of DZ_TUNE_SPCONV64 / DZ_TUNE_SPCONV128: ONE decode for the launch
+// (spconv_h_dispatch) and for the name dz_spconv_variant_split reports, so that the two cannot drift apart.
+static int h_tile_rows(int cout_pad, int knob) {
+    if (cout_pad == 64) return knob == 1 ? 64 : knob == 2 ? 128 : 256;
+    return knob == 1 ? 64 : knob == 3 ? 256 : 128;
+}
+// (the 64-row 128-channel tile has no ring instance for the 128 -> 128 3 x 3 x 3 layers: its LDS-table arm runs them)
+static bool h_ring_ok(int cin, int kvol, int t128) { return !(t128 == 1 && cin == 128 && kvol == 27); }
+
 // Tile choices (per launch at 16 frames, r01e; alternatives that were built and measured slower or equal are listed in
 // 64-row tiles with 4 waves - the r01d defaults, kept below as knob 1 -, 256-row tiles with 64 x 64 wave tiles,
 // 4 register stages, 128 x 128 with 4 waves).
@@ -263,8 +272,9 @@ static int spconv_h_dispatch(const SpConvHArgs &a, hipStream_t stream) {
     }
 #endif
     if ((a.cin == 32 || a.cin == 64) && a.cout_pad == 64) {
-        if (t64 == 1) return launch_spconv_h<HTile<64, 64, 32, 2, 2>, M, 4, 3, 3, 3>(a, stream);       // 4 waves of 32 x 32 (r01d)
-        if (t64 == 2) return launch_spconv_h<HTile<128, 64, 32, 4, 2>, M, 3, 3, 4, 4>(a, stream);      // 8 waves of 32 x 32 (r01e-r03b)
+        const int rows = h_tile_rows(64, t64);
+        if (rows == 64) return launch_spconv_h<HTile<64, 64, 32, 2, 2>, M, 4, 3, 3, 3>(a, stream);       // 4 waves of 32 x 32 (r01d)
+        if (rows == 128) return launch_spconv_h<HTile<128, 64, 32, 4, 2>, M, 3, 3, 4, 4>(a, stream);     // 8 waves of 32 x 32 (r01e-r03b)
         // 8 waves of 64 x 32 over 256 rows: 12 instead of 16 fragment reads per 12 MFMAs, the weight slice fetched once per 256 rows
         // (r03: LDS fragment reads had become the largest single item of the diag breakdown of the 128-channel kernel, -31 %; inside
         // the detector, A/B on one box, two rounds: 861.2 / 861.9 against 855.3 / 853.3 frames/s, +0.2 % on another box)
@@ -285,12 +295,13 @@ static int spconv_h_dispatch(const SpConvHArgs &a, hipStream_t stream) {
             return launch_spconv_h_impl<DT, M, 3, true, 2, 9>(a, stream);
         }
 #endif
-        if (t128 == 1) return launch_spconv_h<HTile<64, 128, 32, 2, 2>, M, 3>(a, stream, !(a.cin == 128 && a.kvol == 27));   // 4 waves (r01d)
-        if (t128 == 2) return launch_spconv_h<HTile<128, 128, 32, 4, 2>, M, 3, 3, 2, 2>(a, stream);    // three register stages (r01e-r02f)
+        const int rows = h_tile_rows(128, t128);
+        if (rows == 64) return launch_spconv_h<HTile<64, 128, 32, 2, 2>, M, 3>(a, stream, h_ring_ok(a.cin, a.kvol, t128));   // 4 waves (r01d)
+        if (rows == 128 && t128 == 2) return launch_spconv_h<HTile<128, 128, 32, 4, 2>, M, 3, 3, 2, 2>(a, stream);    // three register stages (r01e-r02f)
         // 8 waves of 64 x 64 over 256 rows, two register stages (240 registers): 16 instead of 24 fragment reads per 24 MFMAs.  r03,
         // A/B inside the detector: -0.2 % / -0.45 % of a pass on two boxes, +3 % together with the 256-row 64-channel tile on a third:
         // not the default
-        if (t128 == 3) return launch_spconv_h<HTile<256, 128, 32, 4, 2>, M, 2, 2, 2, 2>(a, stream);
+        if (rows == 256) return launch_spconv_h<HTile<256, 128, 32, 4, 2>, M, 2, 2, 2, 2>(a, stream);
         // 8 waves of 32 x 64, four register stages with the ring (202 registers at two waves per SIMD): +0.3 % of a pass over three,
         // A/B inside the detector on one box (tools/gpu_ab_env.sh) - gather latency is not what limits this kernel
         return launch_spconv_h<HTile<128, 128, 32, 4, 2>, M, 3, 4, 2, 2>(a, stream);
@@ -363,20 +374,48 @@ int dz_spconv_forward_split_packed(const float *in, int in_rows, int cin, const 
     return math == DZ_MATH_F16X2 ? spconv_w_packed_dispatch<MathF16>(a, stream) : spconv_w_packed_dispatch<MathBF16>(a, stream);
 }
 
-const char *dz_spconv_variant_split(int cin, int cout) {
+// instance a (cin, cout) layer launches; w_ok: the table comes with tile masks inside the 2 GiB window (what k_spconv_w needs)
+static const char *split_name(int cin, int cout, bool w_ok) {
     const int cout_pad = cout < 32 ? 32 : cout;
-    if (tune("DZ_TUNE_SPCONV_W", 1) && cout_pad == 32) {        // (needs the table's tile masks, which dz_build_neighbors always writes)
+    if (w_ok && tune("DZ_TUNE_SPCONV_W", 1) && cout_pad == 32) {
         if (cin == 16 && cout == 16) return "k_spconv_w<16x16>";
         if (cin == 16 && cout == 32) return "k_spconv_w<16x32>";
         if (cin == 32 && cout == 32) return "k_spconv_w<32x32>";
     }
     if (cin == 16 && cout_pad == 32) return "k_spconv_h<128x32x16>";
     if (cin == 32 && cout_pad == 32) return "k_spconv_h<128x32x32>";
-    if ((cin == 32 || cin == 64) && cout_pad == 64)
-        return tune("DZ_TUNE_SPCONV64", 0) == 2 ? "k_spconv_h<128x64x32>" : "k_spconv_h<256x64x32>";
-    if ((cin == 64 || cin == 128) && cout_pad == 128)
-        return tune("DZ_TUNE_SPCONV128", 3) == 3 ? "k_spconv_h<256x128x32>" : "k_spconv_h<128x128x32>";
+    if ((cin == 32 || cin == 64) && cout_pad == 64) {
+        const int rows = h_tile_rows(64, tune("DZ_TUNE_SPCONV64", 0));
+        return rows == 64 ? "k_spconv_h<64x64x32>" : rows == 128 ? "k_spconv_h<128x64x32>" : "k_spconv_h<256x64x32>";
+    }
+    if ((cin == 64 || cin == 128) && cout_pad == 128) {
+        const int rows = h_tile_rows(128, tune("DZ_TUNE_SPCONV128", 3));
+        return rows == 64 ? "k_spconv_h<64x128x32>" : rows == 128 ? "k_spconv_h<128x128x32>" : "k_spconv_h<256x128x32>";
+    }
     return "none";
+}
+
+const char *dz_spconv_variant_split(int cin, int cout) {
+    return split_name(cin, cout, true);        // (dz_build_neighbors always writes the table's tile masks)
+}
+
+// (the packed table feeds the k_spconv_w instances only, whatever DZ_TUNE_SPCONV_W says: the conditions of spconv_w_packed_dispatch)
+const char *dz_spconv_variant_split_packed(int cin, int cout) {
+    if (cin == 16 && cout == 16) return "k_spconv_w<16x16>";
+    if (cin == 16 && cout == 32) return "k_spconv_w<16x32>";
+    if (cin == 32 && cout == 32) return "k_spconv_w<32x32>";
+    return "none";
+}
+
+const char *dz_spconv_variant_split_arm(int cin, int cout, int kvol, int has_tile_masks, size_t nbr_bytes) {
+    const bool masks = has_tile_masks && nbr_bytes > 0 && nbr_bytes < 0x80000000ull;
+    const char *name = split_name(cin, cout, masks);
+    if (name[0] == 'n' || name[9] == 'w') return name;
+    const int cout_pad = cout < 32 ? 32 : cout;
+    const bool ring = masks && !tune("DZ_TUNE_SPCONV_NOGN", 0) && (cout_pad != 128 || h_ring_ok(cin, kvol, tune("DZ_TUNE_SPCONV128", 3)));
+    static thread_local char buf[64];
+    snprintf(buf, sizeof(buf), "%s %s", name, ring ? "ring" : "lds");
+    return buf;
 }
 
 }  // extern "C"

@@ -374,6 +374,12 @@ int dz_linear_forward_split(const float *x, long rows, int cin, int x_stride, co
                             const float *shift, const float *group_shift, int group_rows, int relu, float *y, int y_stride, int math,
                             int out_f32, int group_max, void *stream);
 const char *dz_spconv_variant_split(int cin, int cout);
+/* ... and with the arm of a launch whose table has kvol taps, comes with / without tile masks and is nbr_bytes long: "<instance> ring"
+ * (neighbour indices through a register ring) or "<instance> lds" (the table slice staged in LDS: no masks, a table of 2 GiB or
+ * more); the k_spconv_w instances have one arm and keep their plain name. */
+const char *dz_spconv_variant_split_arm(int cin, int cout, int kvol, int has_tile_masks, size_t nbr_bytes);
+/* ... and of dz_spconv_forward_split_packed ("none": a layer it refuses). */
+const char *dz_spconv_variant_split_packed(int cin, int cout);
 /* Cross-attention of a few queries over a long memory with the key / value projections folded into the queries (csrc/xattn_fold.hip;
  * multi_head_attention.py:199-288 as called by decoder.py:79-84 for the geometry refiner: 3 queries x 4096 memory points x 8 heads).
  * Equal to  out = softmax(scale * (q_h) . (Wk_h m + bk_h)) (Wv_h m + bv_h)  per head, computed WITHOUT projecting the memory:

@@ -18,8 +18,8 @@ BOX_TOL = 3e-2
 
 
 def test_single_layers_in_f16_mode(device):
-    """One dense 3x3 layer (resident-tile kernel), one 1x1 layer (generic kernel) and one sparse layer: 'f16' against fp32 torch on the
-    SAME fp32 inputs - the error is that of rounding inputs and weights to fp16 (2^-11 relative each), not more."""
+    """One dense 3x3 layer (resident-tile kernel) in 'f16x2' and 'f16' against fp32 torch on the SAME fp32 inputs - the error is that of
+    rounding inputs and weights to fp16 (2^-11 relative each), not more - and one sparse layer in 'f16' against float64."""
     from detzero_amd import ops
     from detzero_amd.det_modules import conv_layer
     g = torch.Generator().manual_seed(0)
@@ -41,6 +41,12 @@ def test_single_layers_in_f16_mode(device):
         assert err < tol, (math, err)
         if math == 3:
             assert err > 1e-5            # it really is the single-product path
+    # the sparse layer: 64 -> 64 submanifold on the gather and on the x-run kernel, 'f16' against float64 on the operands as stored, under
+    # the dense 'f16' bound and above the 'f16x2' one (it really is the single-product path): tests/test_gpu_sparse_conv.py
+    from tests import test_gpu_sparse_conv as sp
+    for engine in ('split', 'x'):
+        name, worst = sp.run_case(sp.sp_case(engine, 'f16', 64, 64, 'subm', 'plain'), device)
+        assert sp.BOUND['f16x2'] < worst <= sp.BOUND['f16'], (name, worst)
 
 
 def test_f16_mode_on_the_headline_workload(device):
