@@ -158,23 +158,13 @@ __device__ __forceinline__ void load_hfrag(HFrag<T> &f, const v4u *__restrict__ 
     }
 }
 
-// TM (term-major): the three terms outermost, so that consecutive MFMAs go to different accumulators when a wave has more than
-// one (same bits: every accumulator still receives lo.hi, hi.lo, hi.hi in that order)
-template <class T, class M, bool TM = false>
+template <class T, class M>
 __device__ __forceinline__ void mma_hfrag(const HFrag<T> &f, f32x16 (&acc)[T::CT][T::PT]) {
     if constexpr (M::TERMS == 1) {              // single product on the hi halves (the lo fragment reads are dead code and disappear)
 #pragma unroll
         for (int ct = 0; ct < T::CT; ++ct)
 #pragma unroll
             for (int pt = 0; pt < T::PT; ++pt) acc[ct][pt] = M::mma(f.c_hi[ct], f.p_hi[pt], acc[ct][pt]);
-    } else if constexpr (TM) {
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-#pragma unroll
-            for (int ct = 0; ct < T::CT; ++ct)
-#pragma unroll
-                for (int pt = 0; pt < T::PT; ++pt)
-                    acc[ct][pt] = M::mma(term == 0 ? f.c_lo[ct] : f.c_hi[ct], term == 1 ? f.p_lo[pt] : f.p_hi[pt], acc[ct][pt]);
     } else {
 #pragma unroll
         for (int ct = 0; ct < T::CT; ++ct)
@@ -346,17 +336,9 @@ __device__ __forceinline__ void store_tile_pair16(const f32x16 (&acc)[T::CT][T::
 // `issue(stage, slot)` loads the chunk the caller's iterator points at (slot = std::integral_constant<int, chunk % NS>, the
 // static index of `stage`); it may issue EXTRA further loads AFTER the stage's NST ones in every call (the sparse conv's
 // neighbour-list prefetch) - the vmcnt bookkeeping below accounts for them.
-// DIAG (development, -DDZ_SPCONV_DIAG builds only; results are garbage for 1-4): 1 = no MFMAs, 2 = no LDS fragment
-// reads, 3 = no LDS stage stores, 4 = no global loads - what is left tells which resource a kernel's time goes to.
-template <class T>
-__device__ __forceinline__ void keep_hfrag(HFrag<T> &f) {
-#pragma unroll
-    for (int i = 0; i < T::PT; ++i) asm volatile("" ::"v"(f.p_hi[i]), "v"(f.p_lo[i]));
-#pragma unroll
-    for (int i = 0; i < T::CT; ++i) asm volatile("" ::"v"(f.c_hi[i]), "v"(f.c_lo[i]));
-}
-
-template <class T, class M, int NS, int EXTRA = 0, int DIAG = 0, bool FREE2 = false, class Issue, class Advance>
+// FREE2: phase 2 (loads, then MFMAs) is not pinned but left to the compiler's scheduler, which interleaves the address math of the
+// loads with the MFMAs (the 8-wave sparse tiles).
+template <class T, class M, int NS, int EXTRA = 0, bool FREE2 = false, class Issue, class Advance>
 __device__ __forceinline__ void hgemm_pipeline(int nchunks, v4u *__restrict__ smem, Issue &&issue, Advance &&advance,
                                                f32x16 (&acc)[T::CT][T::PT], int wp, int wc, int lane, int tid) {
     v4u *const Ps0 = smem, *const Cs0 = smem + 2 * T::PS_U4;          // [2][PS], [2][CS]
@@ -367,21 +349,9 @@ __device__ __forceinline__ void hgemm_pipeline(int nchunks, v4u *__restrict__ sm
 
     static_assert(NS >= 1 && NS <= 4, "1..4 register stages");
     HStage<T> st[NS];
-    auto do_issue = [&](auto &stage, auto slot) {
-        if constexpr (DIAG != 4) issue(stage, slot);
-    };
-    auto do_store = [&](auto &stage, v4u *ps, v4u *cs) {
-        if constexpr (DIAG != 3) store_hstage<T>(stage, ps, cs, tid);
-    };
-    auto do_frag = [&](HFrag<T> &f, const v4u *ps, const v4u *cs, int q) {
-        if constexpr (DIAG != 2) load_hfrag<T>(f, ps, cs, q);
-    };
-    auto do_mma = [&](HFrag<T> &f) {
-        if constexpr (DIAG == 1) keep_hfrag<T>(f); else mma_hfrag<T, M, DIAG == 10>(f, acc);
-    };
-    do_issue(st[0], std::integral_constant<int, 0>{});
-    if constexpr (DIAG != 4) wait_hstage<T, 0>(st[0]);
-    do_store(st[0], Ps0, Cs0);
+    issue(st[0], std::integral_constant<int, 0>{});
+    wait_hstage<T, 0>(st[0]);
+    store_hstage<T>(st[0], Ps0, Cs0, tid);
     __syncthreads();
     // the steady-state loop below is entered only through the branch with UNCONDITIONAL prefetches, so that the
     // compiler's s_waitcnt vmcnt(N) bookkeeping knows exactly NS stages are in flight at the loop header (with
@@ -390,7 +360,7 @@ __device__ __forceinline__ void hgemm_pipeline(int nchunks, v4u *__restrict__ sm
     auto issue_at = [&](auto j_t) {
         constexpr int S = decltype(j_t)::value % NS;
         advance();
-        do_issue(st[S], std::integral_constant<int, S>{});
+        issue(st[S], std::integral_constant<int, S>{});
     };
     if (steady) {
         issue_at(std::integral_constant<int, 1>{});
@@ -404,7 +374,7 @@ __device__ __forceinline__ void hgemm_pipeline(int nchunks, v4u *__restrict__ sm
         if (NS >= 4 && 4 < nchunks) issue_at(std::integral_constant<int, 4>{});
     }
     HFrag<T> f0, f1;
-    do_frag(f0, Ps0 + poff, Cs0 + coff, 0);
+    load_hfrag<T>(f0, Ps0 + poff, Cs0 + coff, 0);
     // chunk c with its stage index S = (c + 1) % NS static; has1: chunk c+1 exists, has2: chunk c+1+NS exists
     auto body = [&](int c, auto s_t, auto static_t, bool has1, bool has2) {
         constexpr int S = decltype(s_t)::value;
@@ -414,27 +384,25 @@ __device__ __forceinline__ void hgemm_pipeline(int nchunks, v4u *__restrict__ sm
         const v4u *Pn = Ps0 + (cur ^ 1) * T::PS_U4 + poff, *Cn = Cs0 + (cur ^ 1) * T::CS_U4 + coff;
         // ---- phase 1: memory instructions first, MFMAs behind them (sched_barrier pins the order: without it the
         // scheduler hoists the MFMAs above the staging and the LDS-write latency lands in front of the barrier)
-        if (Q == 2) do_frag(f1, Pc, Cc, 1);
+        if (Q == 2) load_hfrag<T>(f1, Pc, Cc, 1);
         if (ALL) {
-            if constexpr (DIAG != 4) wait_hstage<T, (NS - 1) * (NST + EXTRA) + EXTRA>(st[S]);     // steady state: the NS-1 younger stages stay in flight
-            do_store(st[S], Ps0 + (cur ^ 1) * T::PS_U4, Cs0 + (cur ^ 1) * T::CS_U4);
+            wait_hstage<T, (NS - 1) * (NST + EXTRA) + EXTRA>(st[S]);     // steady state: the NS-1 younger stages stay in flight
+            store_hstage<T>(st[S], Ps0 + (cur ^ 1) * T::PS_U4, Cs0 + (cur ^ 1) * T::CS_U4, tid);
         } else if (has1) {
-            if constexpr (DIAG != 4) wait_hstage<T, 0>(st[S]);                  // tail: fewer stages may be in flight - drain
-            do_store(st[S], Ps0 + (cur ^ 1) * T::PS_U4, Cs0 + (cur ^ 1) * T::CS_U4);
+            wait_hstage<T, 0>(st[S]);                  // tail: fewer stages may be in flight - drain
+            store_hstage<T>(st[S], Ps0 + (cur ^ 1) * T::PS_U4, Cs0 + (cur ^ 1) * T::CS_U4, tid);
         }
         __builtin_amdgcn_sched_barrier(0);
-        do_mma(f0);
+        mma_hfrag<T, M>(f0, acc);
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
         // ---- phase 2
-        if (ALL || has1) do_frag(f0, Pn, Cn, 0);
-        if (ALL || has2) { advance(); do_issue(st[S], std::integral_constant<int, S>{}); }
+        if (ALL || has1) load_hfrag<T>(f0, Pn, Cn, 0);
+        if (ALL || has2) { advance(); issue(st[S], std::integral_constant<int, S>{}); }
         if (Q == 2) {
-            // phase 2 order: pinned (loads, then MFMAs) or left to the compiler's scheduler (DIAG 6 / FREE2: measured
-            // 3-5 % faster for the 8-wave sparse tiles, where it interleaves the address math with the MFMAs)
-            if constexpr (DIAG != 6 && !FREE2) __builtin_amdgcn_sched_barrier(0);
-            do_mma(f1);
-            if constexpr (DIAG != 6 && !FREE2) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!FREE2) __builtin_amdgcn_sched_barrier(0);
+            mma_hfrag<T, M>(f1, acc);
+            if constexpr (!FREE2) __builtin_amdgcn_sched_barrier(0);
         }
     };
     using TT = std::integral_constant<bool, true>;

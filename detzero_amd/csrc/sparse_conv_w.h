@@ -42,7 +42,6 @@ struct SpConvHArgs {
     float *out;             // pair16 rows
     int cin, cout, cout_pad, kvol, cap, relu;
     unsigned int in_bytes, w_bytes, nbr_bytes, mask_bytes;
-    int diag;                // -DDZ_SPCONV_DIAG builds only (timing experiments; results are garbage when non-zero)
 };
 
 // chunk descriptor (wave-uniform, lives in SGPRs)
@@ -55,7 +54,7 @@ struct WChunk {
     unsigned int rowoff[2];   // per lane: byte offset of its row of each 16-pixel half in one tap of the table (or out of range)
 };
 
-template <int CIN, int COUT, int G, class M, int WAVES, int OCC, bool PK = false>
+template <int CIN, int COUT, int G, class M, int WAVES, int OCC, bool PK>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC))) void k_spconv_w(SpConvHArgs a) {
     constexpr int KS = CIN / 16;            // 32-deep MFMA steps per tap (16 channels x (hi, lo))
     constexpr int KG = CIN / 8;             // 8-channel groups of a row
@@ -175,10 +174,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)
         for (int s = 0; s < G; ++s) {
             // scalar: rides in the instruction's soffset.  PK: the packed table has one row per (tz, ty) = tap / 3 (the entry is loaded
             // once per slot all the same: a second load of it hits the line, and the hand-counted load stream keeps its shape)
-            unsigned int toff = (PK ? ((c.taps >> (5 * s)) & 31u) / 3u : ((c.taps >> (5 * s)) & 31u)) * nbr_tap_bytes;
-#ifdef DZ_SPCONV_DIAG
-            if (a.diag == 3) toff = 0u;                        // every index load reads tap 0 (cache hits)
-#endif
+            const unsigned int toff = (PK ? ((c.taps >> (5 * s)) & 31u) / 3u : ((c.taps >> (5 * s)) & 31u)) * nbr_tap_bytes;
 #pragma unroll
             for (int h = 0; h < 2; ++h)
                 asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(dst[s][h]) : "v"(c.rowoff[h]), "s"(nrsrc), "s"(toff));
@@ -206,11 +202,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)
                     ix[s][h] = (v & keep) | ~keep;
                 }
                 if (__ballot(ix[s][h] >= 0) != 0ull) pres |= 1u << (2 * s + h);
-                unsigned int base = (unsigned int)ix[s][h] * (unsigned int)ROWB + (unsigned int)(kg * 16);
-#ifdef DZ_SPCONV_DIAG
-                if (a.diag == 2) base |= 0x80000000u;         // gathers out of range: same instructions, nothing fetched
-                if (a.diag == 5) base = (unsigned int)(lane * 16);     // every gather hits the same 1 KB
-#endif
+                const unsigned int base = (unsigned int)ix[s][h] * (unsigned int)ROWB + (unsigned int)(kg * 16);
                 asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(dst[s][h][0]) : "v"(base), "s"(prsrc));
                 if constexpr (KS == 2)
                     asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:64" : "=v"(dst[s][h][KS - 1]) : "v"(base), "s"(prsrc));
@@ -218,9 +210,6 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)
         }
         pres &= (1u << (2 * c.nslots)) - 1u;                   // repeated slots: loaded, not multiplied
         if (!c.live) pres = 0u;
-#ifdef DZ_SPCONV_DIAG
-        if (a.diag == 1) pres = 0u;                           // no MFMAs
-#endif
     };
     // residual rows of the chunk's tile, in the accumulators' layout (issued only behind the gathers of a tile's LAST chunk)
     auto issue_res = [&](const WChunk &c, uint2 (&dst)[NR]) {
@@ -298,9 +287,6 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)
                 }
                 uint2 hi, lo;
                 split4<M>(v, hi, lo);
-#ifdef DZ_SPCONV_DIAG
-                if (a.diag == 4 && row != 12345) continue;     // no stores
-#endif
                 if (rok) {
                     unsigned char *gp = reinterpret_cast<unsigned char *>(a.out) + ((size_t)row * COUT + (col & ~7)) * 4 + (col & 7) * 2;
                     *reinterpret_cast<uint2 *>(gp) = hi;
@@ -353,7 +339,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)
     asm volatile("s_waitcnt vmcnt(0)");
 }
 
-template <int CIN, int COUT, int G, class M, int WAVES, int OCC, bool PK = false>
+template <class M, int CIN, int COUT, int G, int WAVES, int OCC, bool PK>
 static int launch_spconv_w(const SpConvHArgs &a, hipStream_t stream) {
     const int lds = a.kvol * (COUT / 16) * (CIN / 8) * 2 * 16 * 16 + 64 * 4;
     static PerDeviceFlags lds_done;

@@ -39,8 +39,6 @@
 // Accumulation order per output element: tz, kc, tap, k - fixed, independent of the tile the row falls into.
 // Epilogue = store_tile_pair16 (hgemm.h): BatchNorm scale / shift, residual, ReLU, split, 32-byte stores, staged through the
 // window buffer the tile has finished with.
-#include <stdlib.h>
-
 #include "hgemm.h"
 
 namespace dz {
@@ -55,12 +53,13 @@ struct SpConvXArgs {
     float *out;
     int cin, cout, cap, relu;
     unsigned int in_bytes, w_bytes, nbr_bytes;
-    unsigned long long *dbg;    // DIAG bit 9 builds: per-wave cycle sums (8 words per wave) or null
     const int *perm;            // output row of each (unit, position) when the table is in tap-set order, or null
     int *queue;                 // 10 words behind the windows: next ticket of each XCD's tile queue, workgroups done, single-unit queue
-    int xrun;                   // consecutive tiles per XCD run (8; DZ_TUNE_XRUN)
-    int steal, singles;         // tail: take whole tiles from other XCDs' queues before the single units; single units per workgroup (1)
-    int sload;                  // window words through scalar loads (1; DZ_TUNE_X_SLOAD)
+    // the schedule, filled by the host with what ships (X_SCHEDULE below).  Kernel arguments, not constants: the kernel is kept
+    // instruction for instruction as it was measured
+    int xrun;                   // consecutive tiles per XCD run
+    int steal, singles;         // tail: take whole tiles from other XCDs' queues before the single units; single units per workgroup
+    int sload;                  // window words through scalar loads
 };
 
 template <int COUT_, int WP_, int WC_, int PT_, int TAPS_, int D_, int RCAP_>
@@ -183,9 +182,7 @@ struct XStage {
     bool live, gather, tz_first, tile_first;    // gather: the slab's window does not fit the buffer, operands come from global memory
 };
 
-// DIAG (development, DZ_TUNE_X_DIAG; timing experiments, results are garbage): bit 0 no MFMAs, 1 no fragment LDS reads, 2 no weight
-// loads, 3 no window loads, 4 no barriers, 5 no epilogue, 7 no tap skipping
-template <class C, class M, int DIAG = 0>
+template <class C, class M>
 __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_spconv_x(SpConvXArgs a) {
     constexpr int PT = C::PT, CT = C::CT, COUT = C::COUT, RCAP = C::RCAP, NW = C::NW, D = C::D, TAPS = C::TAPS, SPS = C::SPS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -194,10 +191,9 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     const int wp = wid / C::WC, wc = wid % C::WC, l31 = lane & 31, kh = lane >> 5;
     const int m = min(*a.d_m_out, a.cap);
     const int nunits = (m + C::UR - 1) / C::UR;
-    // tiles of two units while at least a unit per workgroup remains beyond them (a multiple of 64 = whole runs for all 8 queues), then
-    // single units
+    // tiles of two units while at least `singles` units per workgroup remain beyond them (a multiple of 8 XRUN = whole runs for all 8
+    // queues), then single units
     const int XRUN = a.xrun;
-    // single-unit tickets per workgroup at the end of the launch (0 unless forced: measured best at 8, 16 and 32 frames per pass)
     const int singles = a.singles >= 0 ? a.singles : 0;
     const int nfull = (max(nunits - singles * (int)gridDim.x, 0) / 2) / (8 * XRUN) * (8 * XRUN);
     const int nk = a.cin / 16;
@@ -307,7 +303,7 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 if (a.sload) {
                     asm volatile("s_load_dwordx4 %0, %3, 0x0\n\ts_load_dwordx4 %1, %3, 0x10\n\ts_load_dwordx4 %2, %3, 0x20\n\ts_waitcnt lgkmcnt(0)"
                                  : "=&s"(w0), "=&s"(w1), "=&s"(w2) : "s"(wq) : "memory");
-                } else {            // (development knob DZ_TUNE_X_SLOAD=0: the round-4 loads)
+                } else {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         w0[q] = __builtin_amdgcn_readfirstlane(wq[q]);
@@ -351,7 +347,6 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     // run I of my share of stage s's window pass (WPWIN per wave and stage, always: a run past the window's end - every run of a
     // stage past the end of the stream - fetches nothing, so the per-wave load counts stay static)
     auto issue_win = [&](const XStage &s, auto i_t) {
-        if constexpr (DIAG & 8) return;
         constexpr int I = decltype(i_t)::value;
         const int left = s.wcnt - 1 - wid * 16 - I * NW * 16;     // rows of the window after the first row of my run
         // (rows past the window's end re-read its last row: always inside the buffer, never referenced)
@@ -372,7 +367,6 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     };
     // run I of my share of the weight slices of step q of stage s -> slot `slot` (WPW per wave, always)
     auto issue_w = [&](const XStage &s, int q, int slot, auto i_t) {
-        if constexpr (DIAG & 4) return;
         constexpr int I = decltype(i_t)::value;
         constexpr bool part = C::WJ % NW != 0 && I == C::WPW - 1;             // the last, partial round
         const bool ok = !part || w_last_ok;
@@ -421,7 +415,6 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     auto mfma_slot = [&](const Frag &f, auto i_t) {
         constexpr int i = decltype(i_t)::value, term = i / (CT * PT), pt = (i % (CT * PT)) / CT, ct = i % CT;
         if constexpr (term < 3 - M::TERMS) return;
-        if constexpr (DIAG & 1) { asm volatile("" ::"v"(f.c_hi[ct]), "v"(f.c_lo[ct]), "v"(f.p_hi[pt]), "v"(f.p_lo[pt])); return; }
         acc[ct][pt] = M::mma(term == 0 ? f.c_lo[ct] : f.c_hi[ct], term == 1 ? f.p_lo[pt] : f.p_hi[pt], acc[ct][pt]);
     };
     auto tap_block = [&](const Frag &f, auto &&fill) {        // fill(slot): the filler behind slot's MFMA
@@ -440,8 +433,6 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     };
     static_assert(FS == 6 || FS == 12, "slots per tap");
 
-    unsigned long long tm_vm = 0ull, tm_bar = 0ull, tm_step = 0ull, tm_epi = 0ull, tm_gen = 0ull, tm_n = 0ull;
-    const unsigned long long tm_start = (DIAG & 512) ? __builtin_readcyclecounter() : 0ull;
     XStage cur = gen();
     XStage nxt = gen();
     __syncthreads();
@@ -478,12 +469,8 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         const bool GM = cur.gather;          // gather mode: the B operands come from global memory, not from the window (one small branch
                                              // per operand read: two copies of the step do not fit the register file)
         constexpr int NV = (D - 1) * C::WPW + ((Q >= 1 && Q <= D - 1) ? C::WINPW : 0);     // younger loads that may stay in flight
-        unsigned long long t_top = 0ull;
-        if constexpr (DIAG & 512) t_top = __builtin_readcyclecounter();
-        if constexpr (!(DIAG & 256)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV) : "memory");
-        if constexpr (DIAG & 512) { const unsigned long long t = __builtin_readcyclecounter(); tm_vm += t - t_top; t_top = t; }
-        if constexpr (!(DIAG & 16)) __syncthreads();
-        if constexpr (DIAG & 512) { const unsigned long long t = __builtin_readcyclecounter(); tm_bar += t - t_top; t_top = t; }
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV) : "memory");
+        __syncthreads();
         if (Q == 0 && cur.tz_first) {
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
@@ -517,14 +504,7 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         // straight from global memory
         auto frag_reads = [&](Frag &f, auto t_t) {
             constexpr int t = decltype(t_t)::value, ty = TAPS == 3 ? Q : t / 3, tx = t % 3;
-            f.any = (DIAG & 128) ? 3u : (anym >> ((ty * 3 + tx) * 2)) & 3u;       // (DIAG 128: no tap skipping)
-            if constexpr (DIAG & 2) {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) asm volatile("" : "+v"(f.c_hi[ct]), "+v"(f.c_lo[ct]));
-#pragma unroll
-                for (int pt = 0; pt < PT; ++pt) asm volatile("" : "+v"(f.p_hi[pt]), "+v"(f.p_lo[pt]));
-                return;
-            }
+            f.any = (anym >> ((ty * 3 + tx) * 2)) & 3u;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
                 f.c_hi[ct] = *reinterpret_cast<const v4u *>(smem + w_hi_o + (t * COUT + ct * 32) * 64);
@@ -620,18 +600,11 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) asm volatile("" : "+v"(fp.p_hi[pt]), "+v"(fp.p_lo[pt]));
         }
-        if constexpr (DIAG & 512) { tm_step += __builtin_readcyclecounter() - t_top; ++tm_n; }
     };
 
     int orow[PT][2];            // output rows of my epilogue items (fragment pt, row (lane >> 2) + 16 i of it), -1 = none
     while (cur.live) {
         const bool tile_last = !nxt.live || nxt.tile_first;
-        if (tile_last) {
-            // (round 5: the rows of the epilogue items - through the row map when the table is in tap-set order - are fetched at the START OF
-            // THE EPILOGUE, not here: as plain loads in front of the stage the compiler's wait-count pass, which does not see the asm loads
-            // of the stream, put an `s_waitcnt vmcnt(0)` before them and emptied the prefetch queue at the start of every tile's last
-            // stage; as asm loads their results crossed the stage in registers the compiler is free to copy before they land)
-        }
         step(std::integral_constant<int, 0>{});
         if constexpr (SPS == 3) {
             step(std::integral_constant<int, 1>{});
@@ -640,8 +613,6 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         if (tile_last) {
             // last stage of the tile: finish its last tap, then its window buffer (every wave is done with it after the barrier)
             // stages the epilogue; the loads in flight go to the other window buffer and to other weight slots
-            unsigned long long t_e = 0ull;
-            if constexpr (DIAG & 512) t_e = __builtin_readcyclecounter();
             if (cur.gather) {
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(younger_of(SPS - 1, TAPS - 1)) : "memory");
 #pragma unroll
@@ -651,6 +622,10 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             fp.any = 0u;
             __syncthreads();
             {
+                // (the rows of the epilogue items are fetched here, not in front of the tile's last stage: as plain loads there the
+                // compiler's wait-count pass, which does not see the asm loads of the stream, put an `s_waitcnt vmcnt(0)` before them
+                // and emptied the prefetch queue; as asm loads their results crossed the stage in registers the compiler may copy
+                // before they land)
                 const int nu = cur.half ? 1 : 2;
 #pragma unroll
                 for (int pt = 0; pt < PT; ++pt)
@@ -662,14 +637,6 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             }
             int next_ticket = 0;            // the ticket of the tile after next (thread 0; read at the end of the epilogue)
             if (tid == 0) next_ticket = take_ticket();
-            if constexpr (DIAG & 32) {
-#pragma unroll
-                for (int i = 0; i < CT; ++i)
-#pragma unroll
-                    for (int j = 0; j < PT; ++j)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) asm volatile("" ::"v"(acc[i][j][e]));
-            } else
             x_store_tile<C, M>(acc, smem + C::OFF_WIN + cur.wb * C::WIN_BYTES, sc_s, sh_s, a.cout, a.relu != 0,
                                reinterpret_cast<const unsigned char *>(a.residual), reinterpret_cast<unsigned char *>(a.out), wc, lane, wid, orow);
 #pragma unroll
@@ -679,22 +646,11 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
             if (tid == 0) tk_s[cur.seq & 1] = next_ticket;
-            if constexpr (DIAG & 512) tm_epi += __builtin_readcyclecounter() - t_e;
             if (!nxt.live) break;
         }
         prev_gather = cur.gather;
         cur = nxt;
-        if constexpr (DIAG & 512) {
-            const unsigned long long t_g = __builtin_readcyclecounter();
-            nxt = gen();
-            tm_gen += __builtin_readcyclecounter() - t_g;
-        } else nxt = gen();
-    }
-    if constexpr (DIAG & 512) {
-        if (a.dbg && lane == 0) {
-            unsigned long long *d = a.dbg + ((size_t)blockIdx.x * NW + wid) * 8;
-            d[0] = tm_vm; d[1] = tm_bar; d[2] = tm_step; d[3] = tm_epi; d[4] = tm_gen; d[5] = tm_n; d[6] = __builtin_readcyclecounter() - tm_start; d[7] = 1ull;
-        }
+        nxt = gen();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // the last workgroup to get here resets the queues (every other one has taken its last ticket: its atomics have returned)
@@ -785,92 +741,43 @@ __global__ __launch_bounds__(256) void k_xwin(const int *__restrict__ nbr, int c
 using X32 = XCfg<32, 8, 1, 2, 9, 1, 896>;
 using X64 = XCfg<64, 8, 1, 2, 3, 2, 896>;
 using X128 = XCfg<128, 4, 2, 2, 3, 2, 640>;
-// development variants of the 32-channel configuration (DZ_TUNE_X32 = 1 / 2): 256-thread workgroups whose LDS lets TWO of them share a
-// CU (one's epilogue / barrier waits under the other's steps): one window row per step with the full window, or whole slabs from a
-// short window
-using X32B = XCfg<32, 4, 1, 2, 3, 2, 448>;
-using X32C = XCfg<32, 4, 1, 2, 9, 1, 320>;
-static int x_run_len() {          // tiles per XCD run (development knob; a power of two in [1, 64])
-    static const int v = getenv("DZ_TUNE_XRUN") ? atoi(getenv("DZ_TUNE_XRUN")) : 8;
-    return v >= 1 && v <= 64 && (v & (v - 1)) == 0 ? v : 8;
-}
-static int x_steal() { static const int v = getenv("DZ_TUNE_X_STEAL") ? atoi(getenv("DZ_TUNE_X_STEAL")) : 1; return v; }
-// single-unit tickets per workgroup at the end of a launch: -1 = by the launch's size (k_spconv_x), else forced (development knob).
-// A/B at 32 frames per pass: 0 singles 1063.8 frames/s against 1059.6 with one per workgroup (round 4)
-static int x_singles() { static const int v = getenv("DZ_TUNE_X_SINGLES") ? atoi(getenv("DZ_TUNE_X_SINGLES")) : -1; return v >= -1 && v <= 8 ? v : -1; }
-static int x_sload() { static const int v = getenv("DZ_TUNE_X_SLOAD") ? atoi(getenv("DZ_TUNE_X_SLOAD")) : 1; return v; }
-static int x32_variant() {
-    static const int v = getenv("DZ_TUNE_X32") ? atoi(getenv("DZ_TUNE_X32")) : 0;
-    return v;
-}
-
-template <class C, class M, int DIAG = 0>
-static int launch_x(const SpConvXArgs &a, hipStream_t stream) {
-    static PerDeviceFlags done;
-    if (int rc = reserve_lds(reinterpret_cast<const void *>(&k_spconv_x<C, M, DIAG>), C::LDS_BYTES, done, "dz_spconv_forward_split_x")) return rc;
-    int grid = ceil_div(a.cap, C::UR);
-    const int cus = device_cus() * (C::THREADS <= 256 && 2 * C::LDS_BYTES <= 160 * 1024 ? 2 : 1);      // (workgroups that fit a CU in pairs)
-    if (grid > cus) grid = cus;
-    grid = (grid + 7) & ~7;
-    if (grid < 8) grid = 8;
-    hipLaunchKernelGGL((k_spconv_x<C, M, DIAG>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, stream, a);
-    DZ_LAUNCH_CHECK();
-    return DZ_OK;
-}
-
-[[maybe_unused]] static unsigned long long *x_dbg_buf = nullptr;      // (diag builds) cycle sums of the last timed launch
+// SpConvXArgs::xrun, steal, singles, sload: runs of 8 tiles, stealing on, no single-unit tickets, scalar window loads
+#define X_SCHEDULE 8, 1, 0, 1
 
 template <class C>
-static int x_diag(const SpConvXArgs &a, hipStream_t stream, int d) {
-    switch (d) {
-        case 1: return launch_x<C, MathF16, 1>(a, stream);
-        case 3: return launch_x<C, MathF16, 3>(a, stream);
-        case 4: return launch_x<C, MathF16, 4>(a, stream);
-        case 8: return launch_x<C, MathF16, 8>(a, stream);
-        case 12: return launch_x<C, MathF16, 12>(a, stream);
-        case 16: return launch_x<C, MathF16, 16>(a, stream);
-        case 32: return launch_x<C, MathF16, 32>(a, stream);
-        case 15: return launch_x<C, MathF16, 15>(a, stream);
-        case 128: return launch_x<C, MathF16, 128>(a, stream);
-        case 144: return launch_x<C, MathF16, 144>(a, stream);
-        case 256: return launch_x<C, MathF16, 256>(a, stream);
-        case 2: return launch_x<C, MathF16, 2>(a, stream);
-        case 258: return launch_x<C, MathF16, 258>(a, stream);
-        case 259: return launch_x<C, MathF16, 259>(a, stream);
-        case 271: return launch_x<C, MathF16, 271>(a, stream);
-        case 287: return launch_x<C, MathF16, 287>(a, stream);
-        case 319: return launch_x<C, MathF16, 319>(a, stream);
-        case 447: return launch_x<C, MathF16, 447>(a, stream);
-        case 512: return launch_x<C, MathF16, 512>(a, stream);
-        default: return launch_x<C, MathF16>(a, stream);
-    }
+static int launch_x(const SpConvXArgs &a, int math, hipStream_t stream) {
+    auto go = [&](auto m_t) {
+        using M = typename decltype(m_t)::type;
+        static PerDeviceFlags done;
+        if (int rc = reserve_lds(reinterpret_cast<const void *>(&k_spconv_x<C, M>), C::LDS_BYTES, done, "dz_spconv_forward_split_x")) return rc;
+        int grid = ceil_div(a.cap, C::UR);
+        const int cus = device_cus();            // one 512-thread workgroup per CU
+        if (grid > cus) grid = cus;
+        grid = (grid + 7) & ~7;
+        if (grid < 8) grid = 8;
+        hipLaunchKernelGGL((k_spconv_x<C, M>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, stream, a);
+        DZ_LAUNCH_CHECK();
+        return (int)DZ_OK;
+    };
+    if (math == DZ_MATH_F16) return go(TypeTag<MathF16H>{});
+    return math == DZ_MATH_F16X2 ? go(TypeTag<MathF16>{}) : go(TypeTag<MathBF16>{});
 }
 
-template <class M>
-static int x_dispatch(const SpConvXArgs &a, hipStream_t stream) {
-#ifdef DZ_SPCONV_DIAG
-    static const int diag = getenv("DZ_TUNE_X_DIAG") ? atoi(getenv("DZ_TUNE_X_DIAG")) : 0;
-    if (diag && M::ID == 1 && M::TERMS == 3) {
-        SpConvXArgs b = a;
-        if (diag & 512) {
-            static unsigned long long *dbg = nullptr;
-            if (!dbg && hipMalloc(&dbg, 256 * 8 * 8 * sizeof(unsigned long long)) != hipSuccess) dbg = nullptr;
-            if (dbg) (void)hipMemsetAsync(dbg, 0, 256 * 8 * 8 * sizeof(unsigned long long), stream);
-            b.dbg = dbg;
-            x_dbg_buf = dbg;
-        }
-        if (a.cout == 32) return x_diag<X32>(b, stream, diag);
-        if (a.cout == 64) return x_diag<X64>(b, stream, diag);
-        return x_diag<X128>(b, stream, diag);
-    }
-#endif
-    if (a.cout == 32) {
-        if (x32_variant() == 1) return launch_x<X32B, M>(a, stream);
-        if (x32_variant() == 2) return launch_x<X32C, M>(a, stream);
-        return launch_x<X32, M>(a, stream);
-    }
-    if (a.cout == 64) return launch_x<X64, M>(a, stream);
-    return launch_x<X128, M>(a, stream);
+// The configurations of the engine, by channel count (cin == cout): what dz_spconv_forward_split_x launches, and what the
+// dz_spconv_x_* functions report of it.
+struct XVariant {
+    int channels, unit_rows, window_rows;
+    const char *name;
+    int (*launch)(const SpConvXArgs &, int math, hipStream_t);
+};
+static const XVariant kX[] = {{32, X32::UR, X32::RCAP, "k_spconv_x<32>", launch_x<X32>},
+                              {64, X64::UR, X64::RCAP, "k_spconv_x<64>", launch_x<X64>},
+                              {128, X128::UR, X128::RCAP, "k_spconv_x<128>", launch_x<X128>}};
+
+static const XVariant *x_select(int cin, int cout) {
+    for (const XVariant &v : kX)
+        if (cin == cout && cout == v.channels) return &v;
+    return nullptr;
 }
 
 }  // namespace dz
@@ -880,19 +787,13 @@ using namespace dz;
 extern "C" {
 
 int dz_spconv_x_tile_rows(int cin, int cout) {
-    if (cin != cout) return 0;
-    if (cout == 32) return x32_variant() == 1 ? X32B::UR : (x32_variant() == 2 ? X32C::UR : X32::UR);
-    if (cout == 64) return X64::UR;
-    if (cout == 128) return X128::UR;
-    return 0;
+    const XVariant *v = x_select(cin, cout);
+    return v ? v->unit_rows : 0;
 }
 
 int dz_spconv_x_window_rows(int cin, int cout) {
-    if (cin != cout) return 0;
-    if (cout == 32) return x32_variant() == 1 ? X32B::RCAP : (x32_variant() == 2 ? X32C::RCAP : X32::RCAP);
-    if (cout == 64) return X64::RCAP;
-    if (cout == 128) return X128::RCAP;
-    return 0;
+    const XVariant *v = x_select(cin, cout);
+    return v ? v->window_rows : 0;
 }
 
 size_t dz_spconv_x_windows_words(int cap_out, int tile_rows) {
@@ -917,12 +818,13 @@ int dz_spconv_forward_split_x(const float *in, int in_rows, int cin, const int *
     hipStream_t stream = (hipStream_t)stream_;
     DZ_CHECK_ARG(in && nbr_packed && windows && d_m_out && w && out, "dz_spconv_forward_split_x: null pointer");
     DZ_CHECK_ARG(math == DZ_MATH_F16X2 || math == DZ_MATH_BF16X2 || math == DZ_MATH_F16, "dz_spconv_forward_split_x: math %d is not a split mode", math);
-    const int tr = dz_spconv_x_tile_rows(cin, cout);
-    if (tr == 0) {
+    const XVariant *v = x_select(cin, cout);
+    if (!v) {
         set_error("dz_spconv_forward_split_x: %d -> %d channels (submanifold 32 -> 32, 64 -> 64, 128 -> 128 only)", cin, cout);
         return DZ_ERR_UNSUPPORTED;
     }
-    DZ_CHECK_ARG(tile_rows == tr, "dz_spconv_forward_split_x: windows built for %d-row tiles, the %d-channel kernel uses %d", tile_rows, cout, tr);
+    DZ_CHECK_ARG(tile_rows == v->unit_rows, "dz_spconv_forward_split_x: windows built for %d-row tiles, the %d-channel kernel uses %d", tile_rows, cout,
+                 v->unit_rows);
     if (cap_out == 0) return DZ_OK;
     const size_t in_bytes = (size_t)in_rows * cin * sizeof(float), w_bytes = (size_t)27 * cout * cin * sizeof(float),
                  nbr_bytes = (size_t)9 * cap_out * sizeof(int);
@@ -931,39 +833,14 @@ int dz_spconv_forward_split_x(const float *in, int in_rows, int cin, const int *
         return DZ_ERR_UNSUPPORTED;
     }
     SpConvXArgs a{in, nbr_packed, windows, d_m_out, w, scale, shift, residual, out, cin, cout, cap_out, relu,
-                  (unsigned int)in_bytes, (unsigned int)w_bytes, (unsigned int)nbr_bytes, nullptr, perm,
-                  windows + (size_t)ceil_div(cap_out, tile_rows) * 6, x_run_len(), x_steal(), x_singles(), x_sload()};
-    if (math == DZ_MATH_F16) return x_dispatch<MathF16H>(a, stream);
-    return math == DZ_MATH_F16X2 ? x_dispatch<MathF16>(a, stream) : x_dispatch<MathBF16>(a, stream);
+                  (unsigned int)in_bytes, (unsigned int)w_bytes, (unsigned int)nbr_bytes, perm,
+                  windows + (size_t)ceil_div(cap_out, tile_rows) * 6, X_SCHEDULE};
+    return v->launch(a, math, stream);
 }
-
-#ifdef DZ_SPCONV_DIAG
-/* (diag builds only, not in the header) cycle sums of the last DZ_TUNE_X_DIAG=512 launch, averaged over the waves that ran */
-int dz_spconv_x_debug_dump(void) {
-    if (!x_dbg_buf) return -1;
-    static unsigned long long h[256 * 8 * 8];
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, x_dbg_buf, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -2;
-    double s[7] = {0, 0, 0, 0, 0, 0, 0}, mx = 0;
-    int n = 0;
-    for (int w = 0; w < 256 * 8; ++w) {
-        if (!h[w * 8 + 7]) continue;
-        ++n;
-        for (int k = 0; k < 7; ++k) s[k] += (double)h[w * 8 + k];
-        if ((double)h[w * 8 + 6] > mx) mx = (double)h[w * 8 + 6];
-    }
-    if (!n) return -3;
-    printf("x-dbg: waves %d  steps/wave %.0f | per step (cycles): vmcnt wait %.0f  barrier %.0f  body %.0f | per wave total: epilogue %.0f  gen %.0f  kernel %.0f (max %.0f)\n", n, s[5] / n,
-           s[0] / s[5], s[1] / s[5], s[2] / s[5], s[3] / n, s[4] / n, s[6] / n, mx);
-    fflush(stdout);
-    return 0;
-}
-#endif
 
 const char *dz_spconv_x_variant(int cin, int cout) {
-    if (cin == 32 && cout == 32) return "k_spconv_x<32>";
-    if (cin == 64 && cout == 64) return "k_spconv_x<64>";
-    if (cin == 128 && cout == 128) return "k_spconv_x<128>";
-    return "none";
+    const XVariant *v = x_select(cin, cout);
+    return v ? v->name : "none";
 }
 
 }  // extern "C"

@@ -445,7 +445,7 @@ class VoxelResBackBone8x(_Cached):
 
         # opt-in (PACKED_TABLES): tables read only by the small-channel split-math kernels (<= 32 output channels: conv_input, conv1,
         # conv2) built packed - a third of the words; the index chain gains what the decode costs the convolutions
-        pack = PACKED_TABLES and self.math != 0 and not tiled and self.layout == 0 and os.environ.get('DZ_TUNE_SPCONV_W', '1') != '0'
+        pack = PACKED_TABLES and self.math != 0 and not tiled and self.layout == 0
 
         xrun = (self.engine if self.math != 0 else self.f32_engine) == 'xrun' and self.layout == 0
         xrun_couts = tuple(int(c) for c in os.environ.get('DZ_TUNE_XRUN_COUTS', '32,64,128').split(',') if c)

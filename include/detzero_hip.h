@@ -376,7 +376,8 @@ int dz_linear_forward_split(const float *x, long rows, int cin, int x_stride, co
 const char *dz_spconv_variant_split(int cin, int cout);
 /* ... and with the arm of a launch whose table has kvol taps, comes with / without tile masks and is nbr_bytes long: "<instance> ring"
  * (neighbour indices through a register ring) or "<instance> lds" (the table slice staged in LDS: no masks, a table of 2 GiB or
- * more); the k_spconv_w instances have one arm and keep their plain name. */
+ * more; the 128-row tiles of the layers with up to 32 output channels have this arm only); the k_spconv_w instances have one arm and
+ * keep their plain name.  kvol decides nothing. */
 const char *dz_spconv_variant_split_arm(int cin, int cout, int kvol, int has_tile_masks, size_t nbr_bytes);
 /* ... and of dz_spconv_forward_split_packed ("none": a layer it refuses). */
 const char *dz_spconv_variant_split_packed(int cin, int cout);

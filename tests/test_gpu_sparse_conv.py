@@ -26,7 +26,6 @@ import json
 import os
 import subprocess
 import sys
-import time
 import types
 import zlib
 
@@ -90,14 +89,10 @@ FAMILIES = ('k_spconv', 'k_spconv_h', 'k_spconv_w', 'k_spconv_x', 'k_spconv_xf')
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# the dispatch code, restated (csrc/sparse_conv.hip dz_spconv_forward, sparse_conv_h.hip spconv_h_dispatch / launch_spconv_h /
-# spconv_w_packed_dispatch, sparse_conv_x.hip x_dispatch): the instance a launch must report, under a set of DZ_TUNE_* values
+# the dispatch code, restated (csrc/sparse_conv.hip dz_spconv_forward, sparse_conv_h.hip spconv_h_select, sparse_conv_x.hip x_select):
+# the instance a launch must report
 # ------------------------------------------------------------------------------------------------------------------------
-def _knob(env, name, dflt):
-    return int((env or {}).get('DZ_TUNE_' + name, dflt))
-
-
-def expected_name(engine, cin, cout, kvol, masks, env=None):
+def expected_name(engine, cin, cout, kvol, masks):
     if engine == 'f32':
         return {(16, 16): 'k_spconv<128x16x16>', (16, 32): 'k_spconv<128x32x16>', (32, 32): 'k_spconv<128x32x32>'}.get((cin, cout), 'k_spconv<64x64x32>')
     if engine == 'x':
@@ -107,17 +102,11 @@ def expected_name(engine, cin, cout, kvol, masks, env=None):
     if engine == 'packed':
         return 'k_spconv_w<%dx%d>' % (cin, cout)
     cp = max(cout, 32)
-    if cp == 32 and masks and _knob(env, 'SPCONV_W', 1):
+    if cp == 32 and masks:
         return 'k_spconv_w<%dx%d>' % (cin, cout)
-    t128 = _knob(env, 'SPCONV128', 3)
     if cp == 32:
-        name = 'k_spconv_h<128x32x%d>' % cin
-    elif cp == 64:
-        name = 'k_spconv_h<%dx64x32>' % {1: 64, 2: 128}.get(_knob(env, 'SPCONV64', 0), 256)
-    else:
-        name = 'k_spconv_h<%dx128x32>' % {1: 64, 3: 256}.get(t128, 128)
-    ring = masks and not _knob(env, 'SPCONV_NOGN', 0) and not (cp == 128 and t128 == 1 and cin == 128 and kvol == 27)
-    return name + (' ring' if ring else ' lds')
+        return 'k_spconv_h<128x32x%d> lds' % cin
+    return 'k_spconv_h<256x%dx32>' % cp + (' ring' if masks else ' lds')
 
 
 def reported_name(engine, cin, cout, kvol, masks, cap):
@@ -136,7 +125,7 @@ def reported_name(engine, cin, cout, kvol, masks, cap):
 
 def tile_rows(name, cin=0, cout=0):
     """Row tile of an instance: the first template number of k_spconv / k_spconv_h, 32 per wave for k_spconv_w, the unit of the
-    x-run kernels (dz_spconv_x_tile_rows - DZ_TUNE_X32 changes it)."""
+    x-run kernels (dz_spconv_x_tile_rows)."""
     if name.startswith('k_spconv_w'):
         return 32
     if name.startswith('k_spconv_x'):
@@ -151,9 +140,9 @@ def family(name):
 # ------------------------------------------------------------------------------------------------------------------------
 # cases
 # ------------------------------------------------------------------------------------------------------------------------
-def sp_case(engine, mode, cin, cout, kind, edge, masks=True, sort=False, env=None, sweep=False):
+def sp_case(engine, mode, cin, cout, kind, edge, masks=True, sort=False, sweep=False):
     kvol = int(np.prod(KINDS[kind][0]))
-    name = expected_name(engine, cin, cout, kvol, masks, env)
+    name = expected_name(engine, cin, cout, kvol, masks)
     if engine == 'f32':
         arm = kind
     elif engine == 'packed':
@@ -557,14 +546,37 @@ def test_case_table_covers_every_variant():
         assert edges >= set(M_EDGES), (name, sorted(set(M_EDGES) - edges))
     for name in ('k_spconv_h<256x64x32> ring', 'k_spconv_h<256x128x32> ring', 'k_spconv_h<256x64x32> lds', 'k_spconv_h<256x128x32> lds'):
         assert inst_edges[name] >= {'tiles=%d' % t for t in XCD_TILES}, name
-    # the names under the knobs the README lists (the launch table of spconv_h_dispatch, restated in expected_name) - in this process
-    # the knobs are unset, so only the default column can be asked of the library; tests/sparse_conv_child.py asks the others
-    assert expected_name('split', 64, 64, 27, True, {'DZ_TUNE_SPCONV64': '1'}) == 'k_spconv_h<64x64x32> ring'
-    assert expected_name('split', 128, 128, 27, True, {'DZ_TUNE_SPCONV128': '1'}) == 'k_spconv_h<64x128x32> lds'
-    assert expected_name('split', 64, 128, 27, True, {'DZ_TUNE_SPCONV128': '1'}) == 'k_spconv_h<64x128x32> ring'
     lib = L.load()
     assert lib.dz_spconv_variant_split(64, 64) == b'k_spconv_h<256x64x32>' and lib.dz_spconv_variant_split(128, 128) == b'k_spconv_h<256x128x32>'
     assert lib.dz_spconv_variant_split(16, 16) == b'k_spconv_w<16x16>' and lib.dz_spconv_variant_split(48, 48) == b'none'
+
+
+# every variable the sparse-convolution launch code once read, at a value that used to select another instance, tile or schedule
+REMOVED_ENVS = {'DZ_TUNE_SPCONV64': '1', 'DZ_TUNE_SPCONV128': '1', 'DZ_TUNE_SPCONV_W': '0', 'DZ_TUNE_SPCONV_NOGN': '1', 'DZ_TUNE_W16': '0',
+                'DZ_TUNE_W1632': '1', 'DZ_TUNE_SPCONV_D': '1', 'DZ_TUNE_W_DIAG': '1', 'DZ_TUNE_X32': '1', 'DZ_TUNE_XRUN': '1', 'DZ_TUNE_X_STEAL': '0',
+                'DZ_TUNE_X_SINGLES': '1', 'DZ_TUNE_X_SLOAD': '0', 'DZ_TUNE_X_DIAG': '1'}
+_NAMES_CHILD = """
+import json
+from detzero_amd import lib as L
+from tests import test_gpu_sparse_conv as T
+print(json.dumps({'names': [T.reported_name(c.engine, c.cin, c.cout, c.kvol, c.masks, 1000) for c in T.COVERAGE],
+                  'unit_rows': [L.load().dz_spconv_x_tile_rows(c, c) for c in (32, 64, 128)]}))
+"""
+
+
+def test_selection_reads_no_environment_variable():
+    """The name functions and dz_spconv_x_tile_rows in a child process (the variables were read once per process) started with every
+    variable of REMOVED_ENVS set: exactly the defaults, for every case of COVERAGE and for 32 / 64 / 128 channels."""
+    e = dict(os.environ)
+    e.update(REMOVED_ENVS)
+    e['PYTHONPATH'] = ROOT + os.pathsep + e.get('PYTHONPATH', '')
+    p = subprocess.run([sys.executable, '-c', _NAMES_CHILD], env=e, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-3000:], p.stderr[-3000:])
+    got = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
+    assert len(got['names']) == len(COVERAGE)
+    for c, name in zip(COVERAGE, got['names']):
+        assert name == c.expect, (c.label, c.mode, name, c.expect)
+    assert got['unit_rows'] == [256, 256, 128], got['unit_rows']
 
 
 def test_reference_agrees_with_oracle_and_conv3d():
@@ -795,66 +807,3 @@ def test_backbone_launches_vs_float64(mode, engine, device):
     finally:
         ops.spconv_forward = real
         set_sparse_engine(model, before[0], f32_engine=before[1])
-
-
-# ------------------------------------------------------------------------------------------------------------------------
-# GPU: the knobs README.md calls result-neutral, in child processes (they are read once per process)
-# ------------------------------------------------------------------------------------------------------------------------
-# One row per child; together the rows give every knob every value its dispatch code accepts besides the default.  A knob that a
-# later clean-up removes takes its entries out of this table, and nothing else.
-KNOB_ENVS = (
-    {'DZ_TUNE_SPCONV_W': '0', 'DZ_TUNE_SPCONV64': '1', 'DZ_TUNE_SPCONV128': '1', 'DZ_TUNE_X32': '1', 'DZ_TUNE_XRUN': '1', 'DZ_TUNE_X_STEAL': '0',
-     'DZ_TUNE_X_SINGLES': '0', 'DZ_TUNE_X_SLOAD': '0'},
-    {'DZ_TUNE_SPCONV_NOGN': '1', 'DZ_TUNE_SPCONV64': '2', 'DZ_TUNE_SPCONV128': '2', 'DZ_TUNE_W16': '0', 'DZ_TUNE_W1632': '1', 'DZ_TUNE_X32': '2',
-     'DZ_TUNE_XRUN': '64', 'DZ_TUNE_X_SINGLES': '8'},
-    {'DZ_TUNE_SPCONV128': '4', 'DZ_TUNE_W16': '1', 'DZ_TUNE_W1632': '2'},
-    {'DZ_TUNE_W16': '6'},
-    {'DZ_TUNE_W16': '7'},
-)
-
-
-def knob_cases(env):
-    """The coverage cases a set of knobs can change: every layer x mode x arm of the engines the knobs touch (not the per-instance edge
-    sweeps), with the instance the dispatch code launches under them."""
-    touched = set()
-    for k in env:
-        touched |= ({'x'} if k in ('DZ_TUNE_X32', 'DZ_TUNE_XRUN', 'DZ_TUNE_X_STEAL', 'DZ_TUNE_X_SINGLES', 'DZ_TUNE_X_SLOAD') else {'split'})
-    out = []
-    for c in COVERAGE:
-        if c.engine not in touched or c.sweep:
-            continue
-        if c.engine == 'split':
-            w16 = c.expect == 'k_spconv_w<16x16>' or c.expect == 'k_spconv_w<16x32>'
-            if set(env) <= {'DZ_TUNE_W16', 'DZ_TUNE_W1632'} and not w16:
-                continue
-        c2 = types.SimpleNamespace(**vars(c))
-        c2.expect = expected_name(c.engine, c.cin, c.cout, c.kvol, c.masks, env)
-        out.append(c2)
-    return out
-
-
-@pytest.mark.gpu
-def test_knobs_do_not_change_results(device):
-    """tests/sparse_conv_child.py under each row of KNOB_ENVS: the same bounds and write contract as the default build, and the
-    reported name is the instance the dispatch code launches under the knobs.  One child after another, each with its own time limit;
-    the loop ends at the first child that does not exit 0 - after a crash or a time-out nothing more is started on the GPU."""
-    for i, env in enumerate(KNOB_ENVS):
-        e = dict(os.environ)
-        e.update(env)
-        e['PYTHONPATH'] = ROOT + os.pathsep + e.get('PYTHONPATH', '')
-        t0 = time.time()
-        p = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'sparse_conv_child.py'), str(i)], env=e, cwd=ROOT, capture_output=True,
-                           text=True, timeout=600)
-        lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith('{')]
-        print('  child %d %s: exit %d, %d cases, %.0f s' % (i, ' '.join('%s=%s' % (k[8:], v) for k, v in env.items()), p.returncode, len(lines), time.time() - t0))
-        assert p.returncode == 0, (env, p.stdout[-3000:], p.stderr[-3000:])
-        want = knob_cases(env)
-        assert len(lines) == len(want) > 0, (env, len(lines), len(want))
-        for ln, c in zip(lines, want):
-            assert ln['label'] == c.label and ln['mode'] == c.mode and ln['name'] == c.expect, (env, ln, c.expect)
-            assert ln['contract'] == 'ok' and ln['worst'] <= BOUND[c.mode], (env, ln)
-        worst = {}
-        for ln in lines:
-            worst[(ln['name'], ln['mode'])] = max(worst.get((ln['name'], ln['mode']), 0.0), ln['worst'])
-        for (n, m), w in sorted(worst.items()):
-            print('      %-30s %-7s worst normalised error %.3e' % (n, m, w))

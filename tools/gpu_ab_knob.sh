@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU test suite, then the headline with / without environment knobs, two alternating rounds on ONE box:
 #   tools/gpu_ab_knob.sh "NAME=VALUE [NAME2=VALUE2 ...]" [notests] [layers]
-# e.g. DZ_TUNE_EAGER_PYRAMID=1, DZ_BEV_SCATTER=1, DZ_TUNE_XRUN_SORT=0, DZ_TUNE_X32=1, DZ_TUNE_SPCONV_ENGINE=gather, "--batch 32" style
+# e.g. DZ_TUNE_EAGER_PYRAMID=1, DZ_BEV_SCATTER=1, DZ_TUNE_XRUN_SORT=0, DZ_TUNE_SPCONV_ENGINE=gather, "--batch 32" style
 # bench arguments go through BENCH_ARGS.  layers: also the per-layer sparse-convolution table (tools/bench_spconv.py) under both settings.
 cd $GRAFT_REPO_ROOT
 if [ -z "$2" ] || [ "$2" = "-" ]; then timeout 1200 python -m pytest tests -m gpu -q -x --timeout=600 -p no:cacheprovider 2>&1 | tail -4; fi

@@ -2,12 +2,11 @@
 # The evidence set of a round on ONE GPU box (replaces gpu_round2/3/4.sh, gpu_profiles.sh, gpu_pmc*.sh, gpu_trace*.sh, gpu_x_diag.sh,
 # gpu_pdv_prof.sh of earlier rounds): gpu test-suite, smoke, the full bench line (bench.py --full: all legs), rocprofv3 kernel trace of the headline
 # command, HBM-side PMC passes (FETCH_SIZE / WRITE_SIZE, separate passes - never together with a trace domain) and the SQ matrix-pipe
-# counters of the same command, the per-layer sparse benchmark of both engines, the x-run kernel's in-kernel cycle accounting
-# (diag build), the refiner and two-stage (PDV) benches with their traces.
-# usage: tools/gpu_round.sh <tag> [sections]     tag = r05a ...; sections = any of: tests bench trace pmc sq clk layers xdiag refine pdv
+# counters of the same command, the per-layer sparse benchmark of both engines, the refiner and two-stage (PDV) benches with their traces.
+# usage: tools/gpu_round.sh <tag> [sections]     tag = r05a ...; sections = any of: tests bench trace pmc sq clk layers refine pdv
 #        (default: all).  Outputs -> gpurun_out/<round>/<tag>_*  (copy what is to be judged into profiles/).
 TAG=${1:-r05a}
-SECT=${2:-tests bench trace pmc sq clk layers xdiag refine pdv}
+SECT=${2:-tests bench trace pmc sq clk layers refine pdv}
 cd "$(dirname "$0")/.."
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
@@ -75,23 +74,6 @@ fi
 if has layers; then
   echo "==== per-layer sparse benchmark, both engines"
   for e in gather xrun; do DZ_TUNE_SPCONV_ENGINE=$e timeout 300 python tools/bench_spconv.py --batch 16 --reps 20 --math f16x2 2>&1 | tail -23 > $O/${TAG}_spconv_layers_$e.txt; tail -1 $O/${TAG}_spconv_layers_$e.txt; done
-fi
-if has xdiag; then
-  # k_spconv_x with in-kernel cycle counters / one effect removed at a time (-DDZ_SPCONV_DIAG build of sparse_conv_x.hip; DZ_TUNE_X_DIAG
-  # bits: 1 no MFMAs, 2 no fragment LDS reads, 4 no weight loads, 8 no window loads, 16 no barriers, 32 no epilogue, 512 cycle counters;
-  # results are garbage for all but 512, times are not).  XDIAG="512 1 2 ..." picks the list.
-  echo "==== x-run kernel: cycle accounting (diag build)"
-  cp detzero_amd/libdetzero_hip.so /tmp/libdz_orig.so
-  objs=$(ls detzero_amd/csrc/build/*.o | grep -v sparse_conv_x.o)
-  if /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-inline-asm -DDZ_SPCONV_DIAG -c detzero_amd/csrc/sparse_conv_x.hip -o /tmp/spx_diag.o 2>/dev/null &&
-     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs /tmp/spx_diag.o -o detzero_amd/libdetzero_hip.so 2>/dev/null; then
-    for d in ${XDIAG:-512}; do
-      echo "== DZ_TUNE_X_DIAG=$d"
-      DZ_TUNE_SPCONV_ENGINE=xrun DZ_TUNE_X_DIAG=$d timeout 200 python tools/bench_spconv.py --batch 16 --math f16x2 --reps 5 --only 32-32,64-64,128-128 > /tmp/xd.txt 2>&1
-      grep -E "^x" /tmp/xd.txt | grep -v "+res" | sort -u | cut -c1-30,95-125; grep x-dbg /tmp/xd.txt | sort -u
-    done 2>&1 | grep -v "steps/wave *per wave" | tee $O/${TAG}_xrun_cycles.txt
-  else echo "diag build failed"; fi
-  cp /tmp/libdz_orig.so detzero_amd/libdetzero_hip.so
 fi
 if has refine; then
   echo "==== refiner"
