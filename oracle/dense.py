@@ -57,7 +57,7 @@ def center_head_forward(sd, x, prefix='dense_head.', head_order=HEAD_ORDER):
 
 def topk_desc(scores_flat, k):
     """Deterministic top-k: score descending, ties by ascending flat index (torch.topk leaves ties
-    implementation-defined; tests avoid exact ties, this only makes the oracle reproducible)."""
+    implementation-defined; this is the order the decode kernel implements, tests/test_gpu_head_post.py holds it to it on exact ties)."""
     s = scores_flat.numpy()
     order = np.lexsort((np.arange(s.size), -s.astype(np.float64)))
     order = order[:k]

@@ -128,3 +128,35 @@ def canon_tensor(t):
     idx = t.indices.cpu().numpy()
     o = canon_order(idx, t.spatial_shape)
     return idx[o], t.features.cpu()[torch.from_numpy(o)]
+
+
+def nms_on_threshold_rule(boxes_sorted, got, thresh, eps=1e-5):
+    """The on-threshold rule of the rotated-NMS tests.  boxes_sorted (n,7) in descending score order, got: the indices a sweep
+    kept.  Equal to cref.nms_sorted -> 0.  Otherwise the lists may differ only through decisions that sit ON the threshold (an
+    IoU within float noise of it), and one such flip changes which later boxes are suppressed - so every decision of the sweep
+    under test is checked against the IoUs with the boxes IT kept before: above thresh + eps it must have suppressed, below
+    thresh - eps it must have kept.  Only the IoU columns of the kept boxes are evaluated.  Returns the number of on-threshold
+    decisions (>= 1 when the lists differ); raises AssertionError on a decision that is clearly off the threshold."""
+    from oracle import cref
+    boxes_sorted = np.ascontiguousarray(boxes_sorted, np.float32)
+    got = np.asarray(got, np.int64)
+    n = boxes_sorted.shape[0]
+    ref = cref.nms_sorted(boxes_sorted, thresh) if n else np.zeros((0,), np.int64)
+    if np.array_equal(got, ref):
+        return 0
+    assert got.size == 0 or (got.min() >= 0 and got.max() < n), 'kept index outside the list'
+    assert np.all(np.diff(got) > 0), 'kept boxes are not in score order'
+    kept = np.zeros(n, bool)
+    kept[got] = True
+    iou = cref.boxes_iou_bev(boxes_sorted, boxes_sorted[got]) if got.size else np.zeros((n, 0), np.float32)
+    iou = np.where(got[None, :] < np.arange(n)[:, None], iou, np.float32(0))          # only the boxes kept BEFORE box i count
+    worst = iou.max(1).astype(np.float64) if got.size else np.zeros(n)
+    must_drop = worst > thresh + eps
+    must_keep = worst < thresh - eps
+    bad = np.nonzero(must_drop & kept)[0]
+    assert bad.size == 0, 'box %d kept although it overlaps a kept box by %.6f' % (bad[0], worst[bad[0]])
+    bad = np.nonzero(must_keep & ~kept)[0]
+    assert bad.size == 0, 'box %d suppressed although its largest overlap with a kept box is %.6f' % (bad[0], worst[bad[0]])
+    flips = int((~must_drop & ~must_keep).sum())
+    assert flips >= 1, 'NMS differs from the oracle without any on-threshold decision'
+    return flips
