@@ -1,7 +1,8 @@
 // Rotated-rectangle geometry shared by the kernels that need BEV overlaps (head_post.hip: IoU matrices, NMS;
-// wbf.hip: box fusion).  Formula sequence of utils/detzero_utils/ops/iou3d_nms/src/iou3d_nms_kernel.cu:15-232,328-335
-// in fp32; include it AFTER `#pragma clang fp contract(off)` so that discrete decisions (IoU > thr) agree with the CPU
-// restatement wherever libm and ocml agree on sin/cos/atan2.
+// wbf.hip: box fusion; box_ops.hip: 3-D IoU / GIoU matrices, which also need the convex hull of two footprints).
+// Formula sequence of utils/detzero_utils/ops/iou3d_nms/src/iou3d_nms_kernel.cu:15-232,328-335 in fp32; include it
+// AFTER `#pragma clang fp contract(off)` so that discrete decisions (IoU > thr) agree with the CPU restatement
+// wherever libm and ocml agree on sin/cos/atan2.
 #pragma once
 #include "common.h"
 
@@ -111,6 +112,61 @@ __device__ __forceinline__ float rect_iou(const float *A, const float *B, P2 *cp
     const float sa = A[3] * A[4], sb = B[3] * B[4];
     const float so = rect_overlap(A, B, cp, ang, ld);
     return so / fmaxf(sa + sb - so, GEO_EPS);
+}
+
+// ------------------------------------------------------------------------------------------
+// convex hull of two rotated rectangles
+// ------------------------------------------------------------------------------------------
+// compare-exchange into lexicographic (x, then y) order
+__device__ __forceinline__ void lex_cswap(P2 &a, P2 &b) {
+    const bool sw = b.x < a.x || (b.x == a.x && b.y < a.y);
+    const P2 t = a;
+    if (sw) { a = b; b = t; }
+}
+
+// Area of the convex hull of the eight corners of A and B: what boxes_union_kernel / box_union
+// (iou3d_nms_kernel.cu:235-326,352-368) is meant to compute.  That walk reads hull[0] without ever writing it
+// (:288-316), so it is NOT transcribed: this is the mathematical hull area in fp32.  Corners exactly as rect_overlap
+// builds them; the sort is a 19-exchange network on registers (constant indices only); monotone chain that pops on
+// cross <= 0, so collinear and duplicate corners drop out; shoelace relative to the first hull vertex.  The hull
+// stack is column `tid` of a [9][nthreads] LDS array (`stk`, stride `ld`), by the rule stated above rect_overlap.
+__device__ float rect_hull_area(const float *A, const float *B, P2 *stk, int ld) {
+    const float adx = A[3] / 2, bdx = B[3] / 2, ady = A[4] / 2, bdy = B[4] / 2;
+    const P2 ca{A[0], A[1]}, cb{B[0], B[1]};
+    P2 a0{A[0] - adx, A[1] - ady}, a1{A[0] + adx, A[1] - ady}, a2{A[0] + adx, A[1] + ady}, a3{A[0] - adx, A[1] + ady};
+    P2 b0{B[0] - bdx, B[1] - bdy}, b1{B[0] + bdx, B[1] - bdy}, b2{B[0] + bdx, B[1] + bdy}, b3{B[0] - bdx, B[1] + bdy};
+    const float acs = cosf(A[6]), asn = sinf(A[6]), bcs = cosf(B[6]), bsn = sinf(B[6]);
+    spin(ca, acs, asn, a0); spin(ca, acs, asn, a1); spin(ca, acs, asn, a2); spin(ca, acs, asn, a3);
+    spin(cb, bcs, bsn, b0); spin(cb, bcs, bsn, b1); spin(cb, bcs, bsn, b2); spin(cb, bcs, bsn, b3);
+    P2 p[8] = {a0, a1, a2, a3, b0, b1, b2, b3};     // constant indices only after full unrolling -> registers
+    lex_cswap(p[0], p[2]); lex_cswap(p[1], p[3]); lex_cswap(p[4], p[6]); lex_cswap(p[5], p[7]);
+    lex_cswap(p[0], p[4]); lex_cswap(p[1], p[5]); lex_cswap(p[2], p[6]); lex_cswap(p[3], p[7]);
+    lex_cswap(p[0], p[1]); lex_cswap(p[2], p[3]); lex_cswap(p[4], p[5]); lex_cswap(p[6], p[7]);
+    lex_cswap(p[2], p[4]); lex_cswap(p[3], p[5]);
+    lex_cswap(p[1], p[4]); lex_cswap(p[3], p[6]);
+    lex_cswap(p[1], p[2]); lex_cswap(p[3], p[4]); lex_cswap(p[5], p[6]);
+
+    int k = 0;      // lower chain, left to right: at most 8 entries
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        while (k >= 2 && cr3(stk[(k - 1) * ld], p[i], stk[(k - 2) * ld]) <= 0.f) --k;
+        stk[k * ld] = p[i]; ++k;
+    }
+    const int floor_k = k + 1;      // upper chain, right to left, on top of the lower one; it ends on p[0] again
+#pragma unroll
+    for (int i = 6; i >= 0; --i) {
+        while (k >= floor_k && cr3(stk[(k - 1) * ld], p[i], stk[(k - 2) * ld]) <= 0.f) --k;
+        if (k < 9) { stk[k * ld] = p[i]; ++k; }     // a hull of 8 points has <= 8 vertices + the repeated first; NaN corners never pop
+    }
+    float area = 0.f;
+    const P2 h0 = stk[0];
+    for (int j = 1; j < k - 2; ++j) {
+        const P2 hj = stk[j * ld], hn = stk[(j + 1) * ld];
+        const P2 u{hj.x - h0.x, hj.y - h0.y};
+        const P2 v{hn.x - h0.x, hn.y - h0.y};
+        area += cr2(u, v);
+    }
+    return fabsf(area) / 2.0f;
 }
 
 }  // namespace dz

@@ -166,6 +166,10 @@ struct ScanDims { int d0, d1, d2; };
 // device fill (32-bit pattern) as a plain kernel: no memset nodes, so whole frames capture into a hipGraph
 // as kernels only
 int fill_u32(void *ptr, uint32_t value, size_t nwords, hipStream_t stream);
+// greedy-by-score suppression over an upper-triangle NMS mask (batch, n_cap, col_blocks) of 64-bit words: head_post.hip's
+// k_nms_sweep, for the mask kernels of other files (box_ops.hip)
+int nms_sweep(const unsigned long long *mask, const int *d_n, int batch, int n_cap, int col_blocks, int post_max, int *keep,
+              int *d_num_keep, hipStream_t stream);
 size_t bitmap_scan_workspace_bytes(size_t nwords);
 int bitmap_scan(const uint32_t *bitmap, size_t nwords, uint32_t *prefix, int *d_total, int mode,
                 ScanDims dims, int *coords_out, int cap_out, void *ws, size_t ws_bytes,

@@ -555,6 +555,14 @@ __global__ void k_crop_gather(const int *__restrict__ pairs, const int *__restri
     }
 }
 
+int nms_sweep(const unsigned long long *mask, const int *d_n, int batch, int n_cap, int col_blocks, int post_max, int *keep,
+              int *d_num_keep, hipStream_t stream) {
+    hipLaunchKernelGGL(k_nms_sweep, dim3(batch), dim3(256), (size_t)64 * col_blocks * sizeof(unsigned long long), stream, mask, d_n,
+                       n_cap, col_blocks, post_max, keep, d_num_keep);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
 }  // namespace dz
 
 using namespace dz;

@@ -1166,11 +1166,14 @@ class CenterHead(_Cached):
 
     def decode_batched_nosync(self, head, h, w, index=0):
         """head (B,H*W,12) -> boxes (B,K,7), scores (B,K), labels (B,K) i32 (0-based), keep (B,K) i32, d_nk (B,) i32:
-        top-K decode and rotated NMS of all frames in one launch sequence, counts stay on the device."""
+        top-K decode and NMS (NMS_TYPE: rotated or axis-aligned) of all frames in one launch sequence, counts stay on the device."""
         post = self.model_cfg.POST_PROCESSING
         nms = post.NMS_CONFIG
-        if nms.NMS_TYPE != 'nms_gpu':
-            raise DetZeroHipError('CenterHead: NMS_TYPE %s not supported (nms_gpu only)' % nms.NMS_TYPE)
+        # model_nms_utils.py:17 dispatches on the name; circle_nms is the reference's own `assert False` (centernet_utils.py:173-176)
+        nms_batched = {'nms_gpu': ops.nms_rotated_batched_nosync, 'nms_normal_gpu': ops.nms_normal_batched_nosync}.get(nms.NMS_TYPE)
+        if nms_batched is None:
+            raise DetZeroHipError('CenterHead: NMS_TYPE %s not supported (nms_gpu or nms_normal_gpu; circle_nms is not implemented '
+                                  'by the reference either: its branch is `assert False`)' % nms.NMS_TYPE)
         k = post.MAX_OBJ_PER_SAMPLE
         # candidates come out in descending score order and K <= NMS_PRE_MAXSIZE, so the reference's
         # topk(pre_max) + sort (model_nms_utils.py:15-20) is the identity here
@@ -1179,7 +1182,7 @@ class CenterHead(_Cached):
         boxes, scores, labels, counts = ops.centerhead_decode(
             head, h, w, len(self.class_names_each_head[index]), k, post.SCORE_THRESH, post.POST_CENTER_LIMIT_RANGE,
             self.point_cloud_range, self.voxel_size, self.feature_map_stride, use_iou=self.iou_weight > 0)
-        keep, d_nk = ops.nms_rotated_batched_nosync(boxes, counts, nms.NMS_THRESH, nms.NMS_POST_MAXSIZE)
+        keep, d_nk = nms_batched(boxes, counts, nms.NMS_THRESH, nms.NMS_POST_MAXSIZE)
         return boxes, scores, labels, keep, d_nk
 
     def decode_nosync(self, head, h, w, index=0):

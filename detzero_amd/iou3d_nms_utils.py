@@ -3,6 +3,7 @@ backend (seam 3 of SURVEY.md §8b).  Device tensors in, device tensors out, no D
 import torch
 
 from . import ops
+from .lib import DetZeroHipError
 
 
 def boxes_overlap_bev_gpu(boxes_a, boxes_b):
@@ -17,18 +18,23 @@ def boxes_iou_bev(boxes_a, boxes_b):
 
 
 def boxes_iou3d_gpu(boxes_a, boxes_b):
-    """iou3d_nms_utils.py:74-107: BEV overlap x height overlap / union volume."""
+    """iou3d_nms_utils.py:74-107: BEV overlap x height overlap / union volume, in one kernel (the reference's operation
+    sequence in fp32, bit-identical to its torch composition around boxes_overlap_bev_gpu)."""
     assert boxes_a.shape[1] == boxes_b.shape[1] == 7
-    a_max = (boxes_a[:, 2] + boxes_a[:, 5] / 2).reshape(-1, 1)
-    a_min = (boxes_a[:, 2] - boxes_a[:, 5] / 2).reshape(-1, 1)
-    b_max = (boxes_b[:, 2] + boxes_b[:, 5] / 2).reshape(1, -1)
-    b_min = (boxes_b[:, 2] - boxes_b[:, 5] / 2).reshape(1, -1)
-    overlaps_bev = boxes_overlap_bev_gpu(boxes_a, boxes_b)
-    overlaps_h = torch.clamp(torch.min(a_max, b_max) - torch.max(a_min, b_min), min=0)
-    overlaps_3d = overlaps_bev * overlaps_h
-    vol_a = (boxes_a[:, 3] * boxes_a[:, 4] * boxes_a[:, 5]).reshape(-1, 1)
-    vol_b = (boxes_b[:, 3] * boxes_b[:, 4] * boxes_b[:, 5]).reshape(1, -1)
-    return overlaps_3d / torch.clamp(vol_a + vol_b - overlaps_3d, min=1e-6)
+    return ops.boxes_pairwise_metric(boxes_a.float().contiguous(), boxes_b.float().contiguous(), ops.BOXM_IOU3D)
+
+
+def boxes_giou3d_gpu(boxes_a, boxes_b, exact_height=False):
+    """iou3d_nms_utils.py:110-151 as written: its enclosing height is min(tops) - min(bottoms) (:139), and the tracker's
+    numbers depend on that.  exact_height=True takes max(tops) - min(bottoms), the textbook GIoU."""
+    assert boxes_a.shape[1] == boxes_b.shape[1] == 7
+    return ops.boxes_pairwise_metric(boxes_a.float().contiguous(), boxes_b.float().contiguous(),
+                                     ops.BOXM_GIOU3D_EXACT if exact_height else ops.BOXM_GIOU3D)
+
+
+def boxes_union_bev_gpu(boxes_a, boxes_b):
+    """iou3d_nms_cuda.boxes_union_bev_gpu: (N,7),(M,7) -> (N,M) areas of the convex hull of the two footprints."""
+    return ops.boxes_pairwise_metric(boxes_a[:, :7].float().contiguous(), boxes_b[:, :7].float().contiguous(), ops.BOXM_UNION_BEV)
 
 
 def nms_gpu(boxes, scores, thresh, pre_maxsize=None, **kwargs):
@@ -41,5 +47,23 @@ def nms_gpu(boxes, scores, thresh, pre_maxsize=None, **kwargs):
     if b.shape[0] == 0:
         return order, None
     keep, d_nk = ops.nms_rotated_nosync(b, None, thresh, b.shape[0])
+    nk = int(d_nk.item())
+    return order[keep[:nk].long()].contiguous(), None
+
+
+NMS_MAX_BOXES = 4096        # n_cap limit of dz_nms_rotated / dz_nms_normal
+
+
+def nms_normal_gpu(boxes, scores, thresh, **kwargs):
+    """iou3d_nms_utils.py:173-187: axis-aligned NMS, the heading ignored; no pre_maxsize, as in the reference.
+    Returns (kept indices into `boxes`, None)."""
+    assert boxes.shape[1] == 7
+    if boxes.shape[0] > NMS_MAX_BOXES:
+        raise DetZeroHipError('nms_normal_gpu: %d boxes > %d (the limit of the device NMS)' % (boxes.shape[0], NMS_MAX_BOXES))
+    order = scores.sort(0, descending=True)[1]
+    b = boxes[order].float().contiguous()
+    if b.shape[0] == 0:
+        return order, None
+    keep, d_nk = ops.nms_normal_nosync(b, None, thresh, b.shape[0])
     nk = int(d_nk.item())
     return order[keep[:nk].long()].contiguous(), None

@@ -877,6 +877,47 @@ def boxes_pairwise(a, b, iou):
     return out
 
 
+BOXM_UNION_BEV, BOXM_IOU3D, BOXM_GIOU3D, BOXM_GIOU3D_EXACT = 0, 1, 2, 3        # include/detzero_hip.h
+
+
+def boxes_pairwise_metric(a, b, metric):
+    """a (N,7), b (M,7) f32 -> (N,M) f32 of one of the BOXM_* metrics (one kernel, the final value per pair)."""
+    lib = L.load()
+    L.require_cuda(a, b)
+    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+    rc = lib.dz_boxes_pairwise_metric(L.ptr(a), a.shape[0], L.ptr(b), b.shape[0], int(metric), L.ptr(out), L.stream())
+    L.check(rc, 'dz_boxes_pairwise_metric')
+    return out
+
+
+def nms_normal_nosync(boxes_sorted, d_n, thresh, post_max):
+    """Axis-aligned NMS (heading ignored): boxes_sorted (n_cap,7) descending score; returns keep (n_cap,) i32, d_num_keep (1,) i32."""
+    lib = L.load()
+    L.require_cuda(boxes_sorted)
+    n_cap = boxes_sorted.shape[0]
+    keep = torch.zeros((max(n_cap, 1),), dtype=torch.int32, device=boxes_sorted.device)
+    d_nk = torch.zeros((1,), dtype=torch.int32, device=boxes_sorted.device)
+    ws = _ws(lib.dz_nms_workspace_bytes(n_cap))
+    rc = lib.dz_nms_normal(L.ptr(boxes_sorted), L.ptr(d_n), n_cap, float(thresh), int(post_max), L.ptr(keep),
+                           L.ptr(d_nk), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, 'dz_nms_normal')
+    return keep, d_nk
+
+
+def nms_normal_batched_nosync(boxes_sorted, d_n, thresh, post_max):
+    """boxes_sorted (B,n_cap,7) descending score per item, d_n (B,) -> keep (B,n_cap) i32, d_num_keep (B,) i32."""
+    lib = L.load()
+    L.require_cuda(boxes_sorted, d_n)
+    b, n_cap = boxes_sorted.shape[0], boxes_sorted.shape[1]
+    keep = torch.zeros((b, max(n_cap, 1)), dtype=torch.int32, device=boxes_sorted.device)
+    d_nk = torch.zeros((b,), dtype=torch.int32, device=boxes_sorted.device)
+    ws = _ws(b * lib.dz_nms_workspace_bytes(n_cap))
+    rc = lib.dz_nms_normal_batched(L.ptr(boxes_sorted), L.ptr(d_n), b, n_cap, float(thresh), int(post_max), L.ptr(keep),
+                                   L.ptr(d_nk), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, 'dz_nms_normal_batched')
+    return keep, d_nk
+
+
 def points_in_boxes_v2(points, boxes):
     """points (B,M,3), boxes (B,T,7) -> (B,T,M) i32."""
     lib = L.load()

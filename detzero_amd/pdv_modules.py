@@ -447,11 +447,16 @@ class PDVHead(_Cached):
         roi_labels = box_preds_all.new_zeros((batch_size, nms_config.NMS_POST_MAXSIZE), dtype=torch.long)
         if nms_config.MULTI_CLASSES_NMS:
             raise NotImplementedError
+        # the name selects the function as model_nms_utils.class_agnostic_nms:17 does; only nms_gpu takes pre_maxsize
+        if nms_config.NMS_TYPE not in ('nms_gpu', 'nms_normal_gpu'):
+            raise DetZeroHipError('PDVHead: NMS_TYPE %s not supported (nms_gpu or nms_normal_gpu)' % nms_config.NMS_TYPE)
+        nms_fn = getattr(iou3d_nms_utils, nms_config.NMS_TYPE)
+        nms_kwargs = {'pre_maxsize': nms_config.NMS_PRE_MAXSIZE} if nms_config.NMS_TYPE == 'nms_gpu' else {}
         for index in range(batch_size):
             mask = (batch_dict['batch_index'] == index) if batch_dict.get('batch_index', None) is not None else index
             box_preds, cls_preds = box_preds_all[mask], cls_preds_all[mask]
             cur_scores, cur_labels = torch.max(cls_preds, dim=1)
-            selected, _ = iou3d_nms_utils.nms_gpu(box_preds[:, 0:7], cur_scores, nms_config.NMS_THRESH, pre_maxsize=nms_config.NMS_PRE_MAXSIZE)
+            selected, _ = nms_fn(box_preds[:, 0:7], cur_scores, nms_config.NMS_THRESH, **nms_kwargs)
             selected = selected[:nms_config.NMS_POST_MAXSIZE]
             rois[index, :len(selected)] = box_preds[selected]
             roi_scores[index, :len(selected)] = cur_scores[selected]

@@ -1,0 +1,4 @@
+"""detzero_utils.ops.iou3d_nms.iou3d_nms_utils - the device functions of the reference's module of that name
+(utils/detzero_utils/ops/iou3d_nms/iou3d_nms_utils.py:57-187), re-exported from detzero_amd.iou3d_nms_utils."""
+from detzero_amd.iou3d_nms_utils import (boxes_giou3d_gpu, boxes_iou3d_gpu, boxes_iou_bev, boxes_overlap_bev_gpu,  # noqa: F401
+                                         boxes_union_bev_gpu, nms_gpu, nms_normal_gpu)

@@ -451,6 +451,29 @@ int dz_pack_detections(const float *boxes, const float *scores, const int *label
 int dz_boxes_overlap_bev(const float *a, int na, const float *b, int nb, float *out, void *stream);
 int dz_boxes_iou_bev(const float *a, int na, const float *b, int nb, float *out, void *stream);
 
+/* Pair matrices of the tracker's association metrics (tracking/.../data_association/distance.py), one kernel each, the final
+ * value per (i, j): a (na,7), b (nb,7) -> out (na,nb) f32.
+ *   DZ_BOXM_UNION_BEV     iou3d_nms_cuda.boxes_union_bev_gpu: area of the convex hull of the two footprints' eight corners (the
+ *                         quantity iou3d_nms_kernel.cu:235-326 is meant to compute; its walk reads an unwritten hull[0] and is
+ *                         not transcribed)
+ *   DZ_BOXM_IOU3D         iou3d_nms_utils.boxes_iou3d_gpu (:74-107), bit-identical to that composition around dz_boxes_overlap_bev
+ *   DZ_BOXM_GIOU3D        iou3d_nms_utils.boxes_giou3d_gpu (:110-151) as written: enclosing height = min(tops) - min(bottoms)
+ *   DZ_BOXM_GIOU3D_EXACT  the same with enclosing height = max(tops) - min(bottoms), the textbook GIoU
+ * Any other `metric`: DZ_ERR_UNSUPPORTED, the value in dz_last_error(). */
+#define DZ_BOXM_UNION_BEV 0
+#define DZ_BOXM_IOU3D 1
+#define DZ_BOXM_GIOU3D 2
+#define DZ_BOXM_GIOU3D_EXACT 3
+int dz_boxes_pairwise_metric(const float *a, int na, const float *b, int nb, int metric, float *out, void *stream);
+
+/* iou3d_nms_cuda.nms_normal_gpu (iou3d_nms.cpp + nms_normal_kernel / iou_normal iou3d_nms_kernel.cu:433-491): axis-aligned BEV
+ * IoU, the heading ignored, greedy by score.  Arguments, limits (n_cap <= 4096) and workspace (dz_nms_workspace_bytes) of
+ * dz_nms_rotated / dz_nms_rotated_batched. */
+int dz_nms_normal(const float *boxes, const int *d_n, int n_cap, float thresh, int post_max, int *keep, int *d_num_keep,
+                  void *ws, size_t ws_bytes, void *stream);
+int dz_nms_normal_batched(const float *boxes, const int *d_n, int batch, int n_cap, float thresh, int post_max, int *keep,
+                          int *d_num_keep, void *ws, size_t ws_bytes, void *stream);
+
 /* gather rows: out[i] = src[idx[i]] for i < *d_n (used to apply the NMS keep list on device) */
 int dz_gather_rows(const float *src, const int *idx, const int *d_n, int n_cap, int c, float *out,
                    void *stream);

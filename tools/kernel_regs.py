@@ -31,9 +31,10 @@ def main():
             cur[k] = v
     for r in rows:
         if flt in r['name']:
-            print('%-4s v %-4s a %-3s occ %-2s spill %-3s lds  %s' % (
+            print('%-4s v %-4s a %-3s occ %-2s spill %-3s scratch %-6s lds  %s' % (
                 r.get('VGPRs'), r.get('AGPRs'), r.get('Occupancy [waves/SIMD]'), r.get('VGPRs Spill'),
-                r.get('LDS Size [bytes/block]'), re.sub(r'^void dz::|\(dz::\w+\)$|dz::', '', r['name'])))
+                r.get('ScratchSize [bytes/lane]'), r.get('LDS Size [bytes/block]'),
+                re.sub(r'^void dz::|\(dz::\w+\)$|dz::', '', r['name'])))
 
 
 if __name__ == '__main__':
