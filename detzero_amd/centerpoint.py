@@ -354,6 +354,10 @@ class FramePipeline:
         self.dense_group = int(os.environ.get('DZ_TUNE_DENSE_GROUP', '16'))     # frames per pass of the dense layers (2 GiB image window)
         self.last_overflow = None
         self._overflow_acc = None
+        # True: the head's regression branches (center, center_z, dim, rot) are evaluated at the top-K cells only (post_stage), the
+        # dense stage runs the iou / hm branches alone; False: the full-map route (all six branches at every cell)
+        self.head_at_candidates = True
+        self._partial_head = None     # (address, shape, shared map) of the partial head map the last dense_stage returned
 
     def _voxelize(self, frames, cid=0):
         """-> (features (M,C), coords (M,4) [b,z,y,x], d_n or None).  Rows of a frame beyond its device-side
@@ -523,6 +527,10 @@ class FramePipeline:
     @torch.no_grad()
     def dense_stage(self, res, nb):
         """HeightCompression + BaseBEVBackbone + the CenterHead convolutions -> (head map (B,H*W,12), H, W).
+        With `head_at_candidates` (and a head csrc/head_cand.hip serves) only the branches the selection reads at every cell run here:
+        columns 8:12 of the map (9:12 when IOU_WEIGHT is 0) are written, columns 0:8 are NOT - post_stage fills them at the selected
+        cells from the shared map.  The pipeline keeps that hand-over itself (`_partial_head`: the map's address and shape, and the shared
+        map, an image of this pipeline's workspace valid until the next dense_stage): post_stage must get THIS map, not a copy or a slice.
         More than `dense_group` frames go through the dense layers in groups: the kernels address an image through 32-bit buffer
         offsets, and the 512-channel concatenation of the Waymo config passes 2 GiB at ~20 frames.  The BEV image (1.2 GB at 32
         frames) is built once; a group is a contiguous slice of it."""
@@ -540,14 +548,29 @@ class FramePipeline:
         # upsampled maps, channel-last fp32-sized words, zero border included) allows inside the 2 GiB buffer window
         per_frame = bev.shape[1] * bev.shape[2] * max(int(m.backbone2d.num_bev_features), 2 * int(x.shape[1])) * 4
         group = max(1, min(self.dense_group if self.dense_group > 0 else nb, (2 ** 31 - 1) // per_frame))
+        at_cand = self.head_at_candidates and self.head.at_candidates_ok()
+        self._partial_head = None
+        if at_cand:
+            self.head.candidate_params()             # (packed once, here: never inside post_stage's first captured call)
         if nb <= group:
             with cp_modules.workspace(self._ws):
                 concat = run2d(0, nb)
-                return self.head.run_convs(concat, nb)
-        st = {'out': None, 'h': 0, 'w': 0}
+                if not at_cand:
+                    return self.head.run_convs(concat, nb)
+                shared = self.head.run_shared(concat, nb)
+                hd, hh, hw_ = self.head.run_score_head(shared, nb)
+                self._partial_head = (hd.data_ptr(), tuple(hd.shape), shared)
+                return hd, hh, hw_
+        st = {'out': None, 'h': 0, 'w': 0, 'shared': None}
 
         def head_of_group(concat, g0, ng):
-            hd, st['h'], st['w'] = self.head.run_convs(concat, ng)
+            if at_cand:
+                # the shared maps outlive their group: every group writes its slice of one all-frames image
+                if st['shared'] is None:
+                    st['shared'] = cp_modules.bordered_zeros('head.shared_all', (nb,) + tuple(concat.shape[1:3]) + (self.head.plan()['c'],), concat.device)
+                hd, st['h'], st['w'] = self.head.run_score_head(self.head.run_shared(concat, ng, out=st['shared'][g0:g0 + ng]), ng)
+            else:
+                hd, st['h'], st['w'] = self.head.run_convs(concat, ng)
             if st['out'] is None:
                 st['out'] = hd.new_empty((nb,) + tuple(hd.shape[1:]))
             st['out'][g0:g0 + ng].copy_(hd)          # (the activation images, the head map among them, are reused by the next group)
@@ -560,12 +583,23 @@ class FramePipeline:
                 for g0 in range(0, nb, group):
                     ng = min(group, nb - g0)
                     head_of_group(run2d(g0, ng), g0, ng)
+        if at_cand:
+            self._partial_head = (st['out'].data_ptr(), tuple(st['out'].shape), st['shared'])
         return st['out'], st['h'], st['w']
 
     @torch.no_grad()
     def post_stage(self, head, h, w):
-        """Top-K decode, rotated NMS, packing -> (boxes9 (B,K,9), counts (B,))."""
-        boxes, scores, labels, keep, d_nk = self.head.decode_batched_nosync(head, h, w)
+        """Top-K decode, rotated NMS, packing -> (boxes9 (B,K,9), counts (B,)).  The map of a dense_stage with `head_at_candidates`
+        goes select -> regression at the candidates -> decode of the selected; a full map as before.  While this pipeline's last
+        dense_stage left a partial map, any other tensor is refused: a copy or slice of that map has no columns 0:8 to decode."""
+        shared = None
+        if self._partial_head is not None:
+            ptr, shape, shared = self._partial_head
+            if head.data_ptr() != ptr or tuple(head.shape) != shape:
+                raise DetZeroHipError('FramePipeline.post_stage: the last dense_stage wrote only the selection columns of its head map '
+                                      '(head_at_candidates) and this is not that tensor - pass dense_stage\'s result as it is, or set '
+                                      'head_at_candidates = False for full maps')
+        boxes, scores, labels, keep, d_nk = self.head.decode_batched_nosync(head, h, w, shared=shared)
         return ops.pack_detections(boxes, scores, labels, keep, d_nk, self.post_max), d_nk
 
     def infer(self, prep):
@@ -693,6 +727,7 @@ class FramePipeline:
         outs = []
         prev = None
         for (part, _, _), sub, st in zip(parts, self._subs, self._way_streams):
+            sub.head_at_candidates = self.head_at_candidates
             sub.level_caps, sub.dense_group = self.level_caps, self.dense_group       # (every sub-pass keeps its OWN sticky overflow counter:
             sub.fork_ok = nested_ok                                                    # two streams OR-ing into one word would race)
             st.wait_stream(main)

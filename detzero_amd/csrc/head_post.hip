@@ -317,6 +317,8 @@ struct DecodeArgs {
     const uint32_t *state;
     const unsigned long long *gcand;
     const uint32_t *ties;
+    unsigned long long *sel;      // (B, TOPK_MAXK) sorted candidates: written by k_topk_select, read by k_decode_selected
+    int *nsel;                    // (B) min(K, ncls * HW)
     float *boxes, *scores;
     int *labels, *counts;
     int hw, w, ncls, k, stride;
@@ -328,11 +330,14 @@ constexpr int TOPK_THREADS = 1024;
 constexpr int TOPK_MAXK = 1024;
 
 // one workgroup per batch item: gathers the <= K candidates found by the radix select (ties at the
-// threshold value resolved to the smallest flat indices), bitonic sort (score desc, index asc), decode,
-// masks, ordered compaction.
-__global__ __launch_bounds__(TOPK_THREADS) void k_topk_decode(DecodeArgs a) {
-    __shared__ uint32_t scan_lds[TOPK_THREADS / 64];
-    __shared__ unsigned long long cand[TOPK_MAXK];
+// threshold value resolved to the smallest flat indices), bitonic sort (score desc, index asc); the sorted
+// list goes to global memory (a.sel, a.nsel) - what the regression at the candidates and k_decode_selected read.
+// NT threads sort NT slots, NT = the power of two >= K the launcher picks (512 for the configs' K = 500: 45 compare-exchange steps
+// between 8 waves instead of 55 between 16); slots >= NT of the list are not written and never read (K <= NT).
+template <int NT>
+__global__ __launch_bounds__(NT) void k_topk_select(DecodeArgs a) {
+    __shared__ uint32_t scan_lds[NT / 64];
+    __shared__ unsigned long long cand[NT];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = a.ncls * a.hw;
     const uint32_t *keys = a.keys + (size_t)b * n;
@@ -343,34 +348,34 @@ __global__ __launch_bounds__(TOPK_THREADS) void k_topk_decode(DecodeArgs a) {
     const uint32_t n_gt = st[ST_NGT];              // == K - need_eq
     const uint32_t n_eq = st[ST_NEQ];              // keys == T in the whole map
 
-    cand[tid] = (tid < (int)n_gt && tid < TOPK_MAXK) ? a.gcand[(size_t)b * TOPK_MAXK + tid] : 0ull;
+    cand[tid] = (tid < (int)n_gt && tid < NT) ? a.gcand[(size_t)b * TOPK_MAXK + tid] : 0ull;
     __syncthreads();
     if (n_eq == need_eq && n_eq <= (uint32_t)TIE_CAP) {
         // common case: every key equal to the threshold is selected, no ordering question
-        for (uint32_t j = tid; j < need_eq; j += TOPK_THREADS) {
+        for (uint32_t j = tid; j < need_eq; j += NT) {
             const uint32_t pos = n_gt + j;
-            if (pos < TOPK_MAXK)
+            if (pos < NT)
                 cand[pos] = ((unsigned long long)T << 32) | (uint32_t)(0xFFFFFFFFu - a.ties[(size_t)b * TIE_CAP + j]);
         }
     } else {
         // more ties than needed (flat / saturated score maps): take the first need_eq in index order
         uint32_t taken = 0u;
-        for (int base = 0; base < n && taken < need_eq; base += TOPK_THREADS) {
+        for (int base = 0; base < n && taken < need_eq; base += NT) {
             const int i = base + tid;
             const uint32_t flag = (i < n && keys[i] == T) ? 1u : 0u;
             uint32_t tot;
-            const uint32_t ex = block_excl_scan<TOPK_THREADS / 64>(flag, scan_lds, tot);
+            const uint32_t ex = block_excl_scan<NT / 64>(flag, scan_lds, tot);
             if (flag && taken + ex < need_eq) {
                 const uint32_t pos = n_gt + taken + ex;
-                if (pos < TOPK_MAXK) cand[pos] = ((unsigned long long)T << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
+                if (pos < NT) cand[pos] = ((unsigned long long)T << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
             }
             taken += tot;
         }
     }
     __syncthreads();
 
-    // ---- bitonic sort of TOPK_MAXK 64-bit keys, descending (unused slots are 0 -> sink to the end)
-    for (int size = 2; size <= TOPK_MAXK; size <<= 1) {
+    // ---- bitonic sort of NT 64-bit keys, descending (unused slots are 0 -> sink to the end)
+    for (int size = 2; size <= NT; size <<= 1) {
         for (int strd = size >> 1; strd > 0; strd >>= 1) {
             const int i = tid;
             const int j = i ^ strd;
@@ -383,13 +388,22 @@ __global__ __launch_bounds__(TOPK_THREADS) void k_topk_decode(DecodeArgs a) {
         }
     }
 
-    // ---- decode + masks + ordered compaction
+    a.sel[(size_t)b * TOPK_MAXK + tid] = cand[tid];
+    if (tid == 0) a.nsel[b] = K;
+}
+
+// one workgroup per batch item: decode of the selected candidates (head rows of their cells), masks, ordered compaction.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_decode_selected(DecodeArgs a) {
+    __shared__ uint32_t scan_lds[NT / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int K = min(a.k, a.ncls * a.hw);
     float box[7];
     float score = 0.f;
     int label = 0;
     uint32_t pass = 0u;
     if (tid < K) {
-        const unsigned long long e = cand[tid];
+        const unsigned long long e = a.sel[(size_t)b * TOPK_MAXK + tid];
         const uint32_t kv = (uint32_t)(e >> 32);
         const uint32_t flat = 0xFFFFFFFFu - (uint32_t)(e & 0xFFFFFFFFull);
         score = __uint_as_float(kv);
@@ -409,7 +423,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void k_topk_decode(DecodeArgs a) {
         pass = ok ? 1u : 0u;
     }
     uint32_t tot;
-    const uint32_t pos = block_excl_scan<TOPK_THREADS / 64>(pass, scan_lds, tot);
+    const uint32_t pos = block_excl_scan<NT / 64>(pass, scan_lds, tot);
     if (pass) {
         float *bo = a.boxes + ((size_t)b * a.k + pos) * 7;
         for (int q = 0; q < 7; ++q) bo[q] = box[q];
@@ -714,43 +728,65 @@ int dz_pack_detections(const float *boxes, const float *scores, const int *label
     return DZ_OK;
 }
 
-static size_t decode_layout(int batch, int hw, int ncls, size_t *o_keys, size_t *o_state, size_t *o_cand, size_t *o_ties) {
+static size_t decode_layout(int batch, int hw, int ncls, size_t *o_keys, size_t *o_state, size_t *o_cand, size_t *o_ties,
+                            size_t *o_sel, size_t *o_nsel) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
     *o_keys = take((size_t)batch * hw * ncls * sizeof(uint32_t));
     *o_state = take((size_t)batch * TOPK_STATE_WORDS * sizeof(uint32_t));
     *o_cand = take((size_t)batch * TOPK_MAXK * sizeof(unsigned long long));
     *o_ties = take((size_t)batch * TIE_CAP * sizeof(uint32_t));
+    *o_sel = take((size_t)batch * TOPK_MAXK * sizeof(unsigned long long));
+    *o_nsel = take((size_t)batch * sizeof(int));
     return off;
 }
 
 size_t dz_centerhead_decode_workspace_bytes(int batch, int hw, int ncls, int k) {
     (void)k;
-    size_t a, b, c, d;
-    return decode_layout(batch, hw, ncls, &a, &b, &c, &d);
+    size_t a, b, c, d, e, f;
+    return decode_layout(batch, hw, ncls, &a, &b, &c, &d, &e, &f);
 }
 
-int dz_centerhead_decode(const float *head, int batch, int h, int w, int ncls, int k, float score_thresh,
-                         const float *h_limit6, const float *h_range6, const float *h_vsize3, int stride, int use_iou,
-                         float *boxes, float *scores, int *labels, int *d_counts, void *ws, size_t ws_bytes,
-                         void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    DZ_CHECK_ARG(head && boxes && scores && labels && d_counts && ws, "dz_centerhead_decode: null pointer");
-    DZ_CHECK_ARG(batch >= 1 && h >= 1 && w >= 1 && ncls >= 1 && ncls <= 3, "dz_centerhead_decode: bad sizes (ncls<=3)");
-    DZ_CHECK_ARG(k >= 1 && k <= TOPK_MAXK, "dz_centerhead_decode: K %d not in [1,%d]", k, TOPK_MAXK);
+size_t dz_centerhead_candidates_offset(int batch, int hw, int ncls, int k, int which) {
+    (void)k;
+    static_assert(TOPK_MAXK == DZ_CENTERHEAD_CAND_STRIDE, "the header states the list stride");
+    size_t a, b, c, d, e, f;
+    decode_layout(batch, hw, ncls, &a, &b, &c, &d, &e, &f);
+    return which ? f : e;
+}
+
+static int decode_args(DecodeArgs &a, const char *who, const float *head, int batch, int h, int w, int ncls, int k, void *ws, size_t ws_bytes) {
+    if (!(head && ws)) { set_error("%s: null pointer", who); return DZ_ERR_INVALID; }
+    if (!(batch >= 1 && h >= 1 && w >= 1 && ncls >= 1 && ncls <= 3)) { set_error("%s: bad sizes (ncls<=3)", who); return DZ_ERR_INVALID; }
+    if (!(k >= 1 && k <= TOPK_MAXK)) { set_error("%s: K %d not in [1,%d]", who, k, TOPK_MAXK); return DZ_ERR_INVALID; }
     const int hw = h * w;
     if (ws_bytes < dz_centerhead_decode_workspace_bytes(batch, hw, ncls, k)) {
-        set_error("dz_centerhead_decode: workspace too small");
+        set_error("%s: workspace too small", who);
         return DZ_ERR_WORKSPACE;
     }
-    size_t o_keys, o_state, o_cand, o_ties;
-    decode_layout(batch, hw, ncls, &o_keys, &o_state, &o_cand, &o_ties);
-    uint32_t *keys = (uint32_t *)((char *)ws + o_keys);
-    uint32_t *state = (uint32_t *)((char *)ws + o_state);
-    unsigned long long *gcand = (unsigned long long *)((char *)ws + o_cand);
-    uint32_t *ties = (uint32_t *)((char *)ws + o_ties);
-    const int n = ncls * hw;
-    int rc = fill_u32(state, 0u, (size_t)batch * TOPK_STATE_WORDS, stream);
+    size_t o_keys, o_state, o_cand, o_ties, o_sel, o_nsel;
+    decode_layout(batch, hw, ncls, &o_keys, &o_state, &o_cand, &o_ties, &o_sel, &o_nsel);
+    a = DecodeArgs{};
+    a.head = head;
+    a.keys = (uint32_t *)((char *)ws + o_keys);
+    a.state = (uint32_t *)((char *)ws + o_state);
+    a.gcand = (unsigned long long *)((char *)ws + o_cand);
+    a.ties = (uint32_t *)((char *)ws + o_ties);
+    a.sel = (unsigned long long *)((char *)ws + o_sel);
+    a.nsel = (int *)((char *)ws + o_nsel);
+    a.hw = hw; a.w = w; a.ncls = ncls; a.k = k;
+    return DZ_OK;
+}
+
+int dz_centerhead_select(const float *head, int batch, int h, int w, int ncls, int k, int use_iou, void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DecodeArgs a;
+    int rc = decode_args(a, "dz_centerhead_select", head, batch, h, w, ncls, k, ws, ws_bytes);
+    if (rc) return rc;
+    const int hw = h * w, n = ncls * hw;
+    uint32_t *keys = const_cast<uint32_t *>(a.keys), *state = const_cast<uint32_t *>(a.state), *ties = const_cast<uint32_t *>(a.ties);
+    unsigned long long *gcand = const_cast<unsigned long long *>(a.gcand);
+    rc = fill_u32(state, 0u, (size_t)batch * TOPK_STATE_WORDS, stream);
     if (rc) return rc;
     const dim3 gpix(stream_grid(hw, 256) > 512 ? 512 : stream_grid(hw, 256), batch);
     const dim3 gkey(stream_grid(n, 256) > 512 ? 512 : stream_grid(n, 256), batch);
@@ -761,14 +797,41 @@ int dz_centerhead_decode(const float *head, int batch, int h, int w, int ncls, i
     hipLaunchKernelGGL(k_radix_hist<2>, gkey, dim3(256), 0, stream, keys, n, state);
     hipLaunchKernelGGL(k_radix_pick, dim3(batch), dim3(256), 0, stream, state, 2, k, n);
     hipLaunchKernelGGL(k_topk_collect, gkey, dim3(256), 0, stream, keys, n, state, gcand, ties, TOPK_MAXK);
-    DecodeArgs a;
-    a.head = head; a.keys = keys; a.state = state; a.gcand = gcand; a.ties = ties; a.boxes = boxes; a.scores = scores; a.labels = labels; a.counts = d_counts;
-    a.hw = hw; a.w = w; a.ncls = ncls; a.k = k; a.stride = stride; a.score_thresh = score_thresh;
-    for (int i = 0; i < 6; ++i) a.lim[i] = h_limit6[i];
-    for (int i = 0; i < 3; ++i) { a.lo[i] = h_range6[i]; a.vs[i] = h_vsize3[i]; }
-    hipLaunchKernelGGL(k_topk_decode, dim3(batch), dim3(TOPK_THREADS), 0, stream, a);
+    if (k <= 512) hipLaunchKernelGGL(k_topk_select<512>, dim3(batch), dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL(k_topk_select<TOPK_THREADS>, dim3(batch), dim3(TOPK_THREADS), 0, stream, a);
     DZ_LAUNCH_CHECK();
     return DZ_OK;
+}
+
+int dz_centerhead_decode_selected(const float *head, int batch, int h, int w, int ncls, int k, float score_thresh,
+                                  const float *h_limit6, const float *h_range6, const float *h_vsize3, int stride,
+                                  float *boxes, float *scores, int *labels, int *d_counts, void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(boxes && scores && labels && d_counts && h_limit6 && h_range6 && h_vsize3, "dz_centerhead_decode_selected: null pointer");
+    DecodeArgs a;
+    const int rc = decode_args(a, "dz_centerhead_decode_selected", head, batch, h, w, ncls, k, ws, ws_bytes);
+    if (rc) return rc;
+    a.boxes = boxes; a.scores = scores; a.labels = labels; a.counts = d_counts;
+    a.stride = stride; a.score_thresh = score_thresh;
+    for (int i = 0; i < 6; ++i) a.lim[i] = h_limit6[i];
+    for (int i = 0; i < 3; ++i) { a.lo[i] = h_range6[i]; a.vs[i] = h_vsize3[i]; }
+    if (k <= 512) hipLaunchKernelGGL(k_decode_selected<512>, dim3(batch), dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL(k_decode_selected<TOPK_THREADS>, dim3(batch), dim3(TOPK_THREADS), 0, stream, a);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
+int dz_centerhead_decode(const float *head, int batch, int h, int w, int ncls, int k, float score_thresh,
+                         const float *h_limit6, const float *h_range6, const float *h_vsize3, int stride, int use_iou,
+                         float *boxes, float *scores, int *labels, int *d_counts, void *ws, size_t ws_bytes,
+                         void *stream_) {
+    DZ_CHECK_ARG(head && boxes && scores && labels && d_counts && ws, "dz_centerhead_decode: null pointer");
+    DZ_CHECK_ARG(batch >= 1 && h >= 1 && w >= 1 && ncls >= 1 && ncls <= 3, "dz_centerhead_decode: bad sizes (ncls<=3)");
+    DZ_CHECK_ARG(k >= 1 && k <= TOPK_MAXK, "dz_centerhead_decode: K %d not in [1,%d]", k, TOPK_MAXK);
+    const int rc = dz_centerhead_select(head, batch, h, w, ncls, k, use_iou, ws, ws_bytes, stream_);
+    if (rc) return rc;
+    return dz_centerhead_decode_selected(head, batch, h, w, ncls, k, score_thresh, h_limit6, h_range6, h_vsize3, stride, boxes, scores,
+                                         labels, d_counts, ws, ws_bytes, stream_);
 }
 
 int dz_points_in_boxes_count(const float *boxes, const float *pts, int t, int m, int *counts, void *stream_) {

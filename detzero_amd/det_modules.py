@@ -1114,6 +1114,15 @@ class CenterHead(_Cached):
                           # the split engine works on 32-channel fragments: biases padded per group to 32
                           'shift32': torch.cat([_pad_vec(b, 32) for b in b2]).contiguous(),
                           'g_cout': g_cout, 'g_ooff': [self.COLS[n][0] for n in order]}})
+            # the branches the top-K selection reads at every cell (iou - unless IOU_WEIGHT is 0 and the score ignores it - and hm) as
+            # layers of their own: channel / group slices of the two above (FramePipeline's route, run_score_head)
+            g0 = 4 if self.iou_weight > 0 else 5
+            hid, fin = heads[-1]['hidden'], heads[-1]['final']
+            heads[-1]['first_score_group'] = g0
+            heads[-1]['score_hidden'] = {'w': hid['w'][:, :, g0 * c:].contiguous(), 'scale': hid['scale'][g0 * c:].contiguous(),
+                                         'shift': hid['shift'][g0 * c:].contiguous()}
+            heads[-1]['score_final'] = {'w': fin['w'][g0:].contiguous(), 'shift': fin['shift'][g0 * 16:].contiguous(),
+                                        'shift32': fin['shift32'][g0 * 32:].contiguous(), 'g_cout': g_cout[g0:], 'g_ooff': fin['g_ooff'][g0:]}
         self._plan = {
             'shared': {'w': _conv_weight_taps(sc.weight), 'scale': s_scale, 'shift': s_shift, 'cin': sc.in_channels},
             'heads': heads, 'hidden': heads[0]['hidden'], 'final': heads[0]['final'],
@@ -1121,12 +1130,13 @@ class CenterHead(_Cached):
         }
         return self._plan
 
-    def run_shared(self, concat, batch):
-        """concat (B,H+2,W+2,Cin) zero-bordered -> the shared 3x3 conv's map (B,H+2,W+2,C), zero-bordered (center_head.py:443)."""
+    def run_shared(self, concat, batch, out=None):
+        """concat (B,H+2,W+2,Cin) zero-bordered -> the shared 3x3 conv's map (B,H+2,W+2,C), zero-bordered (center_head.py:443).
+        out: a zero-bordered (B,H+2,W+2,C) image to write instead of the workspace's (only its interior is written)."""
         p = self.plan()
         hp, wp = concat.shape[1], concat.shape[2]
         c = p['c']
-        shared = bordered_zeros('head.shared', (batch, hp, wp, c), concat.device)
+        shared = out if out is not None else bordered_zeros('head.shared', (batch, hp, wp, c), concat.device)
         e = self._e('spatial_features_2d')                    # (the head's hidden maps share the exponent of its input)
         conv_layer(concat, (hp, wp), *self._p(p['shared'], e, e), True, shared, (hp, wp),
                    cin=p['shared']['cin'], in_cstride=concat.shape[3], out_cstride=c, out_d=(1, 1), ho=hp - 2, wo=wp - 2, batch=batch,
@@ -1156,17 +1166,64 @@ class CenterHead(_Cached):
 
     def run_convs(self, concat, batch):
         """concat (B,H+2,W+2,Cin) zero-bordered -> head map (B, H*W, 12) channel-last of the FIRST head (the single-head layout of
-        every DetZero config; FramePipeline's route)."""
+        every DetZero config; FramePipeline's full-map route)."""
         return self.run_head(self.run_shared(concat, batch), batch, 0)
+
+    def at_candidates_ok(self):
+        """Whether the regression branches can be evaluated at the top-K cells only (csrc/head_cand.hip: 64 shared channels); otherwise FramePipeline keeps the full-map route."""
+        return ops.head_at_candidates_supported(self.math, self.model_cfg.SHARED_CONV_CHANNEL)
+
+    def run_score_head(self, shared, batch, index=0):
+        """The branches the top-K selection reads at every cell - iou (when IOU_WEIGHT > 0) and hm - on the shared map -> head map
+        (B, H*W, 12) with columns 8:12 (9:12) written as run_head writes them, bit for bit; columns 0:8 are NOT written here:
+        regress_at_candidates fills them at the selected cells."""
+        p = self.plan()
+        hp_ = p['heads'][index]
+        g0 = hp_['first_score_group']
+        ng = 6 - g0
+        dev = shared.device
+        hp, wp = shared.shape[1], shared.shape[2]
+        h, w = hp - 2, wp - 2
+        c = p['c']
+        mm = self.math
+        hidden = bordered_zeros('head.hidden_score', (batch, hp, wp, ng * c), dev)
+        e = self._e('spatial_features_2d')
+        conv_layer(shared, (hp, wp), *self._p(hp_['score_hidden'], e, e), True, hidden, (hp, wp),
+                   cin=c, in_cstride=c, out_cstride=ng * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm)
+        head = torch.empty((batch, h * w, 12), dtype=torch.float32, device=dev)
+        fin = hp_['score_final']
+        conv_layer(hidden, (hp, wp), *self._p(fin, e, 0, scale=None, shift=fin['shift32' if mm else 'shift']), False, head, (h, w),
+                   cin=c, in_cstride=ng * c, out_cstride=12, out_d=(0, 0), groups=ng, cout_pad=32 if mm else 16,
+                   g_cout=fin['g_cout'], g_ooff=fin['g_ooff'], ho=h, wo=w, batch=batch, math=mm, out_f32=True)
+        return head, h, w
+
+    def candidate_params(self, index=0):
+        """Packed parameters of the two layers as regress_at_candidates hands them to the kernel (built and cached by `_p` exactly as
+        run_head's: call once outside a graph capture).  These are the packs of ALL six branches (384 hidden channels, 6 groups), of
+        which the kernel reads channels 0:256 and groups 0:4: deliberate - they are run_head's own cache entries, so a model that
+        also runs the module path packs nothing twice, and the surplus beside score_hidden / score_final is under 1 MB."""
+        hp_ = self.plan()['heads'][index]
+        e = self._e('spatial_features_2d')
+        return self._p(hp_['hidden'], e, e) + self._p(hp_['final'], e, 0, scale=None, shift=hp_['final']['shift32' if self.math else 'shift'])
+
+    def regress_at_candidates(self, shared, head, cand, ncand, k, index=0):
+        """Columns 0:8 (center, center_z, dim, rot) of the head map at the candidate cells, from the shared map: run_head's values at
+        those cells bit for bit (same accumulation order and roundings)."""
+        hp_ = self.plan()['heads'][index]
+        w1, s1, b1, w2, s2, b2 = self.candidate_params(index)
+        return ops.head_at_candidates(shared, cand, ncand, k, w1, s1, b1, w2, s2, b2, hp_['final']['g_cout'][:4], hp_['final']['g_ooff'][:4],
+                                      head, self.math)
 
     def assign_targets(self, gt_boxes, feature_map_size=None, **kwargs):
         """center_head.py:202-260 (host-side, like the reference's)."""
         from .target_assign import assign_targets
         return assign_targets(self, gt_boxes, feature_map_size)
 
-    def decode_batched_nosync(self, head, h, w, index=0):
+    def decode_batched_nosync(self, head, h, w, index=0, shared=None):
         """head (B,H*W,12) -> boxes (B,K,7), scores (B,K), labels (B,K) i32 (0-based), keep (B,K) i32, d_nk (B,) i32:
-        top-K decode and NMS (NMS_TYPE: rotated or axis-aligned) of all frames in one launch sequence, counts stay on the device."""
+        top-K decode and NMS (NMS_TYPE: rotated or axis-aligned) of all frames in one launch sequence, counts stay on the device.
+        shared: head is run_score_head's map of this shared map - columns 0:8 are computed at the selected cells between the selection
+        and the decode (regress_at_candidates)."""
         post = self.model_cfg.POST_PROCESSING
         nms = post.NMS_CONFIG
         # model_nms_utils.py:17 dispatches on the name; circle_nms is the reference's own `assert False` (centernet_utils.py:173-176)
@@ -1179,9 +1236,17 @@ class CenterHead(_Cached):
         # topk(pre_max) + sort (model_nms_utils.py:15-20) is the identity here
         if k > nms.NMS_PRE_MAXSIZE:
             raise DetZeroHipError('MAX_OBJ_PER_SAMPLE > NMS_PRE_MAXSIZE is not supported')
-        boxes, scores, labels, counts = ops.centerhead_decode(
-            head, h, w, len(self.class_names_each_head[index]), k, post.SCORE_THRESH, post.POST_CENTER_LIMIT_RANGE,
-            self.point_cloud_range, self.voxel_size, self.feature_map_stride, use_iou=self.iou_weight > 0)
+        ncls = len(self.class_names_each_head[index])
+        if shared is not None:
+            ws, cand, ncand = ops.centerhead_select(head, h, w, ncls, k, use_iou=self.iou_weight > 0)
+            self.regress_at_candidates(shared, head, cand, ncand, k, index)
+            boxes, scores, labels, counts = ops.centerhead_decode_selected(
+                head, h, w, ncls, k, post.SCORE_THRESH, post.POST_CENTER_LIMIT_RANGE, self.point_cloud_range, self.voxel_size,
+                self.feature_map_stride, ws)
+        else:
+            boxes, scores, labels, counts = ops.centerhead_decode(
+                head, h, w, ncls, k, post.SCORE_THRESH, post.POST_CENTER_LIMIT_RANGE,
+                self.point_cloud_range, self.voxel_size, self.feature_map_stride, use_iou=self.iou_weight > 0)
         keep, d_nk = nms_batched(boxes, counts, nms.NMS_THRESH, nms.NMS_POST_MAXSIZE)
         return boxes, scores, labels, keep, d_nk
 

@@ -827,6 +827,69 @@ def centerhead_decode(head, h, w, ncls, k, score_thresh, limit6, pc_range, voxel
     return boxes, scores, labels, counts
 
 
+def centerhead_select(head, h, w, ncls, k, use_iou=True):
+    """First half of centerhead_decode: head (B, H*W, 12), columns 8:12 read -> (ws, cand, ncand).  ws is the decode workspace (hand it
+    to centerhead_decode_selected); cand (B, 1024) int64 and ncand (B,) int32 are views of it: the min(K, ncls*HW) selected cells of a
+    frame in descending score order as  score bits << 32 | ~(cls * HW + pix)."""
+    lib = L.load()
+    L.require_cuda(head)
+    b = head.shape[0]
+    ws = _ws(lib.dz_centerhead_decode_workspace_bytes(b, h * w, ncls, k))
+    L.check(lib.dz_centerhead_select(L.ptr(head), b, h, w, ncls, k, 1 if use_iou else 0, L.ptr(ws), ws.numel(), L.stream()), 'dz_centerhead_select')
+    o_list = lib.dz_centerhead_candidates_offset(b, h * w, ncls, k, 0)
+    o_n = lib.dz_centerhead_candidates_offset(b, h * w, ncls, k, 1)
+    cand = ws[o_list:o_list + b * CAND_STRIDE * 8].view(torch.int64).view(b, CAND_STRIDE)
+    ncand = ws[o_n:o_n + b * 4].view(torch.int32)
+    return ws, cand, ncand
+
+
+def centerhead_decode_selected(head, h, w, ncls, k, score_thresh, limit6, pc_range, voxel_size, stride, ws):
+    """Second half of centerhead_decode on the workspace of centerhead_select: columns 0:8 of head are read at the selected cells only.
+    -> boxes (B,K,7), scores (B,K), labels (B,K) i32, counts (B,) i32 (device)."""
+    lib = L.load()
+    L.require_cuda(head, ws)
+    b = head.shape[0]
+    dev = head.device
+    boxes = torch.zeros((b, k, 7), dtype=torch.float32, device=dev)
+    scores = torch.zeros((b, k), dtype=torch.float32, device=dev)
+    labels = torch.zeros((b, k), dtype=torch.int32, device=dev)
+    counts = torch.zeros((b,), dtype=torch.int32, device=dev)
+    rc = lib.dz_centerhead_decode_selected(L.ptr(head), b, h, w, ncls, k, float(score_thresh), L.f6(limit6), L.f6(pc_range), L.f3(voxel_size),
+                                           int(stride), L.ptr(boxes), L.ptr(scores), L.ptr(labels), L.ptr(counts), L.ptr(ws), ws.numel(),
+                                           L.stream())
+    L.check(rc, 'dz_centerhead_decode_selected')
+    return boxes, scores, labels, counts
+
+
+CAND_STRIDE = 1024          # DZ_CENTERHEAD_CAND_STRIDE: candidate words per frame
+
+
+def head_at_candidates_supported(math, channels):
+    return bool(L.load().dz_head_at_candidates_supported(int(math), int(channels)))
+
+
+def head_at_candidates(shared, cand, ncand, k, w1, s1, b1, w2, s2, b2, g_cout, g_ooff, head, math):
+    """The regression branches of a CenterHead at candidate cells (dz_head_at_candidates): shared (B, H+2, W+2, 64) zero-bordered map of
+    `math`, cand (B, stride) int64 / ncand (B,) int32 as centerhead_select leaves them, hidden weights whose first 64 * len(g_cout)
+    output channels are the branches' - packed (9, cout, 64) in the split modes, (9, 64, cout) in fp32 - and the grouped output layer
+    w2 (groups >= len(g_cout), 9, 32, 64), fp32: (groups, 9, 64, 16); writes columns g_ooff[g] .. + g_cout[g] of the candidates' rows
+    of head (B, H*W, 12) in place."""
+    lib = L.load()
+    L.require_cuda(shared, cand, ncand, w1, s1, b1, w2, s2, b2, head)
+    b, hp, wp, c = shared.shape
+    nbr = len(g_cout)
+    w1_cout = w1.shape[-2] if math else w1.shape[-1]
+    if (c != 64 or head.shape != (b, (hp - 2) * (wp - 2), 12) or w1.shape[-1 if math else -2] != 64 or w2.shape[0] < nbr
+            or tuple(w2.shape[1:]) != ((9, 32, 64) if math else (9, 64, 16))):
+        raise L.DetZeroHipError('head_at_candidates: unexpected shapes')
+    ia = (ctypes.c_int * 4)(*([int(v) for v in g_cout] + [0] * (4 - nbr)))
+    io = (ctypes.c_int * 4)(*([int(v) for v in g_ooff] + [0] * (4 - nbr)))
+    rc = lib.dz_head_at_candidates(L.ptr(shared), b, hp - 2, wp - 2, L.ptr(cand), L.ptr(ncand), cand.shape[1], int(k), L.ptr(w1), w1_cout,
+                                   L.ptr(s1), L.ptr(b1), L.ptr(w2), L.ptr(s2), L.ptr(b2), nbr, ia, io, L.ptr(head), int(math), L.stream())
+    L.check(rc, 'dz_head_at_candidates')
+    return head
+
+
 def nms_rotated_nosync(boxes_sorted, d_n, thresh, post_max):
     """boxes_sorted (n_cap,7) descending score; returns keep (n_cap,) i32, d_num_keep (1,) i32."""
     lib = L.load()

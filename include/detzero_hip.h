@@ -424,6 +424,32 @@ int dz_centerhead_decode(const float *head, int batch, int h, int w, int ncls, i
                          const float *h_limit6, const float *h_range6, const float *h_vsize3, int stride,
                          int use_iou, float *boxes, float *scores, int *labels, int *d_counts, void *ws,
                          size_t ws_bytes, void *stream);
+/* The two halves of dz_centerhead_decode (which is select followed by decode_selected on one workspace).
+ * select reads columns 8:12 of the head map only (iou, hm) and leaves in the workspace, per batch item, the min(K, ncls*HW)
+ * selected candidates in descending (score, then ascending flat index) order - 64-bit words  score bits << 32 | ~(cls*HW + pix),
+ * DZ_CENTERHEAD_CAND_STRIDE words per item - and that count.  dz_centerhead_candidates_offset gives the byte offset of the list
+ * (which = 0) or of the (B) int32 counts (which = 1) inside the workspace.  decode_selected reads the list and columns 0:8 of the
+ * head map at the listed cells only - the columns dz_head_at_candidates fills between the two calls. */
+#define DZ_CENTERHEAD_CAND_STRIDE 1024
+size_t dz_centerhead_candidates_offset(int batch, int hw, int ncls, int k, int which);
+int dz_centerhead_select(const float *head, int batch, int h, int w, int ncls, int k, int use_iou, void *ws, size_t ws_bytes, void *stream);
+int dz_centerhead_decode_selected(const float *head, int batch, int h, int w, int ncls, int k, float score_thresh,
+                                  const float *h_limit6, const float *h_range6, const float *h_vsize3, int stride,
+                                  float *boxes, float *scores, int *labels, int *d_counts, void *ws, size_t ws_bytes, void *stream);
+
+/* The regression branches of a CenterHead (center, center_z, dim, rot: center_head.py:14-48) at candidate cells only.
+ * shared (B, h+2, w+2, 64) zero-bordered pair16 map of `math` (a split mode); cand / d_ncand: the list dz_centerhead_select writes
+ * (cand_stride words per item; slots >= d_ncand[b] do nothing).  w1 / s1 / b1: packed hidden-layer weights (9, w1_cout, 64) with
+ * folded BatchNorm scale / shift, of which channels 0 .. 64 * nbranch - 1 are the branches'; w2 (groups, 9, 32, 64), s2 / b2
+ * (groups * 32): the grouped output layer, branch g = group g.  For every candidate the 3 x 3 hidden pixels around its cell are
+ * evaluated (pixels outside the image are zero, as in the zero-bordered hidden map), rounded to pair16, and the output layer
+ * writes columns g_ooff[g] .. + g_cout[g] - 1 of the cell's row of head (B, h*w, 12) fp32.  Accumulation order, MFMA shape and
+ * roundings are those of dz_conv2d_forward_split, so the values are the dense route's bit for bit.  dz_head_at_candidates_supported:
+ * 1 when (math, shared channels) is served. */
+int dz_head_at_candidates_supported(int math, int channels);
+int dz_head_at_candidates(const float *shared, int batch, int h, int w, const unsigned long long *cand, const int *d_ncand, int cand_stride,
+                          int k, const float *w1, int w1_cout, const float *s1, const float *b1, const float *w2, const float *s2,
+                          const float *b2, int nbranch, const int *h_g_cout, const int *h_g_ooff, float *head, int math, void *stream);
 
 /* RoI features of the first-stage boxes (center_head.py:408-432,461-486: get_box_center with num_point 5 + absl_to_relative +
  * centernet_utils.bilinear_interpolate_torch:233-262): boxes (n, 7) of ONE frame; bev = that frame's (h, w, c) map, channel stride 1,
