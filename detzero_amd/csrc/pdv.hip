@@ -34,6 +34,7 @@ struct CentroidGeom {
 };
 
 // voxel_aggregation_utils.py:29-39: index = (p - lo) / vs in float32; outside iff index < 0 or index >= grid; then .long()
+// (a NaN index is outside here: the reference's two comparisons let it through to a conversion without a defined result)
 // (round 5: one atomicOr per point was 0.29 ms per 8 two-sweep frames - the stride-4 / stride-8 cells hold dozens of points each and
 // their atomics queue up on one address.  The lanes of a run of equal bitmap words OR their bits in registers, the run's last lane
 // reads the word first and skips the atomic when its bits are there already - a stale read only costs a redundant atomic.)
@@ -51,7 +52,7 @@ __global__ void k_cen_keys(const float *__restrict__ pts, int n, int stride, Cen
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 q[a] = __fdiv_rn(__fsub_rn(p[1 + a], g.lo[a]), g.vs[a]);
-                ok = ok && !(q[a] < 0.f) && !(q[a] >= (float)g.g[a]);
+                ok = ok && q[a] >= 0.f && q[a] < (float)g.g[a];               // (a NaN coordinate is outside: it has no cell)
             }
             if (ok) {
                 const int cx = (int)q[0], cy = (int)q[1], cz = (int)q[2];
