@@ -357,8 +357,17 @@ int dz_linear_forward_split(const float *x, long rows, int cin, int x_stride, co
         // y = (rows / group_rows, y_stride) fp32: max over every group's rows, fused into the layer's epilogue
         DZ_CHECK_ARG(out_f32 && group_rows >= 128 && group_rows % 128 == 0 && rows % group_rows == 0 && y_stride % 4 == 0 && ((uintptr_t)y & 15u) == 0,
                      "dz_linear_forward_split: group_max needs fp32 output, group_rows %% 128 == 0 (got %d), rows %% group_rows == 0, a 16-byte aligned result", group_rows);
-        const int rc = fill_u32(y, 0xFF800000u, (size_t)(rows / group_rows) * y_stride, (hipStream_t)stream_);        // -inf
-        if (rc) return rc;
+        // -inf into the cout columns the epilogue's atomics work on; columns beside them (y_stride > cout) belong to the caller
+        const long ngroups = rows / group_rows;
+        if (y_stride == cout) {
+            const int rc = fill_u32(y, 0xFF800000u, (size_t)ngroups * y_stride, (hipStream_t)stream_);
+            if (rc) return rc;
+        } else {
+            for (long g = 0; g < ngroups; ++g) {
+                const int rc = fill_u32(y + (size_t)g * y_stride, 0xFF800000u, (size_t)cout, (hipStream_t)stream_);
+                if (rc) return rc;
+            }
+        }
     }
     if (group_rows < 1) group_rows = 1;
     // the rows are fetched through 32-bit buffer offsets: at most ~2 GiB of them per launch

@@ -303,9 +303,9 @@ __global__ __launch_bounds__(PN_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             for (int s = 0; s < 8; ++s) {
                 v4u whi, wlo;
                 wfrag_u(wbase3, 32, 0, s, whi, wlo);
-                if constexpr (M::TERMS != 1) {
-                    d = M::mma(hl[s], whi, d);
+                if constexpr (M::TERMS != 1) {                              // (w lo . x hi, then w hi . x lo: the order of hgemm.h, for the same bits)
                     d = M::mma(hh[s], wlo, d);
+                    d = M::mma(hl[s], whi, d);
                 }
                 d = M::mma(hh[s], whi, d);
             }

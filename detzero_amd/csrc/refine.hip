@@ -9,7 +9,9 @@
 namespace dz {
 
 // x (groups*len, c) row-major -> out (groups, c).  Block = 4 row lanes x 64 channels; every row is read as
-// 256 contiguous bytes per 64-channel slab.
+// 256 contiguous bytes per 64-channel slab.  -0.0 orders below +0.0 (v_max_f32), as in the integer atomics of the fused epilogues.
+// NaN is outside the contract: the refiner pools ReLU outputs.  fmaxf drops a NaN (the maximum of the group's other values, -inf if
+// there are none) where torch.max of the reference would return it.
 __global__ __launch_bounds__(256) void k_group_max(const float *__restrict__ x, int len, int c, float *__restrict__ out) {
     __shared__ float red[4][64];
     const int g = blockIdx.x;

@@ -1015,7 +1015,12 @@ def crop_points_in_boxes_nosync(xyz, boxes, payload, cap):
 
 def mha_core(q, k, v, key_padding_mask, heads, scale, math=0):
     """q (B,Lq,E), k/v (B,Lk,E), mask (B,Lk) bool/uint8 or None -> (B,Lq,E).  math 0: exact fp32 (dz_mha_core); 1 / 2: operands as
-    16-bit pairs on the 16-bit matrix cores (dz_mha_core_split)."""
+    16-bit pairs on the 16-bit matrix cores (dz_mha_core_split).  The split cores stay within their bound (tests/test_gpu_refine_kernels.py:
+    8 x the host emulation of their roundings, 4.0e-3 / 3.2e-3 of sum_j p_j |v_j| for f16x2 / bf16x2) for logits (scale q.k) of standard
+    deviation 2^-12 .. 2^8 and |v| of the order 2^-12 .. 2^8 in f16x2 (below |v| ~ 2^-4 the fp16 lo halves of v turn subnormal and the error
+    grows from 2e-7 to 5e-5 at 2^-12; |q scale log2 e|, |k|, |v| beyond 65504 saturate) and for logits of standard deviation up to 2^4, any
+    v, in bf16x2.  The refiner is well inside: with the synthetic weights on the golden inputs (tests/test_refine.py) its attention layers
+    see logits of standard deviation 1.0 - 1.5 (largest 9) and |v| of median 0.6 - 0.8 (largest 5)."""
     lib = L.load()
     L.require_cuda(q, k, v)
     b, lq, e = q.shape
