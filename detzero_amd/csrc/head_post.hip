@@ -560,8 +560,10 @@ __global__ void k_crop_gather(const int *__restrict__ pairs, const int *__restri
                               int t, int row_words, int *__restrict__ offsets) {
     const int total = min(*d_total, cap);
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid <= t) offsets[gid] = gid < t ? (int)prefix[(size_t)gid * row_words] : *d_total;
-    for (long idx = gid; idx < (long)total * words; idx += (long)gridDim.x * blockDim.x) {
+    const long step = (long)gridDim.x * blockDim.x;
+    for (long b = gid; b <= t; b += step)                        // (the grid is capped: more boxes than threads is possible)
+        offsets[b] = b < t ? (int)prefix[(size_t)b * row_words] : *d_total;
+    for (long idx = gid; idx < (long)total * words; idx += step) {
         const int r = (int)(idx / words), wq = (int)(idx % words);
         const int pt = pairs[(size_t)r * 4 + 3];                 // [box, 0, 0, point]
         out[idx] = payload[(size_t)pt * words + wq];

@@ -148,6 +148,8 @@ __global__ __launch_bounds__(256) void k_prm_boxes(const double *__restrict__ tr
 
 enum { PRM_XYZ = 0, PRM_INTENSITY = 1, PRM_P2CO = 2, PRM_SCORE = 3, PRM_CLASS = 4 };
 
+constexpr int PRM_MAX_CHANNELS = 40;       // channels per feature row, padded to quads (all five features once: 35)
+
 struct PrmEncoding {
     int n;
     int code[8];
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(256) void k_prm_points(const double *__restrict__ p
     const unsigned int q_items = (unsigned int)q_n * quads, items = (unsigned int)(q_n + m_n) * quads;
     const int slots = batch * box_max;
     // per channel: feature code and index inside the feature (the same for every row) - looked up instead of searched
-    __shared__ unsigned char s_code[40], s_k[40];
+    __shared__ unsigned char s_code[PRM_MAX_CHANNELS], s_k[PRM_MAX_CHANNELS];
     __shared__ double s_an[27];
     for (unsigned int c = threadIdx.x; c < 4u * quads; c += blockDim.x) {
         int e = 0;
@@ -344,6 +346,9 @@ int dz_prm_encode_points(const double *pts, const int *box_offsets, const double
     DZ_CHECK_ARG(h_encoding && n_enc >= 1 && n_enc <= 8, "dz_prm_encode_points: 1..8 encoding entries");
     const int ch = prm_channels(h_encoding, n_enc);
     DZ_CHECK_ARG(ch > 0, "dz_prm_encode_points: unknown encoding code");
+    // k_prm_points keeps one table entry per channel of a row padded to whole quads
+    DZ_CHECK_ARG((ch + 3) / 4 * 4 <= PRM_MAX_CHANNELS, "dz_prm_encode_points: %d feature channels exceed %d (a repeated encoding entry?)", ch,
+                 PRM_MAX_CHANNELS);
     if (batch == 0) return DZ_OK;
     DZ_CHECK_ARG(box_offsets && traj && score && obj_box_offsets && traj_local && padding_mask && init_box && anchors,
                  "dz_prm_encode_points: null pointer");

@@ -177,6 +177,8 @@ def prm_features(tracks, encoding=('xyz', 'intensity', 'p2co', 'score'), query_n
     (B,query_num,7), 'padding_mask' (B,query_num) float32, 'pos_init_box' (B,7) float64, 'box_num', 'obj_cls', 'batch_size'}."""
     if any(e not in PRM_CODES for e in encoding):
         raise L.DetZeroHipError('PRM encoding %r (supported: %s)' % (list(encoding), sorted(PRM_CODES)))
+    if len(set(encoding)) != len(encoding):
+        raise L.DetZeroHipError('PRM encoding %r repeats a feature' % (list(encoding),))
     packed = tracks if isinstance(tracks, PackedTracks) else PackedTracks(tracks, device)
     if max(packed.box_num, default=0) > query_num:
         raise L.DetZeroHipError('object track with %d boxes exceeds QUERY_NUM = %d' % (max(packed.box_num), query_num))
@@ -224,6 +226,8 @@ def crm_features(tracks, encoding=('xyz', 'intensity', 'p2co', 'score'), query_n
     encoding is the PRM query encoding, same kernel)."""
     if any(e not in PRM_CODES or e == 'class' for e in encoding):
         raise L.DetZeroHipError('CRM encoding %r (supported on the device: xyz, intensity, p2co, score)' % (list(encoding),))
+    if len(set(encoding)) != len(encoding):
+        raise L.DetZeroHipError('CRM encoding %r repeats a feature' % (list(encoding),))
     packed = tracks if isinstance(tracks, PackedTracks) else PackedTracks(tracks, device)
     if max(packed.box_num, default=0) > query_num:
         raise L.DetZeroHipError('object track with %d boxes exceeds QUERY_NUM = %d' % (max(packed.box_num), query_num))

@@ -608,7 +608,9 @@ int dz_prm_feature_channels(const int *h_encoding, int n_enc);   /* channels of 
  * (B,box_max,m_n,channels), traj_local (B,box_max,7) and padding_mask (B,box_max) float32, init_box (B,7) float64 - points
  * and boxes in the frame of the object's middle box (waymo_position_dataset.py:72-78, data_utils.py:74-113), boxes past
  * an object's own are zero with mask 1.  anchors: scratch of B*box_max*27 + 2*B doubles.  obj_cls (B) 1-based, may be
- * NULL without the 'class' feature. */
+ * NULL without the 'class' feature; a class outside 1..3 (0 = unknown) sets none of the three class channels.  At most 40
+ * channels per row, counted in whole groups of four (every feature once is 35): a longer list - a repeated 'p2co', say -
+ * is refused with DZ_ERR_INVALID. */
 int dz_prm_encode_points(const double *pts, const int *box_offsets, const double *traj, const double *score,
                          const int *obj_box_offsets, const int *obj_cls, const int *q_idx, const int *m_idx, int q_n, int m_n,
                          int batch, int box_max, const int *h_encoding, int n_enc, float *query, float *memory,

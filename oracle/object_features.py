@@ -161,7 +161,8 @@ def prm_object(track, encoding=('xyz', 'intensity', 'p2co', 'score'), query_num=
             lm.append(np.tile(score[:, None, None], (1, memory_pts_num, 1)))
         elif e == 'class':
             one = np.zeros(3)
-            one[cls - 1] = 1
+            if 1 <= cls <= 3:                                                                   # an unknown class (0) has no reference (the
+                one[cls - 1] = 1                                                                # name lookup fails there): all zero by contract
             lq.append(np.tile(one[None, None, :], (t, query_pts_num, 1)))
             lm.append(np.tile(one[None, None, :], (t, memory_pts_num, 1)))
         else:
