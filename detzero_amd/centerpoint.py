@@ -10,6 +10,7 @@ voxelize -> VFE -> sparse backbone -> BEV -> head -> decode -> NMS, every size-d
 in device counters, so one frame is ~110 kernel launches with no host synchronisation; results are
 padded (500, 9) boxes + a count, which is also the payload of the RCCL gather.
 """
+import contextlib
 import math
 import os
 
@@ -18,8 +19,9 @@ import torch
 import torch.nn as nn
 
 from . import det_modules as cp_modules
-from . import iou3d_nms_utils, ops
+from . import iou3d_nms_utils, ops, range_audit as _range_audit
 from .lib import DetZeroHipError
+from .range_audit import RangeAudit
 
 
 class CenterPoint(nn.Module):
@@ -269,9 +271,35 @@ def prescale_exponents(peaks, target=F16_PAIR_TARGET_PEAK):
 
 
 @torch.no_grad()
-def activation_range(model, dataset_info, frames, dynamic=False):
-    """Largest |activation| per stage of the detector on sample frames, measured on the exact-fp32 engine: the outputs of the
-    five sparse stages and the concatenated 2-D feature map.  Leaves the model in 'f32' math."""
+def range_audit(model, dataset_info, frames, math=None, dynamic=False):
+    """One FramePipeline pass over `frames` (sparse backbone, BEV backbone, the head's dense stage, decode) under a RangeAudit ->
+    its report: one dict per STORED tensor (range_audit.RangeAudit.report).  math: the mode to run in (None = the model's current
+    one); with 'f32' the peaks are the calibration measurement of every tensor.  One host sync."""
+    audit = RangeAudit()
+    pipe = FramePipeline(model, dataset_info, math=math, dynamic=dynamic, audit=audit)
+    pipe(list(frames))
+    return audit.report()
+
+
+def group_peaks(report):
+    """{stage: largest peak over the tensors of the stage's exponent group} of a range_audit report (fp32 outputs have no group)."""
+    out = {k: 0.0 for k in PRESCALE_STAGES}
+    for r in report:
+        if r['stage'] in out:
+            out[r['stage']] = max(out[r['stage']], float(r['peak']))
+    return out
+
+
+@torch.no_grad()
+def activation_range(model, dataset_info, frames, dynamic=False, probe='stages'):
+    """Largest |activation| per stage of the detector on sample frames, measured on the exact-fp32 engine.  probe='stages': the outputs
+    of the five sparse stages and the concatenated 2-D feature map.  probe='all': per stage the maximum over EVERY stored tensor that
+    shares the stage's exponent (hidden tensors of the residual blocks, every layer of the BEV blocks, the head's shared and hidden
+    maps - a `range_audit` pass).  Leaves the model in 'f32' math."""
+    if probe == 'all':
+        return group_peaks(range_audit(model, dataset_info, frames, math='f32', dynamic=dynamic))
+    if probe != 'stages':
+        raise DetZeroHipError("activation_range: probe is 'stages' or 'all' (got %r)" % (probe,))
     pipe = FramePipeline(model, dataset_info, math='f32', dynamic=dynamic)
     frames = list(frames)
     out = {}
@@ -284,19 +312,29 @@ def activation_range(model, dataset_info, frames, dynamic=False):
     return out
 
 
-def select_math(model, dataset_info, frames, prefer='f16x2', dynamic=False, target=F16_PAIR_TARGET_PEAK):
+def select_math(model, dataset_info, frames, prefer='f16x2', dynamic=False, target=F16_PAIR_TARGET_PEAK, probe='stages', verify=False):
     """Fit the split-precision arithmetic to a checkpoint from a calibration pass on the exact-fp32 engine: the per-stage activation
     peaks give per-stage power-of-two exponents (`prescale_exponents`) that put every stage's tensors where fp16 pairs carry 22 bits,
     whatever the checkpoint's own scale is - activations of 1e6 (fp16 saturates at 65504) as well as of 1e-4 (the lo half of an
     unscaled pair would be subnormal).  The factors are exact (powers of two folded into scale / shift), so the result is that of
     the same network at O(1000) activations.  Rounds 2-5 fell back to bf16 pairs (16 bits) outside [2^-6, 3e4]; round 6 measured
     bf16 pairs at up to 5e-3 on data-dependent boxes - outside the north star's 1e-3 - so they are an opt-in mode only.
+    probe='all' takes each stage's peak over every stored tensor of its exponent group instead of over the stage outputs alone
+    (`activation_range`): a checkpoint whose hidden activations run hotter than its stage outputs then gets smaller exponents.
+    verify=True runs one audited pass in the chosen mode on the calibration frames afterwards and raises DetZeroHipError naming the
+    first tensor that saturated or went non-finite.
     Returns (mode, per-stage maxima); sets the mode and the pre-scale (model.prescale = the exponents)."""
-    rng = activation_range(model, dataset_info, frames, dynamic)
+    frames = list(frames)
+    rng = activation_range(model, dataset_info, frames, dynamic, probe=probe)
     exps = prescale_exponents(rng, target)
     set_prescale(model, exps if ops.storage_math(ops.math_id(prefer)) == 1 else None)
     model.prescale = exps
     set_math(model, prefer)
+    if verify:
+        bad = _range_audit.first_violation(range_audit(model, dataset_info, frames, math=prefer, dynamic=dynamic))
+        if bad is not None:
+            raise DetZeroHipError("select_math: %r math with the %r exponents %s does not hold this checkpoint's activations - %s"
+                                  % (prefer, probe, exps, _range_audit.describe(bad)))
     return prefer, rng
 
 
@@ -323,8 +361,10 @@ class FramePipeline:
     [0,count) are ``[x,y,z,dx,dy,dz,heading,score,label(1-based)]`` after NMS.
     """
 
-    def __init__(self, model, dataset_info, mode='test', dynamic=False, math=None, ways=None):
+    def __init__(self, model, dataset_info, mode='test', dynamic=False, math=None, ways=None, audit=None):
         self.model = model.eval()
+        # audit: a RangeAudit - every pass of this pipeline then probes the tensors it stores into it (`check_range`); None = no probe
+        self.audit = audit
         if math is not None:
             set_math(model, math)
         # ways: a batch is split into this many sub-passes that run CONCURRENTLY on their own streams (`_call_split`): every launch of
@@ -508,10 +548,25 @@ class FramePipeline:
                                   're-run calibrate() on denser samples / with a larger margin, or drop the calibration'
                                   % (self.level_caps,))
 
+    def _recording(self):
+        return self.audit.recording() if self.audit is not None else contextlib.nullcontext()
+
+    def check_range(self):
+        """Raises when a tensor stored by a pass since the last check saturated its fp16 pairs or went non-finite (needs `audit=`):
+        the pre-scale in force does not hold these frames - re-run select_math(probe='all') on hotter samples; stale exponents after
+        new weights show here too.  One host sync; the records are cleared for the next check."""
+        if self.audit is None:
+            raise DetZeroHipError('FramePipeline.check_range: construct the pipeline with audit=RangeAudit()')
+        bad = _range_audit.first_violation(self.audit.report())
+        self.audit.reset()
+        if bad is not None:
+            raise DetZeroHipError('FramePipeline: range check failed - ' + _range_audit.describe(bad))
+
     @torch.no_grad()
     def backbone_stage(self, prep):
         """The 21 sparse convolutions -> {name: (rows, SparseLevel)}."""
-        res = self.model.backbone3d.run_pyramid(prep)            # (a staggered pyramid finishes its index, and the flag, in here)
+        with self._recording():
+            res = self.model.backbone3d.run_pyramid(prep)        # (a staggered pyramid finishes its index, and the flag, in here)
         self.last_overflow = prep.get('overflow', None)          # flag of THIS pass (device bool); the counter below is sticky
         if self.last_overflow is not None:
             # (after run_pyramid: the flag is written on the index-pyramid side stream, and the main stream has by now waited for
@@ -526,6 +581,11 @@ class FramePipeline:
 
     @torch.no_grad()
     def dense_stage(self, res, nb):
+        """`_dense_stage`, its stored tensors probed into the pipeline's audit when it has one."""
+        with self._recording():
+            return self._dense_stage(res, nb)
+
+    def _dense_stage(self, res, nb):
         """HeightCompression + BaseBEVBackbone + the CenterHead convolutions -> (head map (B,H*W,12), H, W).
         With `head_at_candidates` (and a head csrc/head_cand.hip serves) only the branches the selection reads at every cell run here:
         columns 8:12 of the map (9:12 when IOU_WEIGHT is 0) are written, columns 0:8 are NOT - post_stage fills them at the selected
@@ -728,6 +788,7 @@ class FramePipeline:
         prev = None
         for (part, _, _), sub, st in zip(parts, self._subs, self._way_streams):
             sub.head_at_candidates = self.head_at_candidates
+            sub.audit = self.audit                   # (one record per tensor for both sub-passes: the probes add with device-scope atomics)
             sub.level_caps, sub.dense_group = self.level_caps, self.dense_group       # (every sub-pass keeps its OWN sticky overflow counter:
             sub.fork_ok = nested_ok                                                    # two streams OR-ing into one word would race)
             st.wait_stream(main)

@@ -20,8 +20,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, range_audit
 from .lib import DetZeroHipError
+from .range_audit import RangeAudit  # noqa: F401  (the audit's class is part of this module's surface)
 
 PACKED_TABLES = bool(os.environ.get('DZ_TUNE_PACKED_TABLES'))     # opt-in: packed 27-tap tables for the small-channel levels (measured equal)
 
@@ -398,11 +399,18 @@ class VoxelResBackBone8x(_Cached):
         return p
 
     # ---- execution ------------------------------------------------------------------------------
-    def _res_block(self, x, nbr, level, params, e=0):
+    def _audit(self, name, stage, y, level, e):
+        """Range probe of a convolution's output rows (those below the level's device count) while an audit records."""
+        audit = range_audit.active()
+        if audit is not None:
+            audit.probe('backbone3d.' + name, y, math=self.math, stage=stage, exp=e, d_rows=level.d_m)
+        return y
+
+    def _res_block(self, x, nbr, level, params, e=0, name=None, stage=None):
         """(all tensors of a level - block inputs, hidden activations, the residual - share the level's exponent e)"""
         c1, c2 = params
-        y = ops.spconv_forward(x, nbr, level, *self._p(c1, e, e), None, True, math=self.math)
-        return ops.spconv_forward(y, nbr, level, *self._p(c2, e, e), x, True, math=self.math)
+        y = self._audit('%s.conv1' % name, stage, ops.spconv_forward(x, nbr, level, *self._p(c1, e, e), None, True, math=self.math), level, e)
+        return self._audit('%s.conv2' % name, stage, ops.spconv_forward(y, nbr, level, *self._p(c2, e, e), x, True, math=self.math), level, e)
 
     def build_pyramid(self, voxel_features, voxel_coords, batch_size, d_n=None, overlap=True, side_key=0, caps=None, level1=None,
                       staggered=False, exact=False):
@@ -543,9 +551,9 @@ class VoxelResBackBone8x(_Cached):
         ready(ev)
         ci = p['conv_input']
         e = self._e('x_conv1')                                # (the voxel features themselves are stored unscaled)
-        x = ops.spconv_forward(x, nbr, lvl1, *self._p(ci, 0, e), None, True, math=mm)
-        for bp in p['conv1']:
-            x = self._res_block(x, nbr, lvl1, bp, e)
+        x = self._audit('conv_input', 'x_conv1', ops.spconv_forward(x, nbr, lvl1, *self._p(ci, 0, e), None, True, math=mm), lvl1, e)
+        for bi, bp in enumerate(p['conv1']):
+            x = self._res_block(x, nbr, lvl1, bp, e, 'conv1.%d' % bi, 'x_conv1')
         lvl1.act_exp = e
         out = {'x_conv1': (x, lvl1)}
         level = lvl1
@@ -556,9 +564,10 @@ class VoxelResBackBone8x(_Cached):
             nbr_d, nbr, nxt, ev = steps[i + 1]
             ready(ev)
             e_prev, e = e, self._e('x_conv%d' % (i + 2))
-            x = ops.spconv_forward(x, nbr_d, nxt, *self._p(dp, e_prev, e), None, True, in_level=level, math=mm)
-            for bp in p[name]['blocks']:
-                x = self._res_block(x, nbr, nxt, bp, e)
+            stage = 'x_conv%d' % (i + 2)
+            x = self._audit('%s.0' % name, stage, ops.spconv_forward(x, nbr_d, nxt, *self._p(dp, e_prev, e), None, True, in_level=level, math=mm), nxt, e)
+            for bi, bp in enumerate(p[name]['blocks']):
+                x = self._res_block(x, nbr, nxt, bp, e, '%s.%d' % (name, bi + 1), stage)
             nxt.act_exp = e
             out['x_conv%d' % (i + 2)] = (x, nxt)
             level = nxt
@@ -566,7 +575,7 @@ class VoxelResBackBone8x(_Cached):
         nbr_d, _, nxt, ev = steps[4]
         ready(ev)
         e_prev, e = e, self._e('encoded')
-        x = ops.spconv_forward(x, nbr_d, nxt, *self._p(dp, e_prev, e), None, True, in_level=level, math=mm)
+        x = self._audit('conv_out', 'encoded', ops.spconv_forward(x, nbr_d, nxt, *self._p(dp, e_prev, e), None, True, in_level=level, math=mm), nxt, e)
         nxt.act_exp = e
         out['encoded'] = (x, nxt)
         return out
@@ -841,6 +850,7 @@ class BaseBEVBackbone(_Cached):
         convs = lvl['convs']
         bufs = None
         tiles = zero = None
+        audit = range_audit.active()
         e_in, e_mid = self._e('encoded'), self._e('spatial_features_2d')     # exponents of the BEV input and of every tensor of this module
         if sparse_in is not None and li == 0 and SKIP_EMPTY_TILES:
             # pixel tiles far enough from any data compute the network's zero-input response: they are left out of the launches of the
@@ -881,11 +891,23 @@ class BaseBEVBackbone(_Cached):
                            out_d=(1, 1), ho=oh, wo=ow, batch=batch, math=self.math, in_tiles=tl)
                 if tl is not None:
                     ops.bev_fill_empty_tiles(tl, batch, oh, ow, shc, True, cv['cout'], y, self.math, zero_resp=zero[ci])
+            if audit is not None:
+                # (after the fill of the skipped tiles: the whole zero-bordered image of this launch's frames; nn.Sequential index 1 + 3 ci)
+                audit.probe('backbone2d.blocks.%d.%d' % (li, 1 + 3 * ci), y, math=self.math, stage='spatial_features_2d', exp=e_mid)
             x, xh, xw, xc = y, oh, ow, cv['cout']
         return x, xh, xw, xc
 
-    def _level_deblock(self, lvl, x, xh, xw, xc, concat, coff, h, w, batch):
+    def _level_deblock(self, lvl, x, xh, xw, xc, concat, coff, h, w, batch, li=0):
         """ConvTranspose2d (kernel == stride) + BN + ReLU of a block's output into channels [coff, coff + cout) of the concatenation."""
+        self._deblock_launches(lvl, x, xh, xw, xc, concat, coff, h, w, batch)
+        de = lvl['de']
+        audit = range_audit.active()
+        if audit is not None:
+            audit.probe('backbone2d.deblocks.%d' % li, concat, math=self.math, stage='spatial_features_2d', exp=self._e('spatial_features_2d'),
+                        c_off=coff, c=de['cout'])
+        return coff + de['cout']
+
+    def _deblock_launches(self, lvl, x, xh, xw, xc, concat, coff, h, w, batch):
         de = lvl['de']
         s = de['s']
         ctot = self.num_bev_features
@@ -899,14 +921,13 @@ class BaseBEVBackbone(_Cached):
                        (h + 2, w + 2), cin=de['cin'], in_cstride=xc, ksize=1, stride=1, in_off=1,
                        out_cstride=ctot, out_coff=coff, out_s=s, out_d=(1, 1), ho=xh, wo=xw, batch=batch, math=self.math,
                        groups=s * s, g_cout=[de['cout']] * (s * s), g_ooff=[0] * (s * s), phase_groups=True)
-            return coff + de['cout']
+            return
         for dy in range(s):
             for dx in range(s):
                 conv_layer(x, (xh + 2, xw + 2), *self._p(de['phases'][dy][dx], e_mid, e_mid, scale=de['scale'], shift=de['shift']), True, concat,
                            (h + 2, w + 2), cin=de['cin'], in_cstride=xc, ksize=1, stride=1, in_off=1,
                            out_cstride=ctot, out_coff=coff, out_s=s, out_d=(dy + 1, dx + 1), ho=xh, wo=xw,
                            batch=batch, math=self.math)
-        return coff + de['cout']
 
     def run(self, bev, batch, sparse_in=None):
         """bev (B, H+2, W+2, Cin) zero-bordered channel-last -> concat (B, H+2, W+2, sum(upsample)) zero-bordered.
@@ -926,7 +947,7 @@ class BaseBEVBackbone(_Cached):
         coff = 0
         for li, lvl in enumerate(plan):
             x, xh, xw, xc = self._level_convs(li, lvl, x, xh, xw, xc, batch, dev, sparse_in=sparse_in if li == 0 else None)
-            coff = self._level_deblock(lvl, x, xh, xw, xc, concat, coff, h, w, batch)
+            coff = self._level_deblock(lvl, x, xh, xw, xc, concat, coff, h, w, batch, li)
         return concat
 
     def grouped_fits(self, nb, h, w):
@@ -980,8 +1001,8 @@ class BaseBEVBackbone(_Cached):
             ng = min(group, nb - g0)
             concat = bordered_zeros('bev2d.concat', (ng, h + 2, w + 2, self.num_bev_features), dev)
             coff = 0
-            for lvl, (x, xh, xw, xc) in zip(plan, outs):
-                coff = self._level_deblock(lvl, x[g0:g0 + ng], xh, xw, xc, concat, coff, h, w, ng)
+            for li, (lvl, (x, xh, xw, xc)) in enumerate(zip(plan, outs)):
+                coff = self._level_deblock(lvl, x[g0:g0 + ng], xh, xw, xc, concat, coff, h, w, ng, li)
             consume(concat, g0, ng)
 
     def forward(self, data_dict):
@@ -1141,6 +1162,9 @@ class CenterHead(_Cached):
         conv_layer(concat, (hp, wp), *self._p(p['shared'], e, e), True, shared, (hp, wp),
                    cin=p['shared']['cin'], in_cstride=concat.shape[3], out_cstride=c, out_d=(1, 1), ho=hp - 2, wo=wp - 2, batch=batch,
                    math=self.math)
+        audit = range_audit.active()
+        if audit is not None:
+            audit.probe('dense_head.shared_conv', shared, math=self.math, stage='spatial_features_2d', exp=e)
         return shared
 
     def run_head(self, shared, batch, index=0):
@@ -1162,7 +1186,23 @@ class CenterHead(_Cached):
         conv_layer(hidden, (hp, wp), *self._p(hp_['final'], e, 0, scale=None, shift=hp_['final']['shift32' if mm else 'shift']), False, head, (h, w),
                    cin=c, in_cstride=6 * c, out_cstride=12, out_d=(0, 0), groups=6, cout_pad=32 if mm else 16,
                    g_cout=hp_['final']['g_cout'], g_ooff=hp_['final']['g_ooff'], ho=h, wo=w, batch=batch, math=mm, out_f32=True)
+        self._audit_head('heads_list.%d' % index, 'hidden', 'final', hidden, head, hp_['final'], e)
         return head, h, w
+
+    def _audit_head(self, prefix, hidden_name, final_name, hidden, head, fin, e):
+        """Range probes of a head's hidden map (pair storage in the split modes) and of the written columns of its fp32 output map."""
+        audit = range_audit.active()
+        if audit is None:
+            return
+        audit.probe('dense_head.%s.%s' % (prefix, hidden_name), hidden, math=self.math, stage='spatial_features_2d', exp=e)
+        lo = min(fin['g_ooff'])
+        hi = max(o + n for o, n in zip(fin['g_ooff'], fin['g_cout']))
+        # fp32 output rows of which only columns [lo, hi) are written (the others are left to the candidate kernel, or unwritten): the probe
+        # reads whole groups of 8 channels, so the written columns are copied into a zero-padded image of the pass's workspace
+        flat = head.view(-1, head.shape[-1])
+        stage_img = bordered_zeros('audit.%s.%s' % (prefix, final_name), (flat.shape[0], -(-(hi - lo) // 8) * 8), head.device)
+        stage_img[:, :hi - lo].copy_(flat[:, lo:hi])
+        audit.probe('dense_head.%s.%s' % (prefix, final_name), stage_img, math=0, stage=None, exp=0)
 
     def run_convs(self, concat, batch):
         """concat (B,H+2,W+2,Cin) zero-bordered -> head map (B, H*W, 12) channel-last of the FIRST head (the single-head layout of
@@ -1195,6 +1235,7 @@ class CenterHead(_Cached):
         conv_layer(hidden, (hp, wp), *self._p(fin, e, 0, scale=None, shift=fin['shift32' if mm else 'shift']), False, head, (h, w),
                    cin=c, in_cstride=ng * c, out_cstride=12, out_d=(0, 0), groups=ng, cout_pad=32 if mm else 16,
                    g_cout=fin['g_cout'], g_ooff=fin['g_ooff'], ho=h, wo=w, batch=batch, math=mm, out_f32=True)
+        self._audit_head('heads_list.%d' % index, 'score_hidden', 'score_final', hidden, head, fin, e)
         return head, h, w
 
     def candidate_params(self, index=0):

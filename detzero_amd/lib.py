@@ -103,6 +103,8 @@ _SIGS = {
     'dz_spconv_variant': (ctypes.c_char_p, [c_int, c_int]),
     'dz_pair16_from_f32': (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
     'dz_pair16_to_f32': (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_void_p, c_void_p]),
+    'dz_range_probe': (c_int, [c_void_p, ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'dz_range_reset': (c_int, [c_void_p, c_int, c_void_p]),
     'dz_scatter_rows_split': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     'dz_spconv_forward_split': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),

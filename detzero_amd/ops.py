@@ -609,6 +609,50 @@ def pair16_to_f32(x, math=1):
 
 
 # ------------------------------------------------------------------------------------------------
+# range probe (csrc/range_probe.hip): per-tensor peak / fp16-pair saturation / non-finite counts in device records
+# ------------------------------------------------------------------------------------------------
+RANGE_DTYPE = np.dtype([('peak', np.float32), ('saturated', np.uint64), ('nonfinite', np.uint64), ('elements', np.uint64)])
+
+
+def range_table(n_slots, device):
+    """Zeroed table of n_slots records (n_slots, 4) int64: [peak bits, saturated, nonfinite, elements] (include/detzero_hip.h)."""
+    return torch.zeros((int(n_slots), 4), dtype=torch.int64, device=device)
+
+
+def range_probe(t, slot_view, *, math, rows=None, d_rows=None, c_off=0, c=None):
+    """Add the range of `t` to one record.  t: contiguous float32-typed tensor whose last dimension is the row (fp32 values, or the
+    pair16 words of a split mode); slot_view: one row of a `range_table`; math: the storage of t (a mode name or id; 'f16' reads as
+    'f16x2').  rows: leading rows to read (default all), d_rows: device int32 count that limits them further; [c_off, c_off + c): the
+    channel slice (default: the rest of the row).  Asynchronous on the current stream, no allocation."""
+    lib = L.load()
+    L.require_cuda(t, slot_view, d_rows)
+    if t.dtype != torch.float32 or slot_view.dtype != torch.int64 or slot_view.numel() != 4:
+        raise L.DetZeroHipError('range_probe: a float32-typed tensor and a 4-word int64 record are expected')
+    stride = int(t.shape[-1])
+    cap = t.numel() // max(stride, 1)
+    rows = cap if rows is None else int(rows)
+    if rows > cap:
+        raise L.DetZeroHipError('range_probe: %d rows asked of a tensor of %d' % (rows, cap))
+    c = stride - int(c_off) if c is None else int(c)
+    L.check(lib.dz_range_probe(L.ptr(t) if rows else None, rows, L.ptr(d_rows), stride, int(c_off), c, storage_math(math_id(math)), L.ptr(slot_view),
+                               L.stream()), 'dz_range_probe')
+
+
+def range_reset(table):
+    L.require_cuda(table)
+    L.check(L.load().dz_range_reset(L.ptr(table), table.shape[0], L.stream()), 'dz_range_reset')
+
+
+def range_read(table):
+    """The one host copy of a table -> numpy structured array (peak as float32, the three counters as uint64)."""
+    raw = table.cpu().numpy().view(np.uint64).reshape(-1, 4)
+    out = np.zeros((raw.shape[0],), dtype=RANGE_DTYPE)
+    out['peak'] = (raw[:, 0] & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.float32)
+    out['saturated'], out['nonfinite'], out['elements'] = raw[:, 1], raw[:, 2], raw[:, 3]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # dense conv
 # ------------------------------------------------------------------------------------------------
 def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None):

@@ -238,6 +238,21 @@ const char *dz_spconv_variant(int cin, int cout);
 int dz_pair16_from_f32(const float *src, long rows, int c_src, int c_dst, int math, float *dst, void *stream);
 /* dst (rows, c) f32 <- src (rows, c) pair16 (hi + lo) */
 int dz_pair16_to_f32(const float *src, long rows, int c, int math, float *dst, void *stream);
+/* Range probe of a stored tensor: one streaming read that ADDS to a device record `slot` of four 64-bit words
+ *   slot[0] peak       max |v| over the finite elements, kept as the bits of a non-negative fp32 (zero-extended); v = the element (fp32 storage)
+ *                      or float(hi) + float(lo) in fp32 (pair16 storage)
+ *   slot[1] saturated  DZ_MATH_F16X2 / DZ_MATH_F16 storage only: elements whose hi half is +-65504 (bits 0x7BFF without the sign) - what the
+ *                      clamp of the fp16-pair split leaves behind; always 0 for the other storages
+ *   slot[2] nonfinite  elements that are inf / NaN (pairs: either half has an all-ones exponent); such an element does not enter the peak
+ *   slot[3] elements   elements looked at = rows read x c
+ * Records accumulate over calls (max for the peak, sums for the counters) with device-scope atomics: several launches, frame groups and
+ * streams may share a slot.  No host synchronisation, no allocation.  x: rows of row_stride_words 32-bit words (a multiple of 4, x 16-byte
+ * aligned), of which channels [c_off, c_off + c) are read (both multiples of 8); rows = the row capacity, d_rows = optional device count:
+ * min(*d_rows, rows) rows are read.  math = the STORAGE of x: DZ_MATH_F32, or pair16 of DZ_MATH_F16X2 (= DZ_MATH_F16) / DZ_MATH_BF16X2.
+ * rows == 0: DZ_OK without a launch (x may then be NULL).  dz_range_reset zeroes n_slots consecutive records. */
+int dz_range_probe(const float *x, long rows, const int *d_rows, int row_stride_words, int c_off, int c, int math, unsigned long long *slot,
+                   void *stream);
+int dz_range_reset(unsigned long long *table, int n_slots, void *stream);
 /* dz_scatter_rows writing pair16 rows */
 int dz_scatter_rows_split(const float *src, const int *rank, const int *d_n, int n_cap, int c_src, float *dst,
                           int c_dst, int math, void *stream);
