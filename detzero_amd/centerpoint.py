@@ -241,6 +241,20 @@ def set_sparse_engine(model, engine, f32_engine=None):
     return model
 
 
+def set_dense_engine(model, f32_engine):
+    """Engine of the 3 x 3 stride-1 dense layers (BEV backbone, the head's shared and hidden convolutions) in the exact-fp32 mode:
+    'mfma32' (default: k_conv2d on the fp32 matrix cores) or 'bf16x3' (csrc/conv3x3_t.hip: every operand as three exact bf16 limbs,
+    six bf16 MFMAs per product - fp32-class results in another accumulation order).  Strided layers, deblocks, the grouped output layer
+    and the head-at-candidates kernel stay where they are; the split math modes ignore the switch."""
+    if f32_engine not in ops.DENSE_F32_ENGINES:
+        raise DetZeroHipError('unknown fp32 dense engine %r (%s)' % (f32_engine, ' | '.join(ops.DENSE_F32_ENGINES)))
+    for name in ('backbone2d', 'dense_head'):
+        mod = getattr(model, name, None)
+        if mod is not None and hasattr(mod, 'set_dense_engine'):
+            mod.set_dense_engine(f32_engine)
+    return model
+
+
 # development switch: DZ_TUNE_EAGER_PYRAMID=1 builds the whole index pyramid before the first convolution (the r01c-r03f schedule)
 STAGGERED_PYRAMID = not os.environ.get('DZ_TUNE_EAGER_PYRAMID')
 

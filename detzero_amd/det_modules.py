@@ -63,6 +63,7 @@ class _Cached(nn.Module):
         self._plan = None
         self.act_exp = None
         self.math = 0       # ops.MATH_MODES: 0 = fp32 MFMA, 1 = fp16-pair split, 2 = bf16-pair split, 3 = fp16 pairs with one product (csrc/hgemm.h)
+        self.f32_dense_engine = 'mfma32'    # BaseBEVBackbone / CenterHead: set_dense_engine
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate())
 
     def invalidate(self):
@@ -133,6 +134,28 @@ class _Cached(nn.Module):
         if ck not in entry:
             entry[ck] = ops.pack_weight_split(entry[key], ops.storage_math(self.math))
         return entry[ck]
+
+    def set_dense_engine(self, f32_engine):
+        """Engine of the 3 x 3 stride-1 dense layers in the exact-fp32 mode: 'mfma32' (k_conv2d, the default) or 'bf16x3' (three bf16
+        limbs per operand, csrc/conv3x3_t.hip).  The split modes ignore it."""
+        if f32_engine not in ops.DENSE_F32_ENGINES:
+            raise DetZeroHipError('unknown fp32 dense engine %r (%s)' % (f32_engine, ' | '.join(ops.DENSE_F32_ENGINES)))
+        self.f32_dense_engine = f32_engine
+        CACHE_GEN[0] += 1
+        return self
+
+    def _l3(self, entry, key='w'):
+        """With the bf16x3 engine on in f32 mode: a function that returns the entry's weights in the three-limb layout (packed once,
+        cached in the plan entry like `_w`'s) for conv_layer to use where the kernel covers the layer; None otherwise."""
+        if self.math or getattr(self, 'f32_dense_engine', 'mfma32') != 'bf16x3':
+            return None
+
+        def packed():
+            ck = '%s_limb3' % key
+            if ck not in entry:
+                entry[ck] = ops.pack_weight_limb3(entry[key])
+            return entry[ck]
+        return packed
 
     def _apply(self, fn, *a, **kw):
         self._plan = None
@@ -715,12 +738,14 @@ FUSED_DEBLOCK_PHASES = os.environ.get('DZ_TUNE_DEBLOCK_PHASES', '1') != '0'     
 def conv_layer(inp, in_shape, w, scale, shift, relu, out, out_shape, *, cin, in_cstride, in_coff=0, ksize=3,
                stride=1, in_off=0, out_cstride, out_coff=0, out_s=1, out_d=(0, 0), groups=1, cout_pad=None,
                g_cout=None, g_ooff=None, ho=None, wo=None, batch=1, math=0, out_f32=False, phase_groups=False, in_rowidx=None,
-               in_row_channels=0, in_rows=0, in_tiles=None):
+               in_row_channels=0, in_rows=0, in_tiles=None, w_limb3=None):
     """One dz_conv2d_forward[_split] call.  in_shape/out_shape = (Hp, Wp) of the (padded) images.
-    math != 0: w is the pack_weight_split layout (..., cout_pad, cin)."""
+    math != 0: w is the pack_weight_split layout (..., cout_pad, cin).
+    w_limb3 (f32 mode, `_Cached._l3`): the layer runs on the bf16x3 engine with the weights that function returns wherever
+    dz_conv3x3_limb3_supported takes it, on dz_conv2d_forward otherwise."""
     if cout_pad is None:
         cout_pad = w.shape[-2] if math else w.shape[-1]
-    ops.conv2d(dict(
+    desc = dict(
         inp=inp.data_ptr(), out=out.data_ptr(), w=w.data_ptr(),
         scale=scale.data_ptr() if scale is not None else None,
         shift=shift.data_ptr() if shift is not None else None,
@@ -732,8 +757,12 @@ def conv_layer(inp, in_shape, w, scale, shift, relu, out, out_shape, *, cin, in_
         g_cout=g_cout if g_cout is not None else [cout_pad], g_ooff=g_ooff if g_ooff is not None else [0],
         relu=1 if relu else 0, phase_groups=1 if phase_groups else 0,
         in_rowidx=in_rowidx.data_ptr() if in_rowidx is not None else None, in_row_channels=int(in_row_channels), in_rows=int(in_rows),
-        in_tiles=in_tiles.data_ptr() if in_tiles is not None else None),
-        math=math, out_f32=out_f32, tiles=in_tiles)
+        in_tiles=in_tiles.data_ptr() if in_tiles is not None else None)
+    if w_limb3 is not None and not math and ops.conv3x3_limb3_supported(desc):
+        desc['w'] = w_limb3().data_ptr()
+        ops.conv2d(desc, math=math, out_f32=out_f32, tiles=in_tiles, f32_engine='bf16x3')
+        return
+    ops.conv2d(desc, math=math, out_f32=out_f32, tiles=in_tiles)      # engine off: the call made before the engine existed, word for word
 
 
 class BaseBEVBackbone(_Cached):
@@ -770,6 +799,8 @@ class BaseBEVBackbone(_Cached):
         self.layer_strides, self.upsample_strides = layer_strides, upsample_strides
         self.num_filters, self.num_upsample_filters = num_filters, num_upsample_filters
         self.input_channels = input_channels
+        # engine of the 3 x 3 stride-1 layers in the exact-fp32 mode: 'mfma32' (default) | 'bf16x3' (csrc/conv3x3_t.hip, opt-in: DESIGN.md 2a)
+        self.f32_dense_engine = os.environ.get('DZ_TUNE_DENSE_F32_ENGINE', 'mfma32')
 
     def plan(self):
         if self._plan is not None:
@@ -888,7 +919,7 @@ class BaseBEVBackbone(_Cached):
                 wc, scc, shc = self._p(cv, e_in if (li == 0 and ci == 0) else e_mid, e_mid)
                 conv_layer(x, (xh + 2, xw + 2), wc, scc, shc, True, y, (oh + 2, ow + 2),
                            cin=cv['cin'], in_cstride=xc, ksize=3, stride=s, in_off=0, out_cstride=cv['cout'],
-                           out_d=(1, 1), ho=oh, wo=ow, batch=batch, math=self.math, in_tiles=tl)
+                           out_d=(1, 1), ho=oh, wo=ow, batch=batch, math=self.math, in_tiles=tl, w_limb3=self._l3(cv))
                 if tl is not None:
                     ops.bev_fill_empty_tiles(tl, batch, oh, ow, shc, True, cv['cout'], y, self.math, zero_resp=zero[ci])
             if audit is not None:
@@ -1108,6 +1139,8 @@ class CenterHead(_Cached):
         self.predict_boxes_when_training = predict_boxes_when_training
         self.forward_ret_dict = {}
         self.input_channels = input_channels
+        # engine of the 3 x 3 stride-1 layers in the exact-fp32 mode: 'mfma32' (default) | 'bf16x3' (csrc/conv3x3_t.hip, opt-in: DESIGN.md 2a)
+        self.f32_dense_engine = os.environ.get('DZ_TUNE_DENSE_F32_ENGINE', 'mfma32')
 
     def plan(self):
         if self._plan is not None:
@@ -1161,7 +1194,7 @@ class CenterHead(_Cached):
         e = self._e('spatial_features_2d')                    # (the head's hidden maps share the exponent of its input)
         conv_layer(concat, (hp, wp), *self._p(p['shared'], e, e), True, shared, (hp, wp),
                    cin=p['shared']['cin'], in_cstride=concat.shape[3], out_cstride=c, out_d=(1, 1), ho=hp - 2, wo=wp - 2, batch=batch,
-                   math=self.math)
+                   math=self.math, w_limb3=self._l3(p['shared']))
         audit = range_audit.active()
         if audit is not None:
             audit.probe('dense_head.shared_conv', shared, math=self.math, stage='spatial_features_2d', exp=e)
@@ -1180,7 +1213,7 @@ class CenterHead(_Cached):
         hidden = bordered_zeros('head.hidden', (batch, hp, wp, 6 * c), dev)
         e = self._e('spatial_features_2d')
         conv_layer(shared, (hp, wp), *self._p(hp_['hidden'], e, e), True, hidden, (hp, wp),
-                   cin=c, in_cstride=c, out_cstride=6 * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm)
+                   cin=c, in_cstride=c, out_cstride=6 * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm, w_limb3=self._l3(hp_['hidden']))
         head = torch.empty((batch, h * w, 12), dtype=torch.float32, device=dev)
         # (output layer: no BatchNorm - the plan holds no scale; fp32 output at exponent 0)
         conv_layer(hidden, (hp, wp), *self._p(hp_['final'], e, 0, scale=None, shift=hp_['final']['shift32' if mm else 'shift']), False, head, (h, w),
@@ -1229,7 +1262,8 @@ class CenterHead(_Cached):
         hidden = bordered_zeros('head.hidden_score', (batch, hp, wp, ng * c), dev)
         e = self._e('spatial_features_2d')
         conv_layer(shared, (hp, wp), *self._p(hp_['score_hidden'], e, e), True, hidden, (hp, wp),
-                   cin=c, in_cstride=c, out_cstride=ng * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm)
+                   cin=c, in_cstride=c, out_cstride=ng * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm,
+                   w_limb3=self._l3(hp_['score_hidden']))
         head = torch.empty((batch, h * w, 12), dtype=torch.float32, device=dev)
         fin = hp_['score_final']
         conv_layer(hidden, (hp, wp), *self._p(fin, e, 0, scale=None, shift=fin['shift32' if mm else 'shift']), False, head, (h, w),

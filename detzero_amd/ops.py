@@ -558,6 +558,52 @@ def pack_weight_split(w, math, cout_mult=32):
     return pair16_pack(wt.contiguous(), math)
 
 
+BF16_MAX = 3.3895313892515355e38      # 0x7F7F: the clamp in front of the first rounding of the three-limb split
+
+
+def _limbs3(x):
+    """The three bf16 limbs of fp32 x (csrc/conv3x3_t.hip): h = rn(clamp(x, +-bf16-max)), m = rn(x - h), l = rn(x - h - m) - the last
+    rounding is exact for every finite x, so h + m + l == x bit for bit."""
+    x = x.float()
+    h = x.clamp(-BF16_MAX, BF16_MAX).to(torch.bfloat16)
+    r1 = x - h.float()
+    m = r1.to(torch.bfloat16)
+    l = (r1 - m.float()).to(torch.bfloat16)
+    # a zero limb takes the sign of x, so that the limbs of -0 sum to -0 (the value of the limb is that of its remainder either way)
+    z = torch.copysign(torch.zeros_like(x), x).to(torch.bfloat16)
+    return h, torch.where(m == 0, z, m), torch.where(l == 0, z, l)
+
+
+def limb3_pack(x):
+    """Host/torch packer (any device): x (..., C) fp32, C % 8 == 0 -> (..., C * 3 / 2) float32-typed words: per group of 8 channels
+    16 bytes of h limbs, 16 of m, 16 of l (bf16).  The operand format of dz_conv3x3_limb3_forward's weights."""
+    shp = x.shape
+    if shp[-1] % 8 != 0:
+        raise L.DetZeroHipError('limb3_pack: the last dimension (%d) must be a multiple of 8' % shp[-1])
+    g = shp[-1] // 8
+    out = torch.stack([t.reshape(*shp[:-1], g, 8) for t in _limbs3(x)], dim=-2)
+    return out.reshape(*shp[:-1], g * 24).contiguous().view(torch.float32)
+
+
+def limb3_unpack(x):
+    """limb3_pack's inverse, bit for bit: (..., C * 3 / 2) words -> (..., C) fp32 = h + (m + l) (m + l is the exact first remainder:
+    summed in this order nothing rounds, and +-fp32-max does not pass through 2^128)."""
+    shp = x.shape
+    g = shp[-1] // 12
+    t = x.contiguous().view(torch.bfloat16).reshape(*shp[:-1], g, 3, 8).float()
+    return (t[..., 0, :] + (t[..., 1, :] + t[..., 2, :])).reshape(*shp[:-1], g * 8)
+
+
+def pack_weight_limb3(w, cout_mult=64):
+    """(taps, cin, cout) fp32 conv weights -> (taps, cout_pad, cin * 3 / 2) limb words, output-channel rows (cout padded with zero rows)."""
+    wt = w.float().transpose(-1, -2)
+    co = wt.shape[-2]
+    cp = -(-co // cout_mult) * cout_mult
+    if cp > co:
+        wt = torch.cat([wt, wt.new_zeros(*wt.shape[:-2], cp - co, wt.shape[-1])], dim=-2)
+    return limb3_pack(wt.contiguous())
+
+
 F16_PAIR_WEIGHT_TOP = 2.0 ** 14      # where the largest |weight| of an output channel is placed before the fp16-pair split
 
 
@@ -655,23 +701,41 @@ def range_read(table):
 # ------------------------------------------------------------------------------------------------
 # dense conv
 # ------------------------------------------------------------------------------------------------
-def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None):
+DENSE_F32_ENGINES = ('mfma32', 'bf16x3')
+
+
+def _conv2d_desc(desc_kwargs):
+    d = L.Conv2dDesc()
+    for k, v in desc_kwargs.items():
+        if k in ('g_cout', 'g_ooff'):
+            arr = getattr(d, k)
+            for i, e in enumerate(v):
+                arr[i] = int(e)
+        else:
+            setattr(d, k, v)
+    return d
+
+
+def conv3x3_limb3_supported(desc_kwargs):
+    """Whether the bf16x3 engine of the f32 mode (dz_conv3x3_limb3_forward) takes the layer of these dz_conv2d_desc fields.  Host only."""
+    return bool(L.load().dz_conv3x3_limb3_supported(ctypes.byref(_conv2d_desc(desc_kwargs))))
+
+
+def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None, f32_engine=None):
     """One dense-conv launch from a dict of dz_conv2d_desc fields.  math != 0: pair16 input / weights
     (pack_weight_split layout) and pair16 output unless out_f32.  tiles: the tensor behind `in_tiles` (profiling only: the work of
-    the launch is that of the tiles it runs)."""
+    the launch is that of the tiles it runs).  f32_engine='bf16x3' (math 0 only; the split modes ignore it): the three-limb kernel
+    of csrc/conv3x3_t.hip, `w` in the pack_weight_limb3 layout; a layer it does not cover is an error."""
     lib = L.load()
-    d = L.Conv2dDesc()
-    g_cout = desc_kwargs.pop('g_cout')
-    g_ooff = desc_kwargs.pop('g_ooff')
-    for k, v in desc_kwargs.items():
-        setattr(d, k, v)
-    for i, v in enumerate(g_cout):
-        d.g_cout[i] = int(v)
-    for i, v in enumerate(g_ooff):
-        d.g_ooff[i] = int(v)
+    if f32_engine not in (None,) + DENSE_F32_ENGINES:
+        raise L.DetZeroHipError('unknown fp32 dense engine %r (%s)' % (f32_engine, ' | '.join(DENSE_F32_ENGINES)))
+    limb3 = f32_engine == 'bf16x3' and not math
+    d = _conv2d_desc(desc_kwargs)
 
     def launch():
-        if math:
+        if limb3:
+            L.check(lib.dz_conv3x3_limb3_forward(ctypes.byref(d), L.stream()), 'dz_conv3x3_limb3_forward')
+        elif math:
             L.check(lib.dz_conv2d_forward_split(ctypes.byref(d), int(math), 1 if out_f32 else 0, L.stream()), 'dz_conv2d_forward_split')
         else:
             L.check(lib.dz_conv2d_forward(ctypes.byref(d), L.stream()), 'dz_conv2d_forward')
@@ -690,7 +754,10 @@ def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None):
         share = n_run / float(max(n_run + n_skip, 1))
         flops *= share
         nbytes = 4.0 * (share * (m * d.cin + m * cout) + taps * d.cin * d.cout_pad * d.groups)
-    name = (lib.dz_conv2d_variant_split(ctypes.byref(d), 1 if out_f32 else 0) if math else lib.dz_conv2d_variant(ctypes.byref(d))).decode()
+    if limb3:
+        name = lib.dz_conv3x3_limb3_variant(ctypes.byref(d)).decode()
+    else:
+        name = (lib.dz_conv2d_variant_split(ctypes.byref(d), 1 if out_f32 else 0) if math else lib.dz_conv2d_variant(ctypes.byref(d))).decode()
     PROFILER.wrap(name, flops, nbytes, launch)
 
 
@@ -1186,7 +1253,7 @@ def _install_guards():
     import types
     g = globals()
     for name, obj in list(g.items()):
-        if isinstance(obj, types.FunctionType) and obj.__module__ == __name__ and not name.startswith('_') and name not in ('grid_size_of', 'math_id', 'pair16_pack', 'pair16_unpack'):
+        if isinstance(obj, types.FunctionType) and obj.__module__ == __name__ and not name.startswith('_') and name not in ('grid_size_of', 'math_id', 'pair16_pack', 'pair16_unpack', 'limb3_pack', 'limb3_unpack', 'conv3x3_limb3_supported'):
             g[name] = _guarded(obj)
     for name in ('build_from_coords', 'downsample', 'neighbors_to'):
         setattr(SparseLevel, name, _guarded(getattr(SparseLevel, name)))

@@ -380,6 +380,21 @@ int dz_sparse_to_bev_split_dense(const float *feats, int feat_rows, const uint32
 int dz_conv2d_forward_split(const dz_conv2d_desc *h_desc, int math, int out_f32, void *stream);
 /* the kernel and tile dz_conv2d_forward_split runs for this descriptor and out_f32, "none" where it refuses the layer */
 const char *dz_conv2d_variant_split(const dz_conv2d_desc *h_desc, int out_f32);
+/* Opt-in engine of the exact-fp32 mode for the 3 x 3 stride-1 layers (csrc/conv3x3_t.hip): fp32 images in and out exactly as
+ * dz_conv2d_forward takes and writes them, every operand on the bf16 matrix pipe as THREE bf16 limbs.  Any finite fp32 x is exactly
+ * h + m + l with h = rn(x), m = rn(x - h), l = x - h - m (8 + 8 + 8 = 24 bits; x is clamped to +-bf16-max before the first rounding
+ * only, so no limb is inf); a product is h.h + h.m + m.h + h.l + l.h + m.m, six bf16 MFMAs whose products are exact in fp32 - the
+ * dropped terms are at most 2^-26 of |x.w|.  fp32-class results in another accumulation order than dz_conv2d_forward's.  For
+ * |x| < 2^-100 the l limb is a bf16 subnormal; whether the matrix pipe keeps it has not been measured.
+ *   desc->w = the weights split at plan time: (9, cout_pad, cin / 8, 3, 8) bf16 - per output-channel row and group of 8 input
+ *   channels 16 bytes of h, 16 of m, 16 of l (ops.pack_weight_limb3).  Epilogue and write contract as dz_conv2d_forward.
+ * dz_conv3x3_limb3_supported (host only, no GPU needed) is 1 exactly for kh == kw == 3, stride 1, groups 1, cin % 32 == 0,
+ * cout_pad % 64 == 0, no phase_groups / in_rowidx / in_tiles / group_shift / group_max, and image and weight bytes below 2 GiB;
+ * dz_conv3x3_limb3_forward returns DZ_ERR_UNSUPPORTED for anything else without launching.  dz_conv3x3_limb3_variant:
+ * "k_conv3x3_t<8x32x128>" (cout_pad % 128 == 0), "k_conv3x3_t<8x32x64>" or "none". */
+int dz_conv3x3_limb3_forward(const dz_conv2d_desc *h_desc, void *stream);
+int dz_conv3x3_limb3_supported(const dz_conv2d_desc *h_desc);
+const char *dz_conv3x3_limb3_variant(const dz_conv2d_desc *h_desc);
 /* dz_linear_forward on pair16 rows: x (rows, x_stride words) pair16, w (cout_pad, cin) pair16 (cin, cout_pad % 32 == 0), y pair16
  * rows or, with out_f32 != 0, fp32 rows; group_shift (row groups, cout_pad) fp32 as in dz_linear_forward.
  * group_max != 0 (with out_f32): the torch.max over the points of an object that follows the PointNet encoders
