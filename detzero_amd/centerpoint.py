@@ -236,7 +236,9 @@ def set_sparse_engine(model, engine, f32_engine=None):
     for the submanifold convolutions of the 32 / 64 / 128-channel levels), 'gather' (sparse_conv_h.hip / sparse_conv_w.h only; both
     on rows in the canonical linear-key order) or 'tiles' (sparse_conv_t.hip: tile-resident inputs on rows in the brick order).
     f32_engine: the engine of the exact-fp32 mode, 'gather' (default: sparse_conv.hip) or 'xrun' (plus sparse_conv_xf.hip for the same
-    submanifold convolutions, from the same index); None leaves it as it is."""
+    submanifold convolutions, from the same index) or 'xrun_bf16x3' (the index of 'xrun'; those convolutions on the bf16 matrix pipe with
+    three exact limbs per operand, sparse_conv_xt.hip, at the widths it covers and on sparse_conv_xf.hip at the others); None leaves it
+    as it is."""
     model.backbone3d.set_engine(engine, f32_engine)
     return model
 

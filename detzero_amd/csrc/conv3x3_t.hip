@@ -20,6 +20,7 @@
 //   waves: 4 (pairs of image rows) x 2 (halves of BC); wave tile = 2 x 32 pixels x BC/2 channels; 48 (BC = 128) MFMAs per tap
 //   persistent workgroups, XCD-banded like k_conv3x3_h; a workgroup keeps one channel tile, its weight stream wraps from tile to tile
 #include "hgemm.h"
+#include "limb3.h"
 
 namespace dz {
 
@@ -27,7 +28,6 @@ constexpr int T3_TW = 32, T3_KC = 32, T3_NT = 512;
 constexpr int T3_GRP_U4 = 3;                                      // one 8-channel group: h, m, l
 constexpr int T3_ROW_U4 = (T3_KC / 8) * T3_GRP_U4 + 1;            // 208-byte LDS rows
 constexpr int T3_PXW = T3_TW + 2;
-constexpr float T3_BF16_MAX = 3.3895313892515355e38f;            // 0x7F7F0000
 
 template <int BC>
 struct T3Cfg {
@@ -46,18 +46,6 @@ struct T3Cfg {
     static_assert(BC == 64 || BC == 128, "BC is 64 or 128");
     static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit the LDS of a CU");
 };
-
-// two fp32 values -> their three bf16 limbs, packed (a in the low half): split2<MathBF16> with the clamp in front and one more
-// remainder step
-__device__ __forceinline__ void split3x2(float a, float b, unsigned int &h, unsigned int &m, unsigned int &l) {
-    const f32x2v x = {a, b};
-    const f32x2v xc = {__builtin_amdgcn_fmed3f(a, -T3_BF16_MAX, T3_BF16_MAX), __builtin_amdgcn_fmed3f(b, -T3_BF16_MAX, T3_BF16_MAX)};
-    h = __builtin_bit_cast(unsigned int, __builtin_convertvector(xc, b2_t));
-    const f32x2v r1 = x - f32x2v{__uint_as_float(h << 16), __uint_as_float(h & 0xFFFF0000u)};
-    m = __builtin_bit_cast(unsigned int, __builtin_convertvector(r1, b2_t));
-    const f32x2v r2 = r1 - f32x2v{__uint_as_float(m << 16), __uint_as_float(m & 0xFFFF0000u)};
-    l = __builtin_bit_cast(unsigned int, __builtin_convertvector(r2, b2_t));
-}
 
 template <int BC>
 __global__ __launch_bounds__(T3_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_conv3x3_t(dz_conv2d_desc p, int tiles_x, int tiles_y, unsigned int in_bytes,

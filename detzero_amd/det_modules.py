@@ -376,6 +376,7 @@ class VoxelResBackBone8x(_Cached):
         self.engine = os.environ.get('DZ_TUNE_SPCONV_ENGINE', 'xrun')
         # ... and of the exact-fp32 mode: 'gather' (default: sparse_conv.hip for every convolution) or 'xrun' (the submanifold convolutions
         # of the 32 / 64 / 128-channel levels on sparse_conv_xf.hip, from the same packed tables + windows; everything else as 'gather')
+        # or 'xrun_bf16x3' (as 'xrun', those layers on the bf16 matrix pipe with three exact limbs per operand: sparse_conv_xt.hip)
         self.f32_engine = os.environ.get('DZ_TUNE_SPCONV_F32_ENGINE', 'gather')
         # output widths whose convolutions run on the tile engine when it is selected (the others keep the gather kernels)
         self.tile_couts = tuple(int(c) for c in os.environ.get('DZ_TUNE_SPCONV_TILE_COUTS', '16,32,64,128').split(',') if c)
@@ -386,11 +387,12 @@ class VoxelResBackBone8x(_Cached):
     def set_engine(self, engine, f32_engine=None):
         """'gather' (rows in the canonical linear-key order), 'xrun' (gather + the z-slab window kernel for the submanifold
         convolutions of the 32 / 64 / 128-channel levels; same row order) or 'tiles' (tile-resident convolution; rows in brick order).
-        f32_engine (None = unchanged): the engine of the exact-fp32 mode, 'gather' or 'xrun'."""
+        f32_engine (None = unchanged): the engine of the exact-fp32 mode, 'gather', 'xrun' or 'xrun_bf16x3' (the tables of 'xrun'; the
+        submanifold layers on the three-limb kernel of sparse_conv_xt.hip where it covers the width, on sparse_conv_xf.hip otherwise)."""
         if engine not in ('gather', 'tiles', 'xrun'):
             raise DetZeroHipError('unknown sparse engine %r (gather | xrun | tiles)' % (engine,))
-        if f32_engine is not None and f32_engine not in ('gather', 'xrun'):
-            raise DetZeroHipError('unknown fp32 sparse engine %r (gather | xrun)' % (f32_engine,))
+        if f32_engine is not None and f32_engine not in ops.SPARSE_F32_ENGINES:
+            raise DetZeroHipError('unknown fp32 sparse engine %r (%s)' % (f32_engine, ' | '.join(ops.SPARSE_F32_ENGINES)))
         if engine == 'tiles' and ops.L.load().dz_spconv_tile_rows() == 0:
             raise DetZeroHipError("sparse engine 'tiles' is an experimental build option (measured slower, DESIGN.md 2d): rebuild the library "
                                   'with DZ_BUILD_EXPERIMENTAL=1 (python -m detzero_amd.build --force)')
@@ -432,8 +434,24 @@ class VoxelResBackBone8x(_Cached):
     def _res_block(self, x, nbr, level, params, e=0, name=None, stage=None):
         """(all tensors of a level - block inputs, hidden activations, the residual - share the level's exponent e)"""
         c1, c2 = params
-        y = self._audit('%s.conv1' % name, stage, ops.spconv_forward(x, nbr, level, *self._p(c1, e, e), None, True, math=self.math), level, e)
-        return self._audit('%s.conv2' % name, stage, ops.spconv_forward(y, nbr, level, *self._p(c2, e, e), x, True, math=self.math), level, e)
+        (p1, kw1), (p2, kw2) = self._sub_p(c1, nbr, e), self._sub_p(c2, nbr, e)
+        y = self._audit('%s.conv1' % name, stage, ops.spconv_forward(x, nbr, level, *p1, None, True, math=self.math, **kw1), level, e)
+        return self._audit('%s.conv2' % name, stage, ops.spconv_forward(y, nbr, level, *p2, x, True, math=self.math, **kw2), level, e)
+
+    def _sub_p(self, entry, nbr, e):
+        """((weights, scale, shift), further keywords of ops.spconv_forward) of a submanifold convolution over table `nbr`: `_p`'s and
+        none (the call is the one made without this engine), except in f32 mode with the fp32 engine 'xrun_bf16x3' on a table with x-run
+        windows and a width k_spconv_xt covers - then the weights are the entry's limb form (packed once, cached in the plan entry)
+        and the keyword names the engine.  A width it does not cover stays on k_spconv_xf."""
+        w, scale, shift = self._p(entry, e, e)
+        if self.math or self.f32_engine != 'xrun_bf16x3' or getattr(nbr, 'xwin', None) is None:
+            return (w, scale, shift), {}
+        cin, cout = int(w.shape[1]), int(w.shape[2])
+        if cin != cout or ops.L.load().dz_spconv_x_limb3_window_rows(cin, cout) == 0:
+            return (w, scale, shift), {}
+        if 'w_xlimb3' not in entry:
+            entry['w_xlimb3'] = ops.pack_weight_limb3(entry['w'], cout_mult=32)
+        return (entry['w_xlimb3'], scale, shift), {'f32_engine': 'xrun_bf16x3'}
 
     def build_pyramid(self, voxel_features, voxel_coords, batch_size, d_n=None, overlap=True, side_key=0, caps=None, level1=None,
                       staggered=False, exact=False):
@@ -478,7 +496,7 @@ class VoxelResBackBone8x(_Cached):
         # conv2) built packed - a third of the words; the index chain gains what the decode costs the convolutions
         pack = PACKED_TABLES and self.math != 0 and not tiled and self.layout == 0
 
-        xrun = (self.engine if self.math != 0 else self.f32_engine) == 'xrun' and self.layout == 0
+        xrun = (self.engine == 'xrun' if self.math != 0 else self.f32_engine in ('xrun', 'xrun_bf16x3')) and self.layout == 0
         xrun_couts = tuple(int(c) for c in os.environ.get('DZ_TUNE_XRUN_COUTS', '32,64,128').split(',') if c)
 
         def table(src, dst, k, s, p, cout):

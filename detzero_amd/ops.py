@@ -373,6 +373,11 @@ def gather_rows(src, idx, d_n, n_cap):
     return out
 
 
+# engines of the sparse backbone's exact-fp32 mode (Backbone3d.set_engine): the gather kernel everywhere; + k_spconv_xf for the submanifold
+# convolutions of the 32 / 64 / 128-channel levels; + k_spconv_xt (three bf16 limbs per operand) for those it covers, k_spconv_xf otherwise
+SPARSE_F32_ENGINES = ('gather', 'xrun', 'xrun_bf16x3')
+
+
 def _xrun_f32_usable(lib, nbr, w_taps):
     """The packed table carries x-run windows the exact-fp32 x-run kernel can run this (kvol, cin, cout) fp32 layer from."""
     xwin = getattr(nbr, 'xwin', None)
@@ -381,23 +386,47 @@ def _xrun_f32_usable(lib, nbr, w_taps):
             and xwin[1] == lib.dz_spconv_x_tile_rows(cin, cout))
 
 
-def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None):
+def _xrun_limb3_usable(lib, nbr, w_limb):
+    """The packed table carries x-run windows the bf16x3 x-run kernel can run this layer from; w_limb: its (27, cout, cin * 3 / 2)
+    limb weights (pack_weight_limb3(w, cout_mult=32))."""
+    xwin = getattr(nbr, 'xwin', None)
+    if w_limb.dim() != 3 or w_limb.shape[0] != 27 or w_limb.shape[2] % 12 != 0:
+        return False
+    cout, cin = int(w_limb.shape[1]), int(w_limb.shape[2]) * 2 // 3
+    return (xwin is not None and cin == cout and lib.dz_spconv_x_limb3_window_rows(cin, cout) > 0
+            and xwin[1] == lib.dz_spconv_x_tile_rows(cin, cout))
+
+
+def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None,
+                   f32_engine=None):
     """feats (m_in,cin); nbr (kvol,cap); returns (cap,cout).
     math == 0: fp32 rows, w_taps (kvol,cin,cout) fp32; a packed table with x-run windows (neighbors_xrun / build_windows) runs a
     cin == cout layer of 32 / 64 / 128 channels on the exact-fp32 x-run kernel (dz_spconv_forward_x_f32).
+    f32_engine (math 0 only; the split modes ignore it): None or 'xrun' = the above; 'xrun_bf16x3' = the same table and rows on the
+    three-limb kernel of csrc/sparse_conv_xt.hip (dz_spconv_forward_x_limb3), `w_taps` in the pack_weight_limb3(w, cout_mult=32)
+    layout; a layer or table that kernel does not cover is an error.
     math != 0: pair16 rows (in, residual, out), w_taps (kvol,cout_pad,cin) pair16 from pack_weight_split."""
     lib = L.load()
     L.require_cuda(feats, nbr, w_taps, scale, shift, residual)
+    if f32_engine not in (None,) + SPARSE_F32_ENGINES:
+        raise L.DetZeroHipError('unknown fp32 sparse engine %r (%s)' % (f32_engine, ' | '.join(SPARSE_F32_ENGINES)))
+    limb3 = f32_engine == 'xrun_bf16x3' and not math
     kvol, cap = nbr.shape
     packed = getattr(nbr, 'packed', False)
+    if limb3 and not (packed and _xrun_limb3_usable(lib, nbr, w_taps)):
+        raise L.DetZeroHipError("spconv_forward: fp32 engine 'xrun_bf16x3' needs a packed table with x-run windows and the limb weights "
+                                'of a 32 / 64 / 128-channel cin == cout layer the kernel covers')
     if packed:
         kvol = nbr.kvol
-        # (fp32: only the x-run kernel of sparse_conv_xf.hip reads a packed table - it needs the table's windows, for a layer it covers)
-        if not math and not _xrun_f32_usable(lib, nbr, w_taps):
+        # (fp32: only the x-run kernels of sparse_conv_xf.hip / sparse_conv_xt.hip read a packed table - they need the table's windows,
+        # for a layer they cover)
+        if not math and not limb3 and not _xrun_f32_usable(lib, nbr, w_taps):
             raise L.DetZeroHipError('spconv_forward: a packed neighbour table feeds the split-math kernels only')
     if math:
         # (split weights are padded to 32 output channels: the true count comes from the BatchNorm vector, or `cout=`)
         cin, cout = w_taps.shape[2], (int(cout) if cout is not None else scale.shape[0] if scale is not None else w_taps.shape[1])
+    elif limb3:
+        cin, cout = w_taps.shape[2] * 2 // 3, w_taps.shape[1]
     else:
         cin, cout = w_taps.shape[1], w_taps.shape[2]
     assert feats.shape[1] == cin, (feats.shape, w_taps.shape)
@@ -407,7 +436,11 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
     tiles = getattr(nbr, 'tiles', None) if (math and kvol >= 3) else None
     xwin = getattr(nbr, 'xwin', None) if (packed and cin == cout) else None
     def launch():
-        if xwin is not None and not math:
+        if limb3:
+            rc = lib.dz_spconv_forward_x_limb3(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
+                                               L.ptr(xwin[0]), xwin[1], cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift),
+                                               L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, L.stream())
+        elif xwin is not None and not math:
             rc = lib.dz_spconv_forward_x_f32(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
                                              L.ptr(xwin[0]), xwin[1], cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift),
                                              L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, L.stream())
@@ -443,7 +476,7 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         flops = 2.0 * pairs * cin * cout
         n_in = in_level.num_active() if in_level is not None else m
         nbytes = 4.0 * (n_in * cin + m * cout + kvol * cin * cout + (m * cout if residual is not None else 0)) + 8.0 * pairs
-        name = (lib.dz_spconv_x_f32_variant(cin, cout) if xwin is not None and not math else lib.dz_spconv_x_variant(cin, cout) if xwin is not None else lib.dz_spconv_tiles_variant(cin, cout) if tiles is not None else
+        name = (lib.dz_spconv_x_limb3_variant(cin, cout) if limb3 else lib.dz_spconv_x_f32_variant(cin, cout) if xwin is not None and not math else lib.dz_spconv_x_variant(cin, cout) if xwin is not None else lib.dz_spconv_tiles_variant(cin, cout) if tiles is not None else
                 lib.dz_spconv_variant_split(cin, cout) if math else lib.dz_spconv_variant(cin, cout))
         PROFILER.wrap(name.decode(), flops, nbytes, launch)
     return out

@@ -345,6 +345,23 @@ int dz_spconv_forward_x_f32(const float *in, int in_rows, int cin, const int *nb
                             const float *residual, int relu, float *out, int cout, void *stream);
 int dz_spconv_x_f32_window_rows(int cin, int cout);
 const char *dz_spconv_x_f32_variant(int cin, int cout);
+/* The x-run engine of the exact-fp32 mode on the bf16 matrix pipe (csrc/sparse_conv_xt.hip, opt-in): the same layers, the same
+ * index and the same fp32 rows as dz_spconv_forward_x_f32, every operand as three exact bf16 limbs (csrc/limb3.h) - the rows are
+ * split on chip, no tensor format changes.  w (27, cout, cin * 3 / 2) words: per tap, output channel and group of 8 input
+ * channels 16 bytes of h limbs, 16 of m, 16 of l (ops.pack_weight_limb3(w, cout_mult=32)).
+ *   Per product six v_mfma_f32_32x32x16_bf16 terms, smallest first (l.h, h.l, m.m, m.h, h.m, h.h), fp32 accumulation; the terms
+ *   m.l + l.m + l.l are dropped: at most 2^-26 of |x.w|.  Per output element the k-steps are accumulated in the order (tz,
+ *   16-channel chunk kc, ty, tx), the six terms of a k-step in the order above, whatever unit the row falls into and whether
+ *   the slab's window was staged or gathered: no atomics, launches agree bit for bit.
+ *   out = relu?((sum) * scale + shift (+ residual)); rows at or beyond *d_m_out are not written; the 16 queue words behind the
+ *   windows stay zero.  Refusals as dz_spconv_forward_x_f32.
+ *   dz_spconv_x_limb3_window_rows: rows of a z-slab window the kernel stages in LDS (longer windows run in gather mode), 0 = layer
+ *   not covered (the caller falls back to dz_spconv_forward_x_f32).  dz_spconv_x_limb3_variant: kernel instance name or "none". */
+int dz_spconv_forward_x_limb3(const float *in, int in_rows, int cin, const int *nbr_packed, const int *perm, int *windows, int tile_rows,
+                              int cap_out, const int *d_m_out, const float *w, const float *scale, const float *shift,
+                              const float *residual, int relu, float *out, int cout, void *stream);
+int dz_spconv_x_limb3_window_rows(int cin, int cout);
+const char *dz_spconv_x_limb3_variant(int cin, int cout);
 /* HeightCompression WITHOUT the dense image (round 5): idx (batch, h + 2 pad, w + 2 pad, 2) int32 = the feature row of every
  * (pixel, z slab) of a two-slab level, -1 = empty cell / border / rank >= feat_rows (overflowed capacity).  The first block of
  * BaseBEVBackbone reads the level's rows through it (dz_conv2d_desc.in_rowidx): height_compression.py:20-24 and the ZeroPad2d of
