@@ -231,15 +231,18 @@ def set_math(model, mode):
     return model
 
 
-def set_sparse_engine(model, engine, f32_engine=None):
+def set_sparse_engine(model, engine, f32_engine=None, f32_gather=None):
     """Convolution engine of the sparse backbone in the split math modes: 'xrun' (default: the gather kernels plus sparse_conv_x.hip
     for the submanifold convolutions of the 32 / 64 / 128-channel levels), 'gather' (sparse_conv_h.hip / sparse_conv_w.h only; both
     on rows in the canonical linear-key order) or 'tiles' (sparse_conv_t.hip: tile-resident inputs on rows in the brick order).
     f32_engine: the engine of the exact-fp32 mode, 'gather' (default: sparse_conv.hip) or 'xrun' (plus sparse_conv_xf.hip for the same
     submanifold convolutions, from the same index) or 'xrun_bf16x3' (the index of 'xrun'; those convolutions on the bf16 matrix pipe with
     three exact limbs per operand, sparse_conv_xt.hip, at the widths it covers and on sparse_conv_xf.hip at the others); None leaves it
-    as it is."""
-    model.backbone3d.set_engine(engine, f32_engine)
+    as it is.
+    f32_gather: the arithmetic of the exact-fp32 convolutions that stay on the gather path whatever f32_engine says (conv_input, conv1,
+    the strided layers, submanifold layers without x-run windows): 'mfma32' (default: sparse_conv.hip) or 'bf16x3' (three exact bf16
+    limbs per operand, sparse_conv_gt.hip, for the layers it covers); None leaves it as it is.  A refused call changes nothing."""
+    model.backbone3d.set_engine(engine, f32_engine, f32_gather)
     return model
 
 

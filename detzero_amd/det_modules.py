@@ -378,27 +378,37 @@ class VoxelResBackBone8x(_Cached):
         # of the 32 / 64 / 128-channel levels on sparse_conv_xf.hip, from the same packed tables + windows; everything else as 'gather')
         # or 'xrun_bf16x3' (as 'xrun', those layers on the bf16 matrix pipe with three exact limbs per operand: sparse_conv_xt.hip)
         self.f32_engine = os.environ.get('DZ_TUNE_SPCONV_F32_ENGINE', 'gather')
+        # ... and, orthogonal to it, the arithmetic of the exact-fp32 convolutions that stay on the gather path (conv_input, conv1, the
+        # strided layers, and every submanifold layer whose table has no x-run windows): 'mfma32' (default: k_spconv) or 'bf16x3' (three
+        # exact bf16 limbs per operand on the bf16 matrix pipe: sparse_conv_gt.hip, for the layers dz_spconv_limb3_tile_rows covers)
+        self.f32_gather = os.environ.get('DZ_TUNE_SPCONV_F32_GATHER', 'mfma32')
         # output widths whose convolutions run on the tile engine when it is selected (the others keep the gather kernels)
         self.tile_couts = tuple(int(c) for c in os.environ.get('DZ_TUNE_SPCONV_TILE_COUTS', '16,32,64,128').split(',') if c)
         self.backbone_channels = {'x_conv1': channels[0], 'x_conv2': channels[1], 'x_conv3': channels[2],
                                   'x_conv4': channels[3]}
         self.channels = channels
 
-    def set_engine(self, engine, f32_engine=None):
+    def set_engine(self, engine, f32_engine=None, f32_gather=None):
         """'gather' (rows in the canonical linear-key order), 'xrun' (gather + the z-slab window kernel for the submanifold
         convolutions of the 32 / 64 / 128-channel levels; same row order) or 'tiles' (tile-resident convolution; rows in brick order).
         f32_engine (None = unchanged): the engine of the exact-fp32 mode, 'gather', 'xrun' or 'xrun_bf16x3' (the tables of 'xrun'; the
-        submanifold layers on the three-limb kernel of sparse_conv_xt.hip where it covers the width, on sparse_conv_xf.hip otherwise)."""
+        submanifold layers on the three-limb kernel of sparse_conv_xt.hip where it covers the width, on sparse_conv_xf.hip otherwise).
+        f32_gather (None = unchanged): the arithmetic of the exact-fp32 mode's gather-path convolutions, 'mfma32' or 'bf16x3'
+        (sparse_conv_gt.hip).  A refused call changes nothing."""
         if engine not in ('gather', 'tiles', 'xrun'):
             raise DetZeroHipError('unknown sparse engine %r (gather | xrun | tiles)' % (engine,))
         if f32_engine is not None and f32_engine not in ops.SPARSE_F32_ENGINES:
             raise DetZeroHipError('unknown fp32 sparse engine %r (%s)' % (f32_engine, ' | '.join(ops.SPARSE_F32_ENGINES)))
+        if f32_gather is not None and f32_gather not in ops.SPARSE_F32_GATHER_ENGINES:
+            raise DetZeroHipError('unknown fp32 gather arithmetic %r (%s)' % (f32_gather, ' | '.join(ops.SPARSE_F32_GATHER_ENGINES)))
         if engine == 'tiles' and ops.L.load().dz_spconv_tile_rows() == 0:
             raise DetZeroHipError("sparse engine 'tiles' is an experimental build option (measured slower, DESIGN.md 2d): rebuild the library "
                                   'with DZ_BUILD_EXPERIMENTAL=1 (python -m detzero_amd.build --force)')
         self.engine = engine
         if f32_engine is not None:
             self.f32_engine = f32_engine
+        if f32_gather is not None:
+            self.f32_gather = f32_gather
         self.layout = ops.LAYOUT_BRICK if engine == 'tiles' else ops.LAYOUT_LINEAR
 
     # ---- kernel-layout parameters -------------------------------------------------------------
@@ -438,6 +448,11 @@ class VoxelResBackBone8x(_Cached):
         y = self._audit('%s.conv1' % name, stage, ops.spconv_forward(x, nbr, level, *p1, None, True, math=self.math, **kw1), level, e)
         return self._audit('%s.conv2' % name, stage, ops.spconv_forward(y, nbr, level, *p2, x, True, math=self.math, **kw2), level, e)
 
+    def _conv(self, x, nbr, level, entry, e_in, e_out, **kw):
+        """A convolution of the gather path without residual (conv_input, the down-convolutions, conv_out)."""
+        params, more = self._gather_p(entry, nbr, self._p(entry, e_in, e_out), x.shape[0])
+        return ops.spconv_forward(x, nbr, level, *params, None, True, math=self.math, **kw, **more)
+
     def _sub_p(self, entry, nbr, e):
         """((weights, scale, shift), further keywords of ops.spconv_forward) of a submanifold convolution over table `nbr`: `_p`'s and
         none (the call is the one made without this engine), except in f32 mode with the fp32 engine 'xrun_bf16x3' on a table with x-run
@@ -445,13 +460,31 @@ class VoxelResBackBone8x(_Cached):
         and the keyword names the engine.  A width it does not cover stays on k_spconv_xf."""
         w, scale, shift = self._p(entry, e, e)
         if self.math or self.f32_engine != 'xrun_bf16x3' or getattr(nbr, 'xwin', None) is None:
-            return (w, scale, shift), {}
+            return self._gather_p(entry, nbr, (w, scale, shift))
         cin, cout = int(w.shape[1]), int(w.shape[2])
         if cin != cout or ops.L.load().dz_spconv_x_limb3_window_rows(cin, cout) == 0:
-            return (w, scale, shift), {}
+            return self._gather_p(entry, nbr, (w, scale, shift))
         if 'w_xlimb3' not in entry:
             entry['w_xlimb3'] = ops.pack_weight_limb3(entry['w'], cout_mult=32)
         return (entry['w_xlimb3'], scale, shift), {'f32_engine': 'xrun_bf16x3'}
+
+    def _gather_p(self, entry, nbr, params, in_rows=0):
+        """(`params`, further keywords of ops.spconv_forward) of a convolution that runs on the gather path over table `nbr`: `params`
+        ((weights, scale, shift) of `_p`) and none, except in f32 mode with the gather arithmetic 'bf16x3' on a plain table with tile
+        masks and a layer k_spconv_gt covers, all inside the 2 GiB buffer window - then the weights are the entry's limb form (packed
+        once, cached in the plan entry: the layout of `_sub_p`'s, one copy serves both kernels) and the keywords name the arithmetic and
+        the true output width.  Anything else keeps the call made without it."""
+        if self.math or getattr(self, 'f32_gather', 'mfma32') != 'bf16x3' or getattr(nbr, 'packed', False) or getattr(nbr, 'tile_masks', None) is None:
+            return params, {}
+        w, scale, shift = params
+        cin, cout = int(w.shape[1]), int(w.shape[2])
+        limit = 1 << 31
+        if (ops.L.load().dz_spconv_limb3_tile_rows(cin, cout) == 0 or nbr.numel() * 4 >= limit or nbr.shape[1] * cout * 4 >= limit
+                or int(in_rows) * cin * 4 >= limit):
+            return params, {}
+        if 'w_xlimb3' not in entry:
+            entry['w_xlimb3'] = ops.pack_weight_limb3(entry['w'], cout_mult=32)
+        return (entry['w_xlimb3'], scale, shift), {'f32_gather': 'bf16x3', 'cout': cout}
 
     def build_pyramid(self, voxel_features, voxel_coords, batch_size, d_n=None, overlap=True, side_key=0, caps=None, level1=None,
                       staggered=False, exact=False):
@@ -592,7 +625,7 @@ class VoxelResBackBone8x(_Cached):
         ready(ev)
         ci = p['conv_input']
         e = self._e('x_conv1')                                # (the voxel features themselves are stored unscaled)
-        x = self._audit('conv_input', 'x_conv1', ops.spconv_forward(x, nbr, lvl1, *self._p(ci, 0, e), None, True, math=mm), lvl1, e)
+        x = self._audit('conv_input', 'x_conv1', self._conv(x, nbr, lvl1, ci, 0, e), lvl1, e)
         for bi, bp in enumerate(p['conv1']):
             x = self._res_block(x, nbr, lvl1, bp, e, 'conv1.%d' % bi, 'x_conv1')
         lvl1.act_exp = e
@@ -606,7 +639,7 @@ class VoxelResBackBone8x(_Cached):
             ready(ev)
             e_prev, e = e, self._e('x_conv%d' % (i + 2))
             stage = 'x_conv%d' % (i + 2)
-            x = self._audit('%s.0' % name, stage, ops.spconv_forward(x, nbr_d, nxt, *self._p(dp, e_prev, e), None, True, in_level=level, math=mm), nxt, e)
+            x = self._audit('%s.0' % name, stage, self._conv(x, nbr_d, nxt, dp, e_prev, e, in_level=level), nxt, e)
             for bi, bp in enumerate(p[name]['blocks']):
                 x = self._res_block(x, nbr, nxt, bp, e, '%s.%d' % (name, bi + 1), stage)
             nxt.act_exp = e
@@ -616,7 +649,7 @@ class VoxelResBackBone8x(_Cached):
         nbr_d, _, nxt, ev = steps[4]
         ready(ev)
         e_prev, e = e, self._e('encoded')
-        x = self._audit('conv_out', 'encoded', ops.spconv_forward(x, nbr_d, nxt, *self._p(dp, e_prev, e), None, True, in_level=level, math=mm), nxt, e)
+        x = self._audit('conv_out', 'encoded', self._conv(x, nbr_d, nxt, dp, e_prev, e, in_level=level), nxt, e)
         nxt.act_exp = e
         out['encoded'] = (x, nxt)
         return out

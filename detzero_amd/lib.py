@@ -135,6 +135,10 @@ _SIGS = {
                                           c_void_p, c_int, c_void_p, c_int, c_void_p]),
     'dz_spconv_x_limb3_window_rows': (c_int, [c_int, c_int]),
     'dz_spconv_x_limb3_variant': (ctypes.c_char_p, [c_int, c_int]),
+    'dz_spconv_forward_limb3': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'dz_spconv_limb3_tile_rows': (c_int, [c_int, c_int]),
+    'dz_spconv_limb3_variant': (ctypes.c_char_p, [c_int, c_int]),
     'dz_bev_tile_list_words': (c_size_t, [c_int, c_int, c_int]),
     'dz_bev_tile_list': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'dz_bev_fill_empty_tiles': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

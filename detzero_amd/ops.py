@@ -376,6 +376,9 @@ def gather_rows(src, idx, d_n, n_cap):
 # engines of the sparse backbone's exact-fp32 mode (Backbone3d.set_engine): the gather kernel everywhere; + k_spconv_xf for the submanifold
 # convolutions of the 32 / 64 / 128-channel levels; + k_spconv_xt (three bf16 limbs per operand) for those it covers, k_spconv_xf otherwise
 SPARSE_F32_ENGINES = ('gather', 'xrun', 'xrun_bf16x3')
+# ... and, orthogonal to it, the arithmetic of the convolutions that STAY on the gather path (Backbone3d.set_engine(f32_gather=)):
+# 'mfma32' = k_spconv (sparse_conv.hip, fp32 MFMA); 'bf16x3' = k_spconv_gt (sparse_conv_gt.hip, three exact bf16 limbs per operand)
+SPARSE_F32_GATHER_ENGINES = ('mfma32', 'bf16x3')
 
 
 def _xrun_f32_usable(lib, nbr, w_taps):
@@ -398,21 +401,34 @@ def _xrun_limb3_usable(lib, nbr, w_limb):
 
 
 def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None,
-                   f32_engine=None):
+                   f32_engine=None, f32_gather=None):
     """feats (m_in,cin); nbr (kvol,cap); returns (cap,cout).
     math == 0: fp32 rows, w_taps (kvol,cin,cout) fp32; a packed table with x-run windows (neighbors_xrun / build_windows) runs a
     cin == cout layer of 32 / 64 / 128 channels on the exact-fp32 x-run kernel (dz_spconv_forward_x_f32).
     f32_engine (math 0 only; the split modes ignore it): None or 'xrun' = the above; 'xrun_bf16x3' = the same table and rows on the
     three-limb kernel of csrc/sparse_conv_xt.hip (dz_spconv_forward_x_limb3), `w_taps` in the pack_weight_limb3(w, cout_mult=32)
     layout; a layer or table that kernel does not cover is an error.
+    f32_gather (math 0 only; the split modes ignore it): None or 'mfma32' = dz_spconv_forward on a plain table; 'bf16x3' = the same
+    table and rows on the three-limb gather kernel of csrc/sparse_conv_gt.hip (dz_spconv_forward_limb3), `w_taps` in the
+    pack_weight_limb3(w, cout_mult=32) layout (kvol, cout_pad, cin * 3 / 2) and `cout=` the true width where it is below 32 (default:
+    the BatchNorm vector's, else the weights'); a packed table or a layer the library does not cover is an error.
     math != 0: pair16 rows (in, residual, out), w_taps (kvol,cout_pad,cin) pair16 from pack_weight_split."""
     lib = L.load()
     L.require_cuda(feats, nbr, w_taps, scale, shift, residual)
     if f32_engine not in (None,) + SPARSE_F32_ENGINES:
         raise L.DetZeroHipError('unknown fp32 sparse engine %r (%s)' % (f32_engine, ' | '.join(SPARSE_F32_ENGINES)))
+    if f32_gather not in (None,) + SPARSE_F32_GATHER_ENGINES:
+        raise L.DetZeroHipError('unknown fp32 gather arithmetic %r (%s)' % (f32_gather, ' | '.join(SPARSE_F32_GATHER_ENGINES)))
     limb3 = f32_engine == 'xrun_bf16x3' and not math
+    glimb3 = f32_gather == 'bf16x3' and not math and not limb3
     kvol, cap = nbr.shape
     packed = getattr(nbr, 'packed', False)
+    if glimb3:
+        if packed:
+            raise L.DetZeroHipError("spconv_forward: fp32 gather arithmetic 'bf16x3' reads a plain (kvol, cap) table, not a packed one")
+        if getattr(nbr, 'tile_masks', None) is None or w_taps.dim() != 3 or w_taps.shape[0] != kvol or w_taps.shape[2] % 12 != 0:
+            raise L.DetZeroHipError("spconv_forward: fp32 gather arithmetic 'bf16x3' needs a plain table with tile masks and the "
+                                    '(kvol, cout_pad, cin * 3 / 2) limb weights of the layer')
     if limb3 and not (packed and _xrun_limb3_usable(lib, nbr, w_taps)):
         raise L.DetZeroHipError("spconv_forward: fp32 engine 'xrun_bf16x3' needs a packed table with x-run windows and the limb weights "
                                 'of a 32 / 64 / 128-channel cin == cout layer the kernel covers')
@@ -427,6 +443,12 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         cin, cout = w_taps.shape[2], (int(cout) if cout is not None else scale.shape[0] if scale is not None else w_taps.shape[1])
     elif limb3:
         cin, cout = w_taps.shape[2] * 2 // 3, w_taps.shape[1]
+    elif glimb3:
+        # (limb weights are padded to 32 output channels: the true count comes from `cout=` or the BatchNorm vector)
+        cin, cout = w_taps.shape[2] * 2 // 3, (int(cout) if cout is not None else scale.shape[0] if scale is not None else w_taps.shape[1])
+        if lib.dz_spconv_limb3_tile_rows(cin, cout) == 0 or w_taps.shape[1] != max(cout, 32):
+            raise L.DetZeroHipError("spconv_forward: fp32 gather arithmetic 'bf16x3' does not cover a %d -> %d layer with %d weight rows"
+                                    % (cin, cout, w_taps.shape[1]))
     else:
         cin, cout = w_taps.shape[1], w_taps.shape[2]
     assert feats.shape[1] == cin, (feats.shape, w_taps.shape)
@@ -440,6 +462,10 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
             rc = lib.dz_spconv_forward_x_limb3(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
                                                L.ptr(xwin[0]), xwin[1], cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift),
                                                L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, L.stream())
+        elif glimb3:
+            rc = lib.dz_spconv_forward_limb3(L.ptr(feats), feats.shape[0], cin, L.ptr(nbr), L.ptr(nbr.tile_masks), kvol, cap, L.ptr(out_level.d_m),
+                                             L.ptr(w_taps), L.ptr(scale), L.ptr(shift), L.ptr(residual), 1 if relu else 0, L.ptr(out), cout,
+                                             L.stream())
         elif xwin is not None and not math:
             rc = lib.dz_spconv_forward_x_f32(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
                                              L.ptr(xwin[0]), xwin[1], cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift),
@@ -476,7 +502,7 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         flops = 2.0 * pairs * cin * cout
         n_in = in_level.num_active() if in_level is not None else m
         nbytes = 4.0 * (n_in * cin + m * cout + kvol * cin * cout + (m * cout if residual is not None else 0)) + 8.0 * pairs
-        name = (lib.dz_spconv_x_limb3_variant(cin, cout) if limb3 else lib.dz_spconv_x_f32_variant(cin, cout) if xwin is not None and not math else lib.dz_spconv_x_variant(cin, cout) if xwin is not None else lib.dz_spconv_tiles_variant(cin, cout) if tiles is not None else
+        name = (lib.dz_spconv_x_limb3_variant(cin, cout) if limb3 else lib.dz_spconv_limb3_variant(cin, cout) if glimb3 else lib.dz_spconv_x_f32_variant(cin, cout) if xwin is not None and not math else lib.dz_spconv_x_variant(cin, cout) if xwin is not None else lib.dz_spconv_tiles_variant(cin, cout) if tiles is not None else
                 lib.dz_spconv_variant_split(cin, cout) if math else lib.dz_spconv_variant(cin, cout))
         PROFILER.wrap(name.decode(), flops, nbytes, launch)
     return out

@@ -362,6 +362,28 @@ int dz_spconv_forward_x_limb3(const float *in, int in_rows, int cin, const int *
                               const float *residual, int relu, float *out, int cout, void *stream);
 int dz_spconv_x_limb3_window_rows(int cin, int cout);
 const char *dz_spconv_x_limb3_variant(int cin, int cout);
+/* The gather-path sparse convolution of the exact-fp32 mode on the bf16 matrix pipe (csrc/sparse_conv_gt.hip, opt-in): the layers,
+ * the plain (kvol, cap_out) table with its 32-row tile masks (dz_build_neighbors) and the fp32 rows of dz_spconv_forward, every
+ * operand as three exact bf16 limbs (csrc/limb3.h) - the gathered rows are split on chip on their way into LDS, no tensor format
+ * changes.  Channels 16 -> 16, 16 -> 32, 32 -> 32, 32 -> 64, 64 -> 64, 64 -> 128, 128 -> 128; kvol 1..27.
+ *   w_limb (kvol, cout_pad, cin * 3 / 2) words, cout_pad = max(cout, 32) (a 16-channel output is padded with zero rows, stores
+ *   are masked to cout): per tap, output channel and group of 8 input channels 16 bytes of h limbs, 16 of m, 16 of l
+ *   (ops.pack_weight_limb3(w, cout_mult=32)).
+ *   Per product six v_mfma_f32_32x32x16_bf16 terms, smallest first (l.h, h.l, m.m, m.h, h.m, h.h), fp32 accumulation; the terms
+ *   m.l + l.m + l.l are dropped: at most 2^-26 of |x.w|.  Per output element: channel slice ascending, live taps ascending,
+ *   16-channel k-step ascending, whatever tile the row falls into: no atomics, launches agree bit for bit.
+ *   out = relu?((sum) * scale + shift (+ residual)); scale, shift, residual may be NULL.  Rows below m = min(*d_m_out, cap_out)
+ *   are fully written, rows at or beyond m and anything behind cap_out are not touched; missing neighbours and rows beyond m
+ *   fetch nothing.
+ *   Refused before any launch: null pointers (tile_masks included) and kvol outside 1..27 (DZ_ERR_INVALID), channels the selector
+ *   does not cover, and an input, output or table of 2 GiB or more (DZ_ERR_UNSUPPORTED).
+ *   dz_spconv_limb3_tile_rows: the row tile of the layer's instance, 0 = not covered (the caller keeps dz_spconv_forward).
+ *   dz_spconv_limb3_variant: kernel instance name or "none". */
+int dz_spconv_forward_limb3(const float *in, int in_rows, int cin, const int *nbr, const uint32_t *tile_masks, int kvol, int cap_out,
+                            const int *d_m_out, const float *w_limb, const float *scale, const float *shift, const float *residual,
+                            int relu, float *out, int cout, void *stream);
+int dz_spconv_limb3_tile_rows(int cin, int cout);
+const char *dz_spconv_limb3_variant(int cin, int cout);
 /* HeightCompression WITHOUT the dense image (round 5): idx (batch, h + 2 pad, w + 2 pad, 2) int32 = the feature row of every
  * (pixel, z slab) of a two-slab level, -1 = empty cell / border / rank >= feat_rows (overflowed capacity).  The first block of
  * BaseBEVBackbone reads the level's rows through it (dz_conv2d_desc.in_rowidx): height_compression.py:20-24 and the ZeroPad2d of
