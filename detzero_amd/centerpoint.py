@@ -835,7 +835,13 @@ class CapturedPass:
     """FramePipeline over a static input as ONE captured graph; with ways > 1 the concurrent sub-passes are parallel branches of it
     (each on its own stream, without forks of its own: see `_call_split`).  Measured on one box against ways = 1 (profiles/
     r06_ab_notes.txt): +1.0 % frames/s at 32 frames per pass, +3.0 % at 16, +-0 at 8.  One graph PER sub-pass, replayed side by side
-    (which keeps the sub-passes' inner forks) was built first and is slower than no split at all in bench.py: -2.7 % / -4.5 % / -13 %."""
+    (which keeps the sub-passes' inner forks) was built first and is slower than no split at all in bench.py: -2.7 % / -4.5 % / -13 %.
+
+    The graph holds raw pointers into the plans of the model's modules (kernel-layout and packed weights, scale / shift vectors, the
+    zero-response images).  The pass keeps the plan objects of capture time (`plans`), so those tensors stay alive, and `replay()`
+    refuses with DetZeroHipError once a module has dropped its plan (load_state_dict, invalidate(), a device move): the weights
+    changed, capture again.  `stale()` tells without raising.  Math, pre-scale and engine switches after the capture do not drop a
+    plan: a replay then reproduces the configuration of CAPTURE time, not the model's current one."""
 
     def __init__(self, pipe, static_points):
         self.pipe = pipe
@@ -849,8 +855,16 @@ class CapturedPass:
             self.boxes.copy_(o.view(self.boxes.shape))
             self.counts.copy_(n.view(-1))
         self.branches = pipe.ways if pipe.splits(nb) else 1
+        self.plans = cp_modules.plan_snapshot(pipe.model)       # (strong references: what the graph points at lives as long as this pass)
+
+    def stale(self):
+        """True once a module of the model has dropped the plan this graph was captured on (identity of the plan objects: another
+        model's reload does not count)."""
+        return cp_modules.plans_changed(self.plans)
 
     def replay(self):
+        if self.stale():
+            raise DetZeroHipError('CapturedPass: weights changed since capture; capture again')
         self.graph.replay()
 
 
@@ -863,6 +877,10 @@ class StreamingDetector:
     batches in flight never share memory.  ``feed(frames)`` enqueues A(frames) and B(previous batch) and returns
     the previous batch's (boxes9 (B,K,9), counts (B,)) - device tensors that stay valid until the call after
     next - or None on the first call; ``flush()`` returns the last batch's.  Nothing here synchronises the host.
+
+    Each slot's graphs are bound to the plans of the model's modules as `CapturedPass` is: the slot keeps the plan objects of capture
+    time, and ``feed()`` / ``flush()`` raise DetZeroHipError before launching anything once a module has dropped its plan (``stale()``);
+    math, pre-scale and engine switches after construction leave the graphs at the configuration they were captured in.
     """
 
     def __init__(self, pipe, example_frames, use_graph=True, warmup=3):
@@ -877,7 +895,7 @@ class StreamingDetector:
         self.graph_note = 'hipGraph replay (stage A / stage B graphs, double buffered)' if use_graph else 'eager launches (two streams)'
         cur = torch.cuda.current_stream(dev)
         for k in range(2):
-            slot = {'in': [f.clone() for f in example_frames], 'ga': None, 'gb': None, 'prep': None, 'out': None,
+            slot = {'in': [f.clone() for f in example_frames], 'ga': None, 'gb': None, 'prep': None, 'out': None, 'plans': [],
                     'a_done': torch.cuda.Event(), 'b_done': torch.cuda.Event()}
             self.s_a.wait_stream(cur)
             with torch.cuda.stream(self.s_a):
@@ -897,6 +915,7 @@ class StreamingDetector:
                     ga.replay(); gb.replay()
                     torch.cuda.synchronize(dev)
                     slot['ga'], slot['gb'] = ga, gb
+                    slot['plans'] = cp_modules.plan_snapshot(pipe.model)
                 except Exception as e:  # capture is an optimisation, not a requirement
                     self.graph_note = 'eager launches, two streams (graph capture failed: %s)' % str(e).split('\n')[0][:100]
                     slot['ga'] = slot['gb'] = None
@@ -929,7 +948,16 @@ class StreamingDetector:
             slot['b_done'].record(self.s_b)
         return slot['out']
 
+    def stale(self):
+        """True once a module of the model has dropped the plan a slot's graphs were captured on (eager slots hold no pointers)."""
+        return any(slot['gb'] is not None and cp_modules.plans_changed(slot['plans']) for slot in self.slots)
+
+    def _check_fresh(self):
+        if self.stale():
+            raise DetZeroHipError('StreamingDetector: weights changed since capture; capture again (build a new StreamingDetector)')
+
     def feed(self, frames):
+        self._check_fresh()
         cur = torch.cuda.current_stream(self.dev)
         self.s_a.wait_stream(cur)                          # the caller's frames are ready
         self.s_b.wait_stream(cur)                          # ... and it has finished reading the results handed out before
@@ -944,6 +972,7 @@ class StreamingDetector:
     def flush(self):
         if self.n_fed == 0:
             return None
+        self._check_fresh()
         cur = torch.cuda.current_stream(self.dev)
         out = self._stage_b((self.n_fed - 1) & 1)
         cur.wait_stream(self.s_b)

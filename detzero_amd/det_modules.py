@@ -12,6 +12,7 @@ Internal data layout (differs from the reference on purpose):
   * dense activations: channel-last, zero-bordered images kept under private ``_nhwc_*`` keys of the
     batch_dict; the NCHW tensors the reference's keys promise are zero-copy permuted views.
 """
+import collections
 import contextlib
 import os
 from functools import partial
@@ -55,6 +56,71 @@ _FROM_ENTRY = object()
 CACHE_GEN = [0]
 
 
+class PinnedLRU:
+    """Host-side eviction policy of a small keyed cache: at most `bound` UNPINNED keys, the least recently USED one goes first (a hit
+    through `get` refreshes a key), `pin(key)` takes a key out of the eviction order for good - pinned keys are never evicted and do not
+    count against the bound.  The values live in `store` (a dict of the caller's, or one of its own) under the keys themselves; `put`
+    returns what it evicted, so that the caller decides when the values may be released."""
+
+    def __init__(self, bound=4, store=None):
+        self.bound = int(bound)
+        self.store = {} if store is None else store
+        self._order = collections.OrderedDict()     # unpinned keys, least recently used first
+        self._pinned = set()
+
+    def __contains__(self, key):
+        return key in self._order or key in self._pinned
+
+    def __len__(self):
+        return len(self._order) + len(self._pinned)
+
+    def unpinned(self):
+        return list(self._order)
+
+    def pinned(self):
+        return set(self._pinned)
+
+    def get(self, key, default=None):
+        if key in self._order:
+            self._order.move_to_end(key)
+        elif key not in self._pinned:
+            return default
+        return self.store[key]
+
+    def put(self, key, value):
+        """Insert (or replace) -> [(key, value), ...] of the entries evicted to make room: none or, beyond the bound, exactly one."""
+        self.store[key] = value
+        if key in self._pinned:
+            return []
+        self._order[key] = None
+        self._order.move_to_end(key)
+        out = []
+        while len(self._order) > self.bound:
+            old, _ = self._order.popitem(last=False)
+            out.append((old, self.store.pop(old)))
+        return out
+
+    def pin(self, key):
+        if key in self._pinned:
+            return
+        if key not in self._order:
+            raise KeyError(key)
+        del self._order[key]
+        self._pinned.add(key)
+
+
+def plan_snapshot(model):
+    """[(module, its plan object)] of every module of `model` that holds a built plan: what a captured graph's raw pointers (kernel-layout
+    and packed weights, folded scale / shift vectors, zero-response images) live in.  Keeping the list keeps those tensors alive."""
+    return [(mod, mod._plan) for mod in model.modules() if getattr(mod, '_plan', None) is not None]
+
+
+def plans_changed(snapshot):
+    """Whether any module of a `plan_snapshot` has since dropped or rebuilt its plan (load_state_dict, invalidate(), a device move).
+    Plan identity, not CACHE_GEN: the counter is global and moves with every model's switches."""
+    return any(getattr(mod, '_plan', None) is not plan for mod, plan in snapshot)
+
+
 class _Cached(nn.Module):
     """Modules that cache kernel-layout parameters; the cache is dropped when weights change."""
 
@@ -62,13 +128,22 @@ class _Cached(nn.Module):
         super().__init__()
         self._plan = None
         self.act_exp = None
+        self._prescale_stale = False        # True: weights were loaded after the exponents of act_exp were calibrated (`_e` then refuses)
         self.math = 0       # ops.MATH_MODES: 0 = fp32 MFMA, 1 = fp16-pair split, 2 = bf16-pair split, 3 = fp16 pairs with one product (csrc/hgemm.h)
         self.f32_dense_engine = 'mfma32'    # BaseBEVBackbone / CenterHead: set_dense_engine
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate())
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._weights_loaded())
 
     def invalidate(self):
         self._plan = None
         CACHE_GEN[0] += 1
+
+    def _weights_loaded(self):
+        """load_state_dict post-hook: the plan goes, and a pre-scale calibrated for the weights that were just replaced is marked stale.
+        It is NOT reset here: the modules of a detector each hold their own copy of the exponents, and a reset of the one module that
+        was loaded would leave producer and consumer off by 2^e.  A device move (`_apply`) keeps the values and does not mark it."""
+        if self.act_exp is not None:
+            self._prescale_stale = True
+        self.invalidate()
 
     def set_math(self, mode):
         if ops.math_id(mode) != self.math:
@@ -79,14 +154,23 @@ class _Cached(nn.Module):
     def set_prescale(self, exps):
         """Per-stage power-of-two pre-scale of the activations kept as fp16 pairs: exps = {stage name: e} (centerpoint.select_prescale)
         or None.  A tensor of stage g is stored as value * 2^e_g; the factor is folded, exactly, into the folded-BN scale / shift of
-        the layer that writes it (`_p`), so fp16 pairs keep their 22 bits whatever the checkpoint's activation range is."""
+        the layer that writes it (`_p`), so fp16 pairs keep their 22 bits whatever the checkpoint's activation range is.  The exponents
+        belong to the weights they were calibrated on: load_state_dict marks them stale, and setting them (or None) here clears the mark."""
         self.act_exp = {k: int(v) for k, v in exps.items()} if exps else None
+        self._prescale_stale = False
         CACHE_GEN[0] += 1
         return self
 
     def _e(self, name):
-        """Exponent of stage `name` in the active math mode (0 unless the tensors are fp16 pairs and a pre-scale is set)."""
-        if getattr(self, 'act_exp', None) is None or ops.storage_math(self.math) != 1:
+        """Exponent of stage `name` in the active math mode (0 unless the tensors are fp16 pairs and a pre-scale is set).  The only reader
+        of act_exp: in fp16-pair storage it refuses exponents that were calibrated for weights since replaced (pair16 clamps at 65504
+        without a sign of it); f32 and bf16 pairs take no pre-scale, so the calibration pass of a new select_math runs on a reloaded model."""
+        if ops.storage_math(self.math) != 1:
+            return 0
+        if getattr(self, '_prescale_stale', False):
+            raise DetZeroHipError('%s: the fp16-pair pre-scale %s was calibrated for weights that load_state_dict has since replaced - '
+                                  'run select_math (or set_prescale) again before an f16x2 pass' % (type(self).__name__, self.act_exp))
+        if getattr(self, 'act_exp', None) is None:
             return 0
         return int(self.act_exp.get(name, 0))
 
@@ -898,7 +982,12 @@ class BaseBEVBackbone(_Cached):
         kernels on nb0 all-zero frames: which kernel runs a layer depends on the launch's tile count, and the images must carry ITS bits."""
         e_in, e_mid = self._e('encoded'), self._e('spatial_features_2d')
         key = ('zero_resp', h, w, int(self.math), str(dev), int(nb0), e_in, e_mid)
-        if key not in lvl:
+        cache = lvl.get('_zero_resp_cache')
+        if cache is None:
+            cache = lvl['_zero_resp_cache'] = PinnedLRU(4, store=lvl)        # (the images stay under their keys in the plan entry itself)
+        users = lvl.setdefault('_zero_resp_streams', {})                     # key -> streams whose passes were handed the images
+        outs = cache.get(key)
+        if outs is None:
             ridx = torch.full((nb0, h + 2, w + 2, 2), -1, dtype=torch.int32, device=dev)
             rows = torch.zeros((8, rows_c), dtype=torch.float32, device=dev)
             outs = []
@@ -917,14 +1006,23 @@ class BaseBEVBackbone(_Cached):
                                    ksize=3, stride=1, in_off=0, out_cstride=cv['cout'], out_d=(1, 1), ho=xh, wo=xw, batch=nb0, math=self.math)
                     outs.append(y[:1].clone())
                     x, xc = y, cv['cout']
-            lvl[key] = outs
             # one entry = six (1, H+2, W+2, C) images (~110 MB at 188 x 188 x 128): ragged last groups and other batch sizes add keys -
-            # keep the four most recent
-            order = lvl.setdefault('_zero_resp_keys', [])
-            order.append(key)
-            while len(order) > 4:
-                lvl.pop(order.pop(0), None)
-        return lvl[key]
+            # four unpinned ones are kept, the least recently used goes (`PinnedLRU`)
+            for old_key, old_imgs in cache.put(key, outs):
+                # released here, with record_stream for every stream a pass was handed the images on (the concurrent sub-passes of
+                # FramePipeline run on their own streams and may still be reading them): the allocator reuses the blocks only once the
+                # work queued on those streams so far has finished
+                for st in users.pop(old_key, ()):
+                    for img in old_imgs:
+                        img.record_stream(st)
+                CACHE_GEN[0] += 1       # (a pass that needs the evicted key again rebuilds it: sub-passes one after the other, as for any cache)
+        if torch.cuda.is_current_stream_capturing():
+            # a captured graph records the images' addresses: the key stays for as long as the plan does (the graph's owner keeps the
+            # plan alive: centerpoint.CapturedPass)
+            cache.pin(key)
+        elif torch.device(dev).type == 'cuda':
+            users.setdefault(key, set()).add(torch.cuda.current_stream(dev))
+        return outs
 
     def _level_convs(self, li, lvl, x, xh, xw, xc, batch, dev, sparse_in=None, out_last=None):
         """The 3 x 3 convolutions of block li over `batch` frames -> (activation, H, W, C).  out_last: where the block's LAST
