@@ -1,10 +1,12 @@
 // Box ops next to the head post stage (gfx950): fused pair matrices of the tracker's association metrics (convex-hull
-// "union" area, 3-D IoU, 3-D GIoU) and axis-aligned NMS.
+// "union" area, 3-D IoU, 3-D GIoU), the same metrics on paired boxes, the refining models' recall table and axis-aligned NMS.
 //
 // Reference:
 //   utils/detzero_utils/ops/iou3d_nms/iou3d_nms_utils.py:74-151,173-187 (boxes_iou3d_gpu, boxes_giou3d_gpu, nms_normal_gpu)
 //   utils/detzero_utils/ops/iou3d_nms/src/iou3d_nms_kernel.cu:235-326,352-368 (box_union: see rect_hull_area), :433-491 (iou_normal)
 //   tracking/detzero_track/models/tracking_modules/data_association/distance.py:44-161 (the callers)
+//   refining/detzero_refine/models/geometry_refine_model.py:98-141, position_refine_model.py:100-133 (the recall records' per-track
+//   `boxes_iou3d_gpu(a, b).diag()` loops: k_paired_metric, k_track_recall_iou3d)
 //
 // Parity notes: fp32, the reference's operation order, FMA contraction disabled - the 3-D IoU is bit-identical to the torch
 // composition around dz_boxes_overlap_bev that it replaces, and the axis-aligned predicate (+, -, *, /, fmaxf, fminf only) is
@@ -27,6 +29,27 @@ __device__ __forceinline__ bool footprints_near(const float *A, const float *B) 
     return dx * dx + dy * dy <= reach * reach;
 }
 
+// One pair, the final value: the body shared by the matrix kernel and the paired kernels below, so that a paired result is
+// element (i, i) of the matrix bit for bit.  cp / ang = the thread's LDS columns (stride METRIC_THREADS).
+template <int METRIC>
+__device__ __forceinline__ float pair_metric(const float *A, const float *B, P2 *cp, float *ang) {
+    if (METRIC == DZ_BOXM_UNION_BEV) return rect_hull_area(A, B, cp, METRIC_THREADS);
+    // iou3d_nms_utils.py:86-105 / :122-150, operation for operation
+    const float a_max = A[2] + A[5] / 2, a_min = A[2] - A[5] / 2;
+    const float b_max = B[2] + B[5] / 2, b_min = B[2] - B[5] / 2;
+    const float bev = footprints_near(A, B) ? rect_overlap(A, B, cp, ang, METRIC_THREADS) : 0.f;
+    const float oh = fmaxf(fminf(a_max, b_max) - fmaxf(a_min, b_min), 0.f);
+    const float o3 = bev * oh;
+    const float va = (A[3] * A[4]) * A[5], vb = (B[3] * B[4]) * B[5];
+    const float u3 = fmaxf((va + vb) - o3, 1e-6f);
+    if (METRIC == DZ_BOXM_IOU3D) return o3 / u3;
+    // the reference's enclosing height is min(tops) - min(bottoms) (:139 `max_of_max = torch.min(...)`); EXACT = max(tops) - min(bottoms)
+    const float top = METRIC == DZ_BOXM_GIOU3D_EXACT ? fmaxf(a_max, b_max) : fminf(a_max, b_max);
+    const float uh = fmaxf(top - fminf(a_min, b_min), 0.f);
+    const float c3 = fmaxf(rect_hull_area(A, B, cp, METRIC_THREADS) * uh, 1e-6f);
+    return o3 / u3 - (c3 - u3) / c3;
+}
+
 // one thread per (i, j) pair, the final value in one pass
 template <int METRIC>
 __global__ __launch_bounds__(METRIC_THREADS) void k_pairwise_metric(const float *__restrict__ a, int na, const float *__restrict__ b, int nb,
@@ -41,27 +64,82 @@ __global__ __launch_bounds__(METRIC_THREADS) void k_pairwise_metric(const float 
         float A[7], B[7];
 #pragma unroll
         for (int q = 0; q < 7; ++q) { A[q] = a[i * 7 + q]; B[q] = b[j * 7 + q]; }
-        if (METRIC == DZ_BOXM_UNION_BEV) {
-            out[idx] = rect_hull_area(A, B, cp, METRIC_THREADS);
-            continue;
+        out[idx] = pair_metric<METRIC>(A, B, cp, ang_s + threadIdx.x);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// paired metric and the refiner's recall table
+// ------------------------------------------------------------------------------------------
+// out[i] = metric(a[i], b[i]): the diagonal of k_pairwise_metric without the matrix.  The refining models' recall records
+// (refining/detzero_refine/models/geometry_refine_model.py:114-122, position_refine_model.py:106-114) build a T x T matrix per
+// track and side and keep `.diag()`.
+template <int METRIC>
+__global__ __launch_bounds__(METRIC_THREADS) void k_paired_metric(const float *__restrict__ a, const float *__restrict__ b, int n,
+                                                                  float *__restrict__ out) {
+    __shared__ P2 cp_s[(METRIC == DZ_BOXM_UNION_BEV ? 9 : 16) * METRIC_THREADS];
+    __shared__ float ang_s[METRIC == DZ_BOXM_UNION_BEV ? 1 : 16 * METRIC_THREADS];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {      // n * 7 < 2^31 (entry point)
+        float A[7], B[7];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) { A[q] = a[i * 7 + q]; B[q] = b[i * 7 + q]; }
+        out[i] = pair_metric<METRIC>(A, B, cp_s + threadIdx.x, ang_s + threadIdx.x);
+    }
+}
+
+// Recall table of one batch of tracks in one launch: replaces the per-track loop of geometry_refine_model.py:98-141 and
+// position_refine_model.py:100-133 (two T x T boxes_iou3d_gpu matrices cut to their diagonals and five or more .item() per track).
+// One thread per (track, row); a group covers 128 rows of ONE track, so its counters belong to one line of `counts`
+// (batch, 2, n_thr + 1): [b][s][0] = counted rows, [b][s][1 + k] = counted rows with iou > thr[k]; s = 0 input side (in, gt),
+// s = 1 output side (out, gt).  Per counter a __ballot + popcount per wave, the two waves' words added through LDS, one
+// integer atomicAdd per (group, counter): integer adds commute, the table is the same on every run.  Rows outside the mask
+// or the track's length are never read as boxes; their iou_in / iou_out entries are 0.
+constexpr int RECALL_MAX_THR = 8;
+struct RecallThr { float v[RECALL_MAX_THR]; };
+
+__global__ __launch_bounds__(METRIC_THREADS) void k_track_recall_iou3d(const float *__restrict__ boxes_in, const float *__restrict__ boxes_out,
+                                                                       const float *__restrict__ boxes_gt, const unsigned char *__restrict__ mask,
+                                                                       const int *__restrict__ d_len, int t_cap, int groups_per_track,
+                                                                       RecallThr thr, int n_thr, float *__restrict__ iou_in,
+                                                                       float *__restrict__ iou_out, int *__restrict__ counts) {
+    __shared__ P2 cp_s[16 * METRIC_THREADS];
+    __shared__ float ang_s[16 * METRIC_THREADS];
+    __shared__ int wave_cnt[METRIC_THREADS / 64][2 * (RECALL_MAX_THR + 1)];
+    const int b = blockIdx.x / groups_per_track;
+    const int row = (blockIdx.x % groups_per_track) * METRIC_THREADS + threadIdx.x;
+    const int len = max(min(d_len[b], t_cap), 0);
+    const int at = b * t_cap + row;                       // batch * t_cap * 7 < 2^31 (entry point)
+    const bool counted = row < len && mask[at] != 0;
+    float v_in = 0.f, v_out = 0.f;
+    if (counted) {
+        float A[7], B[7], G[7];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) { A[q] = boxes_in[at * 7 + q]; B[q] = boxes_out[at * 7 + q]; G[q] = boxes_gt[at * 7 + q]; }
+        v_in = pair_metric<DZ_BOXM_IOU3D>(A, G, cp_s + threadIdx.x, ang_s + threadIdx.x);
+        v_out = pair_metric<DZ_BOXM_IOU3D>(B, G, cp_s + threadIdx.x, ang_s + threadIdx.x);
+    }
+    if (row < t_cap) {
+        if (iou_in) iou_in[at] = v_in;
+        if (iou_out) iou_out[at] = v_out;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per_side = n_thr + 1;
+    const int n_counted = __popcll(__ballot(counted));
+    if (lane == 0) { wave_cnt[wave][0] = n_counted; wave_cnt[wave][per_side] = n_counted; }
+#pragma unroll
+    for (int k = 0; k < RECALL_MAX_THR; ++k) {            // constant indices into thr.v after unrolling
+        if (k < n_thr) {                                  // (uniform)
+            const int c_in = __popcll(__ballot(counted && v_in > thr.v[k]));
+            const int c_out = __popcll(__ballot(counted && v_out > thr.v[k]));
+            if (lane == 0) { wave_cnt[wave][1 + k] = c_in; wave_cnt[wave][per_side + 1 + k] = c_out; }
         }
-        // iou3d_nms_utils.py:86-105 / :122-150, operation for operation
-        const float a_max = A[2] + A[5] / 2, a_min = A[2] - A[5] / 2;
-        const float b_max = B[2] + B[5] / 2, b_min = B[2] - B[5] / 2;
-        const float bev = footprints_near(A, B) ? rect_overlap(A, B, cp, ang_s + threadIdx.x, METRIC_THREADS) : 0.f;
-        const float oh = fmaxf(fminf(a_max, b_max) - fmaxf(a_min, b_min), 0.f);
-        const float o3 = bev * oh;
-        const float va = (A[3] * A[4]) * A[5], vb = (B[3] * B[4]) * B[5];
-        const float u3 = fmaxf((va + vb) - o3, 1e-6f);
-        if (METRIC == DZ_BOXM_IOU3D) {
-            out[idx] = o3 / u3;
-            continue;
-        }
-        // the reference's enclosing height is min(tops) - min(bottoms) (:139 `max_of_max = torch.min(...)`); EXACT = max(tops) - min(bottoms)
-        const float top = METRIC == DZ_BOXM_GIOU3D_EXACT ? fmaxf(a_max, b_max) : fminf(a_max, b_max);
-        const float uh = fmaxf(top - fminf(a_min, b_min), 0.f);
-        const float c3 = fmaxf(rect_hull_area(A, B, cp, METRIC_THREADS) * uh, 1e-6f);
-        out[idx] = o3 / u3 - (c3 - u3) / c3;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * per_side) {
+        int sum = 0;
+#pragma unroll
+        for (int w = 0; w < METRIC_THREADS / 64; ++w) sum += wave_cnt[w][threadIdx.x];
+        if (sum) atomicAdd(counts + b * 2 * per_side + threadIdx.x, sum);
     }
 }
 
@@ -121,6 +199,13 @@ static int launch_metric(const float *a, int na, const float *b, int nb, float *
     return DZ_OK;
 }
 
+template <int METRIC>
+static int launch_paired(const float *a, const float *b, int n, float *out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_paired_metric<METRIC>, dim3(stream_grid(n, METRIC_THREADS)), dim3(METRIC_THREADS), 0, stream, a, b, n, out);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
 }  // namespace dz
 
 using namespace dz;
@@ -142,6 +227,59 @@ int dz_boxes_pairwise_metric(const float *a, int na, const float *b, int nb, int
         case DZ_BOXM_GIOU3D: return launch_metric<DZ_BOXM_GIOU3D>(a, na, b, nb, out, stream);
         default: return launch_metric<DZ_BOXM_GIOU3D_EXACT>(a, na, b, nb, out, stream);
     }
+}
+
+int dz_boxes_paired_metric(const float *a, const float *b, int n, int metric, float *out, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(n >= 0, "dz_boxes_paired_metric: negative size");
+    if (metric < DZ_BOXM_UNION_BEV || metric > DZ_BOXM_GIOU3D_EXACT) {
+        set_error("dz_boxes_paired_metric: unknown metric %d", metric);
+        return DZ_ERR_UNSUPPORTED;
+    }
+    if ((long)n * 7 >= (1L << 31)) {
+        set_error("dz_boxes_paired_metric: %d boxes overflow 32-bit offsets", n);
+        return DZ_ERR_UNSUPPORTED;
+    }
+    if (n == 0) return DZ_OK;
+    DZ_CHECK_ARG(a && b && out, "dz_boxes_paired_metric: null pointer");
+    switch (metric) {
+        case DZ_BOXM_UNION_BEV: return launch_paired<DZ_BOXM_UNION_BEV>(a, b, n, out, stream);
+        case DZ_BOXM_IOU3D: return launch_paired<DZ_BOXM_IOU3D>(a, b, n, out, stream);
+        case DZ_BOXM_GIOU3D: return launch_paired<DZ_BOXM_GIOU3D>(a, b, n, out, stream);
+        default: return launch_paired<DZ_BOXM_GIOU3D_EXACT>(a, b, n, out, stream);
+    }
+}
+
+int dz_track_recall_iou3d(const float *boxes_in, const float *boxes_out, const float *boxes_gt, const unsigned char *mask, const int *d_len,
+                          int batch, int t_cap, const double *h_thresholds, int n_thr, float *iou_in, float *iou_out, int *counts,
+                          void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(batch >= 0 && t_cap >= 0, "dz_track_recall_iou3d: negative size");
+    if (n_thr < 1 || n_thr > RECALL_MAX_THR) {
+        set_error("dz_track_recall_iou3d: %d thresholds (1..%d)", n_thr, RECALL_MAX_THR);
+        return DZ_ERR_UNSUPPORTED;
+    }
+    if ((long)batch * t_cap * 7 >= (1L << 31)) {        // also bounds the grid and the table: groups <= batch * t_cap, 18 counters < 7 * 128 floats
+        set_error("dz_track_recall_iou3d: batch %d x t_cap %d overflows 32-bit offsets", batch, t_cap);
+        return DZ_ERR_UNSUPPORTED;
+    }
+    DZ_CHECK_ARG(h_thresholds, "dz_track_recall_iou3d: null thresholds");
+    if (batch == 0) return DZ_OK;
+    DZ_CHECK_ARG(counts, "dz_track_recall_iou3d: null counts");
+    if ((long)batch * 2 * (n_thr + 1) >= (1L << 31)) {
+        set_error("dz_track_recall_iou3d: batch %d overflows the count table's 32-bit offsets", batch);
+        return DZ_ERR_UNSUPPORTED;
+    }
+    const int rc = fill_u32(counts, 0u, (size_t)batch * 2 * (n_thr + 1), stream);
+    if (rc != DZ_OK || t_cap == 0) return rc;
+    DZ_CHECK_ARG(boxes_in && boxes_out && boxes_gt && mask && d_len, "dz_track_recall_iou3d: null pointer");
+    RecallThr thr = {};
+    for (int k = 0; k < n_thr; ++k) thr.v[k] = (float)h_thresholds[k];      // torch compares an fp32 tensor with a Python scalar in fp32
+    const int groups_per_track = ceil_div(t_cap, METRIC_THREADS);
+    hipLaunchKernelGGL(k_track_recall_iou3d, dim3((unsigned)batch * groups_per_track), dim3(METRIC_THREADS), 0, stream, boxes_in, boxes_out,
+                       boxes_gt, mask, d_len, t_cap, groups_per_track, thr, n_thr, iou_in, iou_out, counts);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
 }
 
 int dz_nms_normal_batched(const float *boxes, const int *d_n, int batch, int n_cap, float thresh, int post_max, int *keep,

@@ -24,6 +24,13 @@ def boxes_iou3d_gpu(boxes_a, boxes_b):
     return ops.boxes_pairwise_metric(boxes_a.float().contiguous(), boxes_b.float().contiguous(), ops.BOXM_IOU3D)
 
 
+def boxes_iou3d_paired_gpu(boxes_a, boxes_b):
+    """(N,7),(N,7) -> (N,): boxes_iou3d_gpu(boxes_a, boxes_b).diag() bit for bit, one thread per pair instead of the N x N matrix
+    (what the refining models' recall records take from it, geometry_refine_model.py:114-122, position_refine_model.py:106-114)."""
+    assert boxes_a.shape[1] == boxes_b.shape[1] == 7 and boxes_a.shape[0] == boxes_b.shape[0]
+    return ops.boxes_paired_metric(boxes_a.float().contiguous(), boxes_b.float().contiguous(), ops.BOXM_IOU3D)
+
+
 def boxes_giou3d_gpu(boxes_a, boxes_b, exact_height=False):
     """iou3d_nms_utils.py:110-151 as written: its enclosing height is min(tops) - min(bottoms) (:139), and the tracker's
     numbers depend on that.  exact_height=True takes max(tops) - min(bottoms), the textbook GIoU."""

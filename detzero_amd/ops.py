@@ -1123,6 +1123,41 @@ def boxes_pairwise_metric(a, b, metric):
     return out
 
 
+def boxes_paired_metric(a, b, metric):
+    """a, b (N,7) f32 -> (N,) f32, out[i] = metric(a[i], b[i]): the diagonal of boxes_pairwise_metric, bit for bit, without the matrix."""
+    lib = L.load()
+    L.require_cuda(a, b)
+    if a.shape != b.shape:
+        raise L.DetZeroHipError('boxes_paired_metric: %s against %s boxes' % (tuple(a.shape), tuple(b.shape)))
+    out = torch.empty((a.shape[0],), dtype=torch.float32, device=a.device)
+    rc = lib.dz_boxes_paired_metric(L.ptr(a), L.ptr(b), a.shape[0], int(metric), L.ptr(out), L.stream())
+    L.check(rc, 'dz_boxes_paired_metric')
+    return out
+
+
+def track_recall_iou3d_nosync(boxes_in, boxes_out, boxes_gt, mask, d_len, thresholds, want_iou=True):
+    """Recall table of a batch of tracks (dz_track_recall_iou3d): boxes_* (B,T,7) f32, mask (B,T) uint8, d_len (B,) int32 device
+    tensors, thresholds a host sequence of 1..8 numbers.  Returns (counts (B,2,n_thr+1) int32, iou_in, iou_out (B,T) f32 or None)
+    on the device, nothing synchronised."""
+    lib = L.load()
+    L.require_cuda(boxes_in, boxes_out, boxes_gt, mask, d_len)
+    b, t = boxes_in.shape[0], boxes_in.shape[1]
+    for x in (boxes_in, boxes_out, boxes_gt):
+        if tuple(x.shape) != (b, t, 7) or x.dtype != torch.float32:
+            raise L.DetZeroHipError('track_recall_iou3d: boxes must be (B,T,7) float32, got %s %s' % (tuple(x.shape), x.dtype))
+    if tuple(mask.shape) != (b, t) or mask.dtype != torch.uint8 or tuple(d_len.shape) != (b,) or d_len.dtype != torch.int32:
+        raise L.DetZeroHipError('track_recall_iou3d: mask must be (B,T) uint8 and d_len (B,) int32')
+    thr = (L.c_double * len(thresholds))(*[float(v) for v in thresholds])
+    dev = boxes_in.device
+    counts = torch.empty((b, 2, len(thresholds) + 1), dtype=torch.int32, device=dev)
+    iou_in = torch.empty((b, t), dtype=torch.float32, device=dev) if want_iou else None
+    iou_out = torch.empty((b, t), dtype=torch.float32, device=dev) if want_iou else None
+    rc = lib.dz_track_recall_iou3d(L.ptr(boxes_in), L.ptr(boxes_out), L.ptr(boxes_gt), L.ptr(mask), L.ptr(d_len), b, t, thr,
+                                   len(thresholds), L.ptr(iou_in), L.ptr(iou_out), L.ptr(counts), L.stream())
+    L.check(rc, 'dz_track_recall_iou3d')
+    return counts, iou_in, iou_out
+
+
 def nms_normal_nosync(boxes_sorted, d_n, thresh, post_max):
     """Axis-aligned NMS (heading ignored): boxes_sorted (n_cap,7) descending score; returns keep (n_cap,) i32, d_num_keep (1,) i32."""
     lib = L.load()

@@ -9,6 +9,13 @@ Putting THIS directory on ``PYTHONPATH`` (``python -m detzero_amd.shim`` prints 
 ``detzero_amd`` - the reference's ``test.py`` then runs unchanged on the HIP backend (``--workers 0``: frames are
 voxelized on the device, which forked DataLoader workers cannot own).  ``tensorboardX`` / ``easydict`` fall-backs live in
 ``_fallbacks`` and are appended at the END of ``sys.path`` by ``install()``, so real installations win.
+
+``refining/tools/test.py`` and its ``eval_utils.py`` import (test.py:11-19, eval_utils.py:8-12) the same utilities and
+
+    detzero_refine.datasets.build_dataloader, detzero_refine.models.{build_network, load_data_to_gpu}
+
+which resolve to ``detzero_amd.refine_dataset`` (test mode, not distributed: batches of tracks are turned into model inputs
+on the device, in-process) and ``detzero_amd.refine_models`` (GRM / PRM / CRM with their recall records).
 """
 import os
 import sys
@@ -18,7 +25,7 @@ FALLBACK_DIR = os.path.join(SHIM_DIR, '_fallbacks')
 
 
 def install():
-    """Make ``detzero_det`` / ``detzero_utils`` (and, if missing, ``tensorboardX`` / ``easydict``) importable in this process."""
+    """Make ``detzero_det`` / ``detzero_refine`` / ``detzero_utils`` (and, if missing, ``tensorboardX`` / ``easydict``) importable in this process."""
     root = os.path.dirname(os.path.dirname(SHIM_DIR))
     for p in (root, SHIM_DIR):
         if p not in sys.path:

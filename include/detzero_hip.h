@@ -560,6 +560,26 @@ int dz_boxes_iou_bev(const float *a, int na, const float *b, int nb, float *out,
 #define DZ_BOXM_GIOU3D 2
 #define DZ_BOXM_GIOU3D_EXACT 3
 int dz_boxes_pairwise_metric(const float *a, int na, const float *b, int nb, int metric, float *out, void *stream);
+/* The same metrics on PAIRED boxes: a, b (n,7) -> out (n,) f32, out[i] = metric(a[i], b[i]) - element (i, i) of
+ * dz_boxes_pairwise_metric's matrix bit for bit (one pair body serves both kernels), without the matrix.  n == 0 launches nothing.
+ * Any other `metric`, or n * 7 >= 2^31: DZ_ERR_UNSUPPORTED. */
+int dz_boxes_paired_metric(const float *a, const float *b, int n, int metric, float *out, void *stream);
+/* Recall table of the refining models' generate_recall_record (refining/detzero_refine/models/geometry_refine_model.py:98-141,
+ * position_refine_model.py:100-133) for a whole batch of tracks in one launch.
+ *   boxes_in / boxes_out / boxes_gt (batch, t_cap, 7) f32, padded; mask (batch, t_cap) uint8, 1 = matched pair, counted;
+ *   d_len (batch) int32 on the device: valid rows per track, clamped to 0..t_cap.  Rows with mask 0 or at / beyond d_len[b] are
+ *   never read as boxes.
+ *   h_thresholds: host array, 1 <= n_thr <= 8, each cast to f32 (as torch compares an fp32 tensor with a Python scalar).
+ *   iou_in / iou_out (batch, t_cap) f32, each optional (NULL): the paired DZ_BOXM_IOU3D of (in, gt) resp. (out, gt) on counted
+ *   rows, 0 on every other row.
+ *   counts (batch, 2, n_thr + 1) int32, zeroed here on `stream`: [b][s][0] = counted rows of track b, [b][s][1 + k] = counted
+ *   rows with iou > thresholds[k] (strictly, in fp32); s = 0 input side, s = 1 output side.  Integer adds only: the table is
+ *   the same on every run.
+ * DZ_ERR_UNSUPPORTED for n_thr outside 1..8 and batch * t_cap * 7 >= 2^31 (checked before any pointer is looked at);
+ * DZ_ERR_INVALID for null pointers and negative sizes. */
+int dz_track_recall_iou3d(const float *boxes_in, const float *boxes_out, const float *boxes_gt, const unsigned char *mask,
+                          const int *d_len, int batch, int t_cap, const double *h_thresholds, int n_thr, float *iou_in,
+                          float *iou_out, int *counts, void *stream);
 
 /* iou3d_nms_cuda.nms_normal_gpu (iou3d_nms.cpp + nms_normal_kernel / iou_normal iou3d_nms_kernel.cu:433-491): axis-aligned BEV
  * IoU, the heading ignored, greedy by score.  Arguments, limits (n_cap <= 4096) and workspace (dz_nms_workspace_bytes) of
