@@ -169,4 +169,36 @@ __device__ float rect_hull_area(const float *A, const float *B, P2 *stk, int ld)
     return fabsf(area) / 2.0f;
 }
 
+// ------------------------------------------------------------------------------------------
+// pair metrics
+// ------------------------------------------------------------------------------------------
+// true when the circumscribed circles of the two footprints are at most 5 cm apart (k_nms_mask's test): beyond that
+// rect_overlap finds no vertex (its corner test has a 1 cm margin) and returns exactly +0
+__device__ __forceinline__ bool footprints_near(const float *A, const float *B) {
+    const float dx = A[0] - B[0], dy = A[1] - B[1];
+    const float reach = sqrtf(0.25f * (A[3] * A[3] + A[4] * A[4])) + sqrtf(0.25f * (B[3] * B[3] + B[4] * B[4])) + 0.05f;
+    return dx * dx + dy * dy <= reach * reach;
+}
+
+// One pair, the final value of a DZ_BOXM_* metric: the one body of box_ops.hip's matrix and paired kernels and of track.hip's
+// affinity kernel, so that their results agree bit for bit.  cp / ang = the thread's LDS columns (stride ld).
+template <int METRIC>
+__device__ __forceinline__ float pair_metric_ld(const float *A, const float *B, P2 *cp, float *ang, int ld) {
+    if (METRIC == DZ_BOXM_UNION_BEV) return rect_hull_area(A, B, cp, ld);
+    // iou3d_nms_utils.py:86-105 / :122-150, operation for operation
+    const float a_max = A[2] + A[5] / 2, a_min = A[2] - A[5] / 2;
+    const float b_max = B[2] + B[5] / 2, b_min = B[2] - B[5] / 2;
+    const float bev = footprints_near(A, B) ? rect_overlap(A, B, cp, ang, ld) : 0.f;
+    const float oh = fmaxf(fminf(a_max, b_max) - fmaxf(a_min, b_min), 0.f);
+    const float o3 = bev * oh;
+    const float va = (A[3] * A[4]) * A[5], vb = (B[3] * B[4]) * B[5];
+    const float u3 = fmaxf((va + vb) - o3, 1e-6f);
+    if (METRIC == DZ_BOXM_IOU3D) return o3 / u3;
+    // the reference's enclosing height is min(tops) - min(bottoms) (:139 `max_of_max = torch.min(...)`); EXACT = max(tops) - min(bottoms)
+    const float top = METRIC == DZ_BOXM_GIOU3D_EXACT ? fmaxf(a_max, b_max) : fminf(a_max, b_max);
+    const float uh = fmaxf(top - fminf(a_min, b_min), 0.f);
+    const float c3 = fmaxf(rect_hull_area(A, B, cp, ld) * uh, 1e-6f);
+    return o3 / u3 - (c3 - u3) / c3;
+}
+
 }  // namespace dz

@@ -21,33 +21,11 @@ namespace dz {
 
 constexpr int METRIC_THREADS = 128;
 
-// true when the circumscribed circles of the two footprints are at most 5 cm apart (k_nms_mask's test): beyond that
-// rect_overlap finds no vertex (its corner test has a 1 cm margin) and returns exactly +0
-__device__ __forceinline__ bool footprints_near(const float *A, const float *B) {
-    const float dx = A[0] - B[0], dy = A[1] - B[1];
-    const float reach = sqrtf(0.25f * (A[3] * A[3] + A[4] * A[4])) + sqrtf(0.25f * (B[3] * B[3] + B[4] * B[4])) + 0.05f;
-    return dx * dx + dy * dy <= reach * reach;
-}
-
-// One pair, the final value: the body shared by the matrix kernel and the paired kernels below, so that a paired result is
-// element (i, i) of the matrix bit for bit.  cp / ang = the thread's LDS columns (stride METRIC_THREADS).
+// One pair, the final value (box_geom.h: pair_metric_ld, shared with track.hip's affinity kernel): the body shared by the matrix
+// kernel and the paired kernels below, so that a paired result is element (i, i) of the matrix bit for bit.
 template <int METRIC>
 __device__ __forceinline__ float pair_metric(const float *A, const float *B, P2 *cp, float *ang) {
-    if (METRIC == DZ_BOXM_UNION_BEV) return rect_hull_area(A, B, cp, METRIC_THREADS);
-    // iou3d_nms_utils.py:86-105 / :122-150, operation for operation
-    const float a_max = A[2] + A[5] / 2, a_min = A[2] - A[5] / 2;
-    const float b_max = B[2] + B[5] / 2, b_min = B[2] - B[5] / 2;
-    const float bev = footprints_near(A, B) ? rect_overlap(A, B, cp, ang, METRIC_THREADS) : 0.f;
-    const float oh = fmaxf(fminf(a_max, b_max) - fmaxf(a_min, b_min), 0.f);
-    const float o3 = bev * oh;
-    const float va = (A[3] * A[4]) * A[5], vb = (B[3] * B[4]) * B[5];
-    const float u3 = fmaxf((va + vb) - o3, 1e-6f);
-    if (METRIC == DZ_BOXM_IOU3D) return o3 / u3;
-    // the reference's enclosing height is min(tops) - min(bottoms) (:139 `max_of_max = torch.min(...)`); EXACT = max(tops) - min(bottoms)
-    const float top = METRIC == DZ_BOXM_GIOU3D_EXACT ? fmaxf(a_max, b_max) : fminf(a_max, b_max);
-    const float uh = fmaxf(top - fminf(a_min, b_min), 0.f);
-    const float c3 = fmaxf(rect_hull_area(A, B, cp, METRIC_THREADS) * uh, 1e-6f);
-    return o3 / u3 - (c3 - u3) / c3;
+    return pair_metric_ld<METRIC>(A, B, cp, ang, METRIC_THREADS);
 }
 
 // one thread per (i, j) pair, the final value in one pass

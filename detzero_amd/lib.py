@@ -44,6 +44,13 @@ class Conv2dDesc(ctypes.Structure):
     ]
 
 
+class TrackTable(ctypes.Structure):
+    """Mirror of ``dz_track_table`` (include/detzero_hip.h)."""
+    _fields_ = [(k, c_void_p) for k in ('x', 'P', 'Q', 'dt', 'box', 'cls', 'score', 'update_score', 'num_points', 'hit', 'miss', 'id')] + [('cap', c_int)]
+
+
+_TT = ctypes.POINTER(TrackTable)
+
 # name -> (restype, argtypes); must list every symbol of include/detzero_hip.h (tests check this)
 _SIGS = {
     'dz_version': (ctypes.c_char_p, []),
@@ -230,6 +237,15 @@ _SIGS = {
     'dz_rows_all_zero': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'dz_add_layernorm_combine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'dz_add_layernorm': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    'dz_track_predict': (c_int, [_TT, c_int, c_int, c_void_p]),
+    'dz_track_affinity': (c_int, [_TT, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                  c_void_p, c_void_p]),
+    'dz_track_update': (c_int, [_TT, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
+    'dz_track_spawn': (c_int, [_TT, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p]),
+    'dz_track_merge_workspace_bytes': (c_size_t, [c_int]),
+    'dz_track_merge': (c_int, [_TT, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dz_track_compact': (c_int, [_TT, c_int, c_void_p, c_int, _TT, c_void_p, c_void_p]),
+    'dz_track_log': (c_int, [_TT, c_int, c_int, c_void_p, ctypes.c_long, c_void_p]),
 }
 
 _lib = None

@@ -1315,6 +1315,134 @@ class LaunchProfiler:
         return agg
 
 
+# ------------------------------------------------------------------------------------------------
+# tracker (csrc/track.hip): a device-resident track table of one sequence and the seven per-frame ops on it
+# ------------------------------------------------------------------------------------------------
+TRACK_ROW_WORDS = 16                 # include/detzero_hip.h: DZ_TRACK_ROW_WORDS
+TRACK_AFF_IOU_BEV = 16               # DZ_TRACK_AFF_IOU_BEV; the other two affinity metrics are BOXM_IOU3D / BOXM_GIOU3D
+TRACK_MAX_CLASSES = 8
+_TRACK_FIELDS = (('x', 5, torch.float32), ('P', 25, torch.float32), ('Q', 25, torch.float32), ('dt', 1, torch.float32),
+                 ('box', 9, torch.float32), ('cls', 1, torch.int32), ('score', 1, torch.float32), ('update_score', 1, torch.float32),
+                 ('num_points', 1, torch.int32), ('hit', 1, torch.int32), ('miss', 1, torch.int32), ('id', 1, torch.int32))
+
+
+class TrackTable:
+    """Struct of arrays of ``cap`` tracks on the device (``dz_track_table``); rows [0, n) are live, n is kept by the caller."""
+
+    def __init__(self, cap, device=None):
+        self.cap = int(cap)
+        self.device = torch.device(device) if device is not None else _dev()
+        self.arrays = {name: torch.zeros((self.cap, w) if w > 1 else (self.cap,), dtype=dt, device=self.device) for name, w, dt in _TRACK_FIELDS}
+        self.c = L.TrackTable(*[L.ptr(self.arrays[name]) for name, _, _ in _TRACK_FIELDS], self.cap)
+
+    def __getattr__(self, name):
+        try:
+            return self.__dict__['arrays'][name]
+        except KeyError:
+            raise AttributeError(name)
+
+    def grown(self, n, need):
+        """This table if ``need`` rows fit, else a new one of at least twice the capacity holding rows [0, n)."""
+        if need <= self.cap:
+            return self
+        cap = self.cap
+        while cap < need:
+            cap *= 2
+        new = TrackTable(cap, self.device)
+        for name in self.arrays:
+            new.arrays[name][:n].copy_(self.arrays[name][:n])
+        return new
+
+
+def _track_rows(buf, what):
+    if buf is None:
+        return None, 0
+    L.require_cuda(buf)
+    if buf.dtype != torch.int32 or buf.dim() != 2 or buf.shape[1] != TRACK_ROW_WORDS:
+        raise L.DetZeroHipError('%s: a row buffer is (rows, %d) int32, got %s %s' % (what, TRACK_ROW_WORDS, tuple(buf.shape), buf.dtype))
+    return buf, buf.shape[0]
+
+
+def _track_idx(idx, what):
+    L.require_cuda(idx)
+    if idx.dtype != torch.int32 or idx.dim() != 1:
+        raise L.DetZeroHipError('%s: an index list is a 1-d int32 device tensor' % what)
+    return idx
+
+
+def _track_thr(thr):
+    return (L.c_float * len(thr))(*[float(v) for v in thr])
+
+
+def track_predict_nosync(table, n, gate_class):
+    """KalmanFilter.predict on rows [0, n) in place; table.box[:n] are the predicted boxes."""
+    L.check(L.load().dz_track_predict(ctypes.byref(table.c), int(n), int(gate_class), L.stream()), 'dz_track_predict')
+
+
+def track_affinity_nosync(table, n, ext, row_idx, det, col_idx, metric, distinguish_class, thr):
+    """Cost matrix (len(row_idx), len(col_idx)) f32 of one association stage (dz_track_affinity)."""
+    ext, n_ext = _track_rows(ext, 'track_affinity')
+    det, n_det = _track_rows(det, 'track_affinity')
+    row_idx, col_idx = _track_idx(row_idx, 'track_affinity'), _track_idx(col_idx, 'track_affinity')
+    out = torch.empty((row_idx.shape[0], col_idx.shape[0]), dtype=torch.float32, device=row_idx.device)
+    rc = L.load().dz_track_affinity(ctypes.byref(table.c), int(n), L.ptr(ext), n_ext, L.ptr(row_idx), row_idx.shape[0], L.ptr(det), n_det,
+                                    L.ptr(col_idx), col_idx.shape[0], int(metric), int(bool(distinguish_class)), _track_thr(thr), len(thr),
+                                    L.ptr(out), L.stream())
+    L.check(rc, 'dz_track_affinity')
+    return out
+
+
+def track_update_nosync(table, n, det, match, r):
+    """KalmanFilter.update for match (m,3) int32 rows [table row, det row, stage]."""
+    det, n_det = _track_rows(det, 'track_update')
+    L.require_cuda(match)
+    if match.dtype != torch.int32 or match.dim() != 2 or match.shape[1] != 3:
+        raise L.DetZeroHipError('track_update: match is (m, 3) int32')
+    L.check(L.load().dz_track_update(ctypes.byref(table.c), int(n), L.ptr(det), n_det, L.ptr(match), match.shape[0], float(r), L.stream()),
+            'dz_track_update')
+
+
+def track_spawn_nosync(table, n, src, src_idx, ids, p, q, dt):
+    """Append len(src_idx) tracks at rows [n, n + m) from rows of the row buffer ``src``; p, q = the constructor's (p0, p1), (q0, q1)."""
+    src, n_src = _track_rows(src, 'track_spawn')
+    src_idx, ids = _track_idx(src_idx, 'track_spawn'), _track_idx(ids, 'track_spawn')
+    if ids.shape[0] != src_idx.shape[0] or n + src_idx.shape[0] > table.cap:
+        raise L.DetZeroHipError('track_spawn: %d ids for %d rows, %d + %d rows in a table of %d' % (ids.shape[0], src_idx.shape[0], n, src_idx.shape[0], table.cap))
+    rc = L.load().dz_track_spawn(ctypes.byref(table.c), int(n), L.ptr(src), n_src, L.ptr(src_idx), L.ptr(ids), src_idx.shape[0], float(p[0]),
+                                 float(p[1]), float(q[0]), float(q[1]), float(dt), L.stream())
+    L.check(rc, 'dz_track_spawn')
+
+
+def track_merge_nosync(table, n, thr):
+    """overlap_track_merge's verdicts: removed (n,) int32 0 / 1 on the device."""
+    lib = L.load()
+    removed = torch.empty((max(int(n), 1),), dtype=torch.int32, device=table.device)
+    ws = _ws(lib.dz_track_merge_workspace_bytes(int(n)))
+    rc = lib.dz_track_merge(ctypes.byref(table.c), int(n), _track_thr(thr), len(thr), L.ptr(removed), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, 'dz_track_merge')
+    return removed[:n]
+
+
+def track_compact_nosync(src, n, removed, death_age, dst):
+    """Stable removal into ``dst`` (another TrackTable); returns the new count as a (1,) int32 device tensor."""
+    if removed is not None:
+        L.require_cuda(removed)
+        if removed.dtype != torch.int32 or removed.shape[0] < n:
+            raise L.DetZeroHipError('track_compact: removed is (n,) int32')
+    d_count = torch.empty((1,), dtype=torch.int32, device=src.device)
+    rc = L.load().dz_track_compact(ctypes.byref(src.c), int(n), L.ptr(removed), int(death_age), ctypes.byref(dst.c), L.ptr(d_count), L.stream())
+    L.check(rc, 'dz_track_compact')
+    return d_count
+
+
+def track_log_nosync(table, n, frame, log, log_n):
+    """info() of rows [0, n) into rows [log_n, log_n + n) of the row buffer ``log``."""
+    log, rows = _track_rows(log, 'track_log')
+    if log_n + n > rows:
+        raise L.DetZeroHipError('track_log: rows %d..%d of a log of %d' % (log_n, log_n + n, rows))
+    L.check(L.load().dz_track_log(ctypes.byref(table.c), int(n), int(frame), L.ptr(log), int(log_n), L.stream()), 'dz_track_log')
+
+
 PROFILER = None
 
 

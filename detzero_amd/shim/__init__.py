@@ -16,6 +16,16 @@ voxelized on the device, which forked DataLoader workers cannot own).  ``tensorb
 
 which resolve to ``detzero_amd.refine_dataset`` (test mode, not distributed: batches of tracks are turned into model inputs
 on the device, in-process) and ``detzero_amd.refine_models`` (GRM / PRM / CRM with their recall records).
+
+``tracking/tools/run_track.py`` imports (run_track.py:8-12) ``detzero_utils.config_utils.log_cfg_info``,
+``detzero_utils.common_utils.get_log_info`` and
+
+    detzero_track.models.{build_model, run_model}, detzero_track.datasets.build_dataloader
+
+which resolve to ``detzero_amd.track_models`` (the tracker on a device-resident track table, one sequence after another in this
+process; ``--split test``).  ``detzero_track.utils.{data_utils, transform_utils}`` (daemon/combine_output.py:14-15) and
+``detzero_track.models.tracking_modules.data_association`` (``bev_overlap_gpu``, ``GNN_assignment``) resolve to
+``detzero_amd.track_adapter`` / ``detzero_amd.track_models``.
 """
 import os
 import sys
@@ -25,7 +35,7 @@ FALLBACK_DIR = os.path.join(SHIM_DIR, '_fallbacks')
 
 
 def install():
-    """Make ``detzero_det`` / ``detzero_refine`` / ``detzero_utils`` (and, if missing, ``tensorboardX`` / ``easydict``) importable in this process."""
+    """Make ``detzero_det`` / ``detzero_refine`` / ``detzero_track`` / ``detzero_utils`` (and, if missing, ``tensorboardX`` / ``easydict``) importable in this process."""
     root = os.path.dirname(os.path.dirname(SHIM_DIR))
     for p in (root, SHIM_DIR):
         if p not in sys.path:

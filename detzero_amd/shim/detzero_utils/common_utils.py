@@ -1,5 +1,6 @@
 """detzero_utils.common_utils - the names the reference's detection tools import (test.py:1-19, eval_utils.py:1-11:
-create_logger, set_random_seed, init_dist_pytorch, init_dist_slurm, get_dist_info, merge_results_dist, mask_points_by_range),
+create_logger, set_random_seed, init_dist_pytorch, init_dist_slurm, get_dist_info, merge_results_dist, mask_points_by_range) and
+its tracking tools (run_track.py:9, models/__init__.py:6: get_log_info, multi_processing),
 implemented for this backend: one process per GPU, backend "nccl" = RCCL on ROCm, and the per-rank result lists merged
 with a collective instead of the reference's pickle files + barriers (utils/detzero_utils/common_utils.py:119-140)."""
 import logging
@@ -86,3 +87,17 @@ def merge_results_dist(result_part, size, tmpdir):
     parts = [None] * world
     dist.all_gather_object(parts, result_part)
     return interleave_parts(parts, size) if rank == 0 else None
+
+
+def get_log_info(input_str, boundary='-', total_len=100, space_len=10):
+    """``input_str`` centred in a line of ``total_len`` characters: ``space_len`` blanks either side, ``boundary`` outside them."""
+    room = total_len - len(input_str)
+    space = 0 if room <= 0 else min(space_len, room // 2)
+    side = max(room // 2 - space, 0)
+    return boundary * side + ' ' * space + input_str + ' ' * space + boundary * side
+
+
+def multi_processing(function, data_dict, workers, bar=False):
+    """``[function(x) for x in data_dict]`` in this process.  The reference fans out over a process pool when ``workers`` > 1; here
+    the work runs on the GPU of this process and ``workers`` is accepted for the signature only."""
+    return [function(x) for x in data_dict]

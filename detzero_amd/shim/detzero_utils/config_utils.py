@@ -1,6 +1,6 @@
 """detzero_utils.config_utils - the global ``cfg`` and the three functions the reference's tools call (test.py:1-19):
 cfg_from_yaml_file (with ``_BASE_CONFIG_`` includes, resolved against the working directory because the reference's tools run
-from detection/tools), cfg_from_list (``KEY.SUB value`` overrides from the command line) and log_config_to_file."""
+from detection/tools), cfg_from_list (``KEY.SUB value`` overrides from the command line) and log_config_to_file; log_cfg_info for tracking/tools/run_track.py."""
 import ast
 
 import yaml
@@ -23,6 +23,16 @@ def _walk(node, prefix):
 def log_config_to_file(cfg, pre='cfg', logger=None):
     for path, val, section in _walk(cfg, pre):
         logger.info('\n%s = edict()' % path if section else '%s: %s' % (path, val))
+
+
+def log_cfg_info(cfg, cfg_str_list, logger):
+    """Every entry as ``KEY: value`` (a section as its bare name, then its entries), logged and appended to ``cfg_str_list``."""
+    for key, val in cfg.items():
+        line = '{:30}'.format(key) if isinstance(val, AttrDict) else '{:30}: {}'.format(key, val)
+        logger.info(line)
+        cfg_str_list.append(line)
+        if isinstance(val, AttrDict):
+            log_cfg_info(val, cfg_str_list, logger)
 
 
 def _parse(text):

@@ -170,3 +170,83 @@ def synth_object_track(seed, n_frames, name='Vehicle', pts_lo=0, pts_hi=600, ori
         pts.append(np.concatenate([xyz, np.tanh(rng.uniform(0, 3, size=(n, 1)))], axis=1))
     score = rng.uniform(0.05, 0.99, size=n_frames)
     return {'boxes_global': boxes, 'score': score, 'pts': pts, 'name': name}
+
+
+# ------------------------------------------------------------------------------------------------
+# tracker input
+# ------------------------------------------------------------------------------------------------
+TRACK_CLASSES = ['Vehicle', 'Pedestrian', 'Cyclist']
+TRACK_EVENTS = {
+    'missing': {1: [10, 11, 12]},          # object -> frames without a detection
+    'late': {2: (8, [5, 6, 7])},           # object -> (first confident frame, earlier frames with a low score)
+    'low': {3: [6, 14]},                   # object -> frames with a low score
+    'chain': {4: 0},                       # object -> frame with two more detections 1.8 m and 3.6 m along its axis (A-B-C)
+    'dup': {5: 9},                         # object -> frame with a second detection 0.5 m away
+    'false_pos': [(2, 1), (5, 2), (9, 3), (13, 4)],      # (first frame, frames alive)
+    'empty': [15],                         # frames without any detection
+}
+
+
+def synth_track_sequence(seed, n_frames=24, n_objects=20, origin=(3000.0, -2000.0, 40.0), events=None, sequence_name='synthetic'):
+    """One sequence of processed detection frames as the tracker takes them: ``{str(sample_idx): frame}`` with float32
+    ``boxes_global`` (N,7) in global coordinates around ``origin``, ``name``, ``score``, ``num_points`` and ``pose``.  Objects sit on a
+    16 m lattice and move along their heading: vehicles parked, crawling (below the tracker's speed gate) or driving, pedestrians,
+    cyclists.  ``events`` (see TRACK_EVENTS) scripts gaps, late starts, low scores, near-duplicates and false positives."""
+    rng = np.random.default_rng(seed)
+    ev = {'missing': {}, 'late': {}, 'low': {}, 'chain': {}, 'dup': {}, 'false_pos': [], 'empty': []}
+    ev.update(events or {})
+    sizes = {0: (4.6, 2.0, 1.7), 1: (0.8, 0.8, 1.75), 2: (1.8, 0.7, 1.6)}
+    side = int(math.ceil(math.sqrt(n_objects)))
+    cls = np.array([(0, 0, 1, 0, 2)[k % 5] for k in range(n_objects)])
+    speed = np.where(cls == 0, rng.choice([0.0, 1.0, 4.0, 6.0], size=n_objects), np.where(cls == 1, 1.3, 4.5))
+    heading = rng.uniform(-math.pi, math.pi, size=n_objects)
+    for k in list(ev['chain']) + list(ev['late']):
+        if k < n_objects:
+            cls[k], speed[k], heading[k] = 0, 0.0, 0.0
+    size = np.array([sizes[c] for c in cls]) * rng.uniform(0.9, 1.1, size=(n_objects, 1))
+    start = np.array(origin)[None, :] + np.stack([(np.arange(n_objects) % side) * 16.0, (np.arange(n_objects) // side) * 16.0,
+                                                   rng.uniform(-0.5, 0.5, size=n_objects)], axis=1)
+    vel = np.stack([np.cos(heading), np.sin(heading), np.zeros(n_objects)], axis=1) * speed[:, None]
+    out = {}
+    for f in range(n_frames):
+        rows = []         # (box7, class, score, points)
+        if f not in ev['empty']:
+            for k in range(n_objects):
+                score = rng.uniform(0.35, 0.95)
+                if f in ev['missing'].get(k, ()):
+                    continue
+                if k in ev['late']:
+                    first, lows = ev['late'][k]
+                    if f < first and f not in lows:
+                        continue
+                    if f in lows:
+                        score = rng.uniform(0.03, 0.07)
+                if f in ev['low'].get(k, ()):
+                    score = rng.uniform(0.03, 0.07)
+                centre = start[k] + vel[k] * (0.1 * f) + rng.normal(0, 0.03, size=3)
+                box = np.concatenate([centre, size[k] * rng.uniform(0.99, 1.01, size=3), [heading[k] + rng.normal(0, 0.01)]])
+                rows.append((box, cls[k], score, rng.integers(5, 800)))
+                axis = np.array([math.cos(heading[k]), math.sin(heading[k]), 0.0])
+                if ev['chain'].get(k) == f:
+                    for step in (1.8, 3.6):
+                        extra = box.copy()
+                        extra[:3] += axis * step
+                        rows.append((extra, cls[k], rng.uniform(0.35, 0.95), rng.integers(5, 800)))
+                if ev['dup'].get(k) == f:
+                    extra = box.copy()
+                    extra[:3] += axis * 0.5
+                    rows.append((extra, cls[k], rng.uniform(0.35, 0.95), rng.integers(5, 800)))
+            for j, (first, alive) in enumerate(ev['false_pos']):
+                if first <= f < first + alive:
+                    centre = np.array(origin) + np.array([-40.0 - 12.0 * j, -40.0, 0.0]) + rng.normal(0, 0.03, size=3)
+                    rows.append((np.concatenate([centre, sizes[j % 3], [0.3 * j]]), j % 3, rng.uniform(0.35, 0.95), rng.integers(5, 800)))
+        pose = np.eye(4)
+        pose[:3, 3] = np.array(origin) + np.array([0.5 * f, 0.0, 0.0])
+        out[str(f)] = {
+            'boxes_global': np.array([r[0] for r in rows], dtype=np.float32).reshape(-1, 7),
+            'name': np.array([TRACK_CLASSES[r[1]] for r in rows], dtype='<U10'),
+            'score': np.array([r[2] for r in rows], dtype=np.float32),
+            'num_points': np.array([r[3] for r in rows], dtype=np.int32),
+            'pose': pose, 'sequence_name': sequence_name, 'frame_id': f, 'sample_idx': f,
+        }
+    return out

@@ -1,0 +1,651 @@
+"""The DetZero tracker on a device-resident track table: TrackManager, PostProcessor, DetZeroTracker, build_model / run_model and
+the dataset side (WaymoTrackDataset, build_dataloader).
+
+Mirror of the reference's tracking package, same class names and config keys:
+  * ``tracking/detzero_track/models/tracking_modules/track_manager.py:12-310``   TrackManager
+  * ``.../data_association/data_association.py:9-155``, ``distance.py:9-41``     two_stage / one_stage / only_two_stage, GNN_assignment
+  * ``.../kalman_filter/kalman_filter.py:6-146``                                 KalmanFilter (as kernels: csrc/track.hip)
+  * ``.../post_process.py:10-138``                                               PostProcessor
+  * ``tracking/detzero_track/models/{__init__,detzero_tracker}.py``              DetZeroTracker, build_model, run_model
+  * ``tracking/detzero_track/datasets/{__init__,dataset,waymo_dataset}.py``      WaymoTrackDataset, build_dataloader
+
+What is where.  The reference keeps a Python list of filter objects and walks it for every step; here the tracks of one sequence
+are rows of a struct-of-arrays table on the device and the per-track / per-pair arithmetic (predict, the association cost
+matrices with their masking, update, spawn, overlap_track_merge, the removal of merged and dead tracks, info()) are kernels.
+The host keeps the reference's control flow: frames in order, the index bookkeeping of the association stages - including the
+second stage's unmatched detections that never spawn and the num_points filter - and ``linear_sum_assignment``.  Per frame it
+sees the cost matrices, sends the match lists back and reads one track count.  The ``info()`` rows of a pass are appended to a
+device log that is read once when the pass ends (the reverse pass needs the forward results' ids and ``start`` flags, so a
+sequence with REVERSE_TRACKING costs two reads); the forward rows that join the reverse pass, and the tracks it spawns from
+them, are addressed as rows of that log on the device.
+
+All per-frame arithmetic goes through one narrow ops object (``HipTrackOps`` is the only implementation in the product); the
+tests drive the same orchestration with a numpy restatement of the seven ops.
+
+Arithmetic is fp32, which is what the reference computes when its detections are float32; float64 ``boxes_global`` (what
+transform_to_global produces) are rounded to fp32 when a frame is uploaded.  The size and heading of a track equal columns 3:7 of
+its box wherever the reference reads them, so the table stores the box only.
+
+Not covered (DetZeroHipError naming it): FILTER.NAME AB3DMOT, DISTANCE_METHOD IoU2D, and assign mode (every split but 'test':
+``assign_track_target``) - run with ``--split test``.
+"""
+import os
+import pickle
+from collections import defaultdict
+
+import numpy as np
+import torch
+
+from . import ops, track_adapter
+from .lib import DetZeroHipError
+
+ROW_WORDS = ops.TRACK_ROW_WORDS
+ROW_SCORE, ROW_HIT, ROW_NPTS, ROW_ID, ROW_CLS, ROW_FRAME = 9, 10, 11, 12, 13, 14      # include/detzero_hip.h: the row buffer's words
+AFF_IOU_BEV, AFF_IOU3D, AFF_GIOU3D = ops.TRACK_AFF_IOU_BEV, ops.BOXM_IOU3D, ops.BOXM_GIOU3D
+# ('GIoU3D_dis_mat' is the key data_association/__init__.py:14 registers for GIoU3D_dis_mat)
+METRICS = {'IoUBEV': AFF_IOU_BEV, 'IoU3D': AFF_IOU3D, 'GIoU3D': AFF_GIOU3D, 'GIoU3D_dis_mat': AFF_GIOU3D}
+MAX_CLASSES = ops.TRACK_MAX_CLASSES
+REVERSE_DELTA_T = -0.1                                  # track_manager.py:258
+
+
+# ------------------------------------------------------------------------------------------------
+# assignment (distance.py:9-41)
+# ------------------------------------------------------------------------------------------------
+def GNN_assignment(cost_matrix, threshold=1.):
+    """Global nearest neighbour: costs >= threshold become 5000 (in place), Hungarian assignment, pairs at 5000 dropped.
+    Returns (matched (K,2), unmatched rows, unmatched columns)."""
+    from scipy.optimize import linear_sum_assignment
+    n, m = cost_matrix.shape
+    if n == 0 or m == 0:
+        return np.zeros((0, 2), dtype=int), np.arange(n), np.arange(m)
+    cost_matrix[cost_matrix >= threshold] = 5000.
+    rows, cols = linear_sum_assignment(cost_matrix)
+    ok = cost_matrix[rows, cols] < threshold
+    matched = np.stack([rows[ok], cols[ok]], axis=1).astype(int) if ok.any() else np.empty((0, 2), dtype=int)
+    row_free = np.setdiff1d(np.arange(n), matched[:, 0]).astype(int)
+    col_free = np.setdiff1d(np.arange(m), matched[:, 1]).astype(int)
+    return matched, row_free, col_free
+
+
+# ------------------------------------------------------------------------------------------------
+# ops: the per-frame arithmetic on the device table
+# ------------------------------------------------------------------------------------------------
+def det_rows(boxes, cls, score, num_points):
+    """A frame's detections as a row buffer (include/detzero_hip.h): (D, 16) int32 host array."""
+    d = len(cls)
+    rows = np.zeros((d, ROW_WORDS), dtype=np.int32)
+    if d == 0:
+        return rows
+    f = rows.view(np.float32)
+    f[:, :7] = np.asarray(boxes, dtype=np.float32).reshape(d, -1)[:, :7]
+    f[:, ROW_SCORE] = np.asarray(score, dtype=np.float32)
+    rows[:, ROW_HIT] = 1
+    rows[:, ROW_NPTS] = np.asarray(num_points).astype(np.int32)
+    rows[:, ROW_ID] = -1
+    rows[:, ROW_CLS] = cls
+    return rows
+
+
+class HipTrackOps:
+    """The seven ops on csrc/track.hip.  One instance = one sequence at a time; ``start_pass`` empties the table.
+
+    Interface (what a stand-in for tests implements):
+      start_pass(ext=None)         empty table and log; ``ext`` = the log handle of an earlier pass whose rows can be addressed
+      n                            live tracks
+      set_detections(rows)         the frame's detections, a (D,16) int32 host row buffer
+      predict(gate_class)
+      affinity(row_idx, col_idx, metric, distinguish_class, thr) -> (R,C) float32 host cost matrix; row_idx < 0 = ext row -i-1
+      update(match, r)             (M,3) [table row, detection row, stage]; r = the measurement noise
+      spawn(source, idx, ids, p, q, dt)    source 'det' or 'ext'
+      merge(thr)                   overlap_track_merge's verdicts, kept inside for compact
+      compact(merged, death_age) -> new n
+      log(frame)                   info() of every live track
+      fetch_log() -> (rows (L,16) int32 host array, handle)
+    """
+
+    def __init__(self, device=None, init_cap=256):
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.init_cap = init_cap
+        self.start_pass()
+
+    def _dev(self, a, dtype=np.int32):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.device)
+
+    def start_pass(self, ext=None):
+        self.table, self.spare = ops.TrackTable(self.init_cap, self.device), ops.TrackTable(self.init_cap, self.device)
+        self.n = 0
+        self.log_buf = torch.zeros((4 * self.init_cap, ROW_WORDS), dtype=torch.int32, device=self.device)
+        self.log_n = 0
+        self.ext = ext
+        self.det = None
+        self.removed = None
+
+    def set_detections(self, rows):
+        self.det = self._dev(rows) if len(rows) else torch.zeros((0, ROW_WORDS), dtype=torch.int32, device=self.device)
+
+    def predict(self, gate_class):
+        ops.track_predict_nosync(self.table, self.n, gate_class)
+
+    def affinity(self, row_idx, col_idx, metric, distinguish_class, thr):
+        row_idx, col_idx = np.asarray(row_idx), np.asarray(col_idx)
+        n_ext = 0 if self.ext is None else self.ext.shape[0]
+        tab, fwd = row_idx[row_idx >= 0], -row_idx[row_idx < 0] - 1
+        if (len(tab) and tab.max() >= self.n) or (len(fwd) and fwd.max() >= n_ext):
+            raise DetZeroHipError('track affinity: row index outside the table (%d) / the forward rows (%d)' % (self.n, n_ext))
+        if len(col_idx) and (col_idx.min() < 0 or col_idx.max() >= self.det.shape[0]):
+            raise DetZeroHipError('track affinity: detection index outside the frame (%d)' % self.det.shape[0])
+        out = ops.track_affinity_nosync(self.table, self.n, self.ext, self._dev(row_idx), self.det, self._dev(col_idx), metric,
+                                        distinguish_class, thr)
+        return out.cpu().numpy()
+
+    def update(self, match, r):
+        if len(match):
+            ops.track_update_nosync(self.table, self.n, self.det, self._dev(match), r)
+
+    def spawn(self, source, idx, ids, p, q, dt):
+        m = len(idx)
+        if m == 0:
+            return
+        src = self.det if source == 'det' else self.ext
+        if src is None or np.min(idx) < 0 or np.max(idx) >= src.shape[0]:
+            raise DetZeroHipError('track spawn: source row outside its buffer')
+        grown = self.table.grown(self.n, self.n + m)
+        if grown is not self.table:
+            self.table, self.spare = grown, ops.TrackTable(grown.cap, self.device)
+        ops.track_spawn_nosync(self.table, self.n, src, self._dev(idx), self._dev(ids), p, q, dt)
+        self.n += m
+
+    def merge(self, thr):
+        self.removed = ops.track_merge_nosync(self.table, self.n, thr)
+
+    def compact(self, merged, death_age):
+        if self.n == 0:
+            return 0
+        d_count = ops.track_compact_nosync(self.table, self.n, self.removed if merged else None, death_age, self.spare)
+        self.table, self.spare = self.spare, self.table
+        self.n = int(d_count.item())
+        return self.n
+
+    def log(self, frame):
+        if self.log_n + self.n > self.log_buf.shape[0]:
+            rows = self.log_buf.shape[0]
+            while rows < self.log_n + self.n:
+                rows *= 2
+            new = torch.zeros((rows, ROW_WORDS), dtype=torch.int32, device=self.device)
+            new[:self.log_n].copy_(self.log_buf[:self.log_n])
+            self.log_buf = new
+        ops.track_log_nosync(self.table, self.n, frame, self.log_buf, self.log_n)
+        self.log_n += self.n
+
+    def fetch_log(self):
+        handle = self.log_buf[:self.log_n]
+        return handle.cpu().numpy(), handle
+
+
+# ------------------------------------------------------------------------------------------------
+# TrackManager
+# ------------------------------------------------------------------------------------------------
+def _lower(cfg):
+    return {k.lower(): v for k, v in cfg.items()}
+
+
+class TrackManager:
+    """``forward({sample_idx: frame})`` -> ``{track_id: {boxes_global, name, score, sample_idx, hit, num_points, obj_ids, pose}}``
+    (track_manager.py:85-143).  ``ops_factory`` builds the ops object of a sequence (default: HipTrackOps)."""
+
+    def __init__(self, model_cfg, init_track_id=0, ops_factory=None):
+        self.model_cfg = model_cfg
+        self.init_track_id = init_track_id
+        self.ops_factory = ops_factory if ops_factory is not None else HipTrackOps
+        self.ops = None
+
+        flt = _lower(model_cfg.FILTER)
+        if flt['name'] != 'KalmanFilter':
+            raise DetZeroHipError('FILTER.NAME %s is not provided by the HIP tracker (KalmanFilter only)' % flt['name'])
+        if flt.get('x_dim', 5) != 5 or flt.get('z_dim', 3) != 3:
+            raise DetZeroHipError('KalmanFilter with X_DIM %s / Z_DIM %s (5 / 3 only)' % (flt.get('x_dim'), flt.get('z_dim')))
+        self.p, self.q = tuple(flt.get('p', [1, 1])), tuple(flt.get('q', [1, 1]))
+        self.r, self.delta_t = float(flt.get('r', 1)), float(flt.get('delta_t', 0.1))
+
+        age = _lower(model_cfg.TRACK_AGE)
+        self.birth_age, self.death_age = age.get('birth_age', 1), age.get('death_age', -1)
+
+        da = _lower(model_cfg.DATA_ASSOCIATION)
+        self.class_names = list(da['class_name'])
+        if len(self.class_names) > MAX_CLASSES:
+            raise DetZeroHipError('%d classes (at most %d)' % (len(self.class_names), MAX_CLASSES))
+        self.class_code = {n: i for i, n in enumerate(self.class_names)}
+        self.gate_class = self.class_code.get('Vehicle', -1)
+        self.distinguish_class = bool(da['distinguish_class'])
+        if da['distance_method'] not in METRICS:
+            raise DetZeroHipError('DISTANCE_METHOD %s is not provided by the HIP tracker (%s)' % (da['distance_method'], ', '.join(METRICS)))
+        self.metric = METRICS[da['distance_method']]
+        if da['assignment_method'] != 'GNN':
+            raise DetZeroHipError('ASSIGNMENT_METHOD %s (GNN only)' % da['assignment_method'])
+        stage = da['stage']
+        self.stage = stage['NAME']
+        if self.stage not in ('one_stage', 'two_stage'):
+            raise DetZeroHipError('association STAGE.NAME %s' % self.stage)
+        self.dist_thr = [float(v) for v in stage['FIRST_STAGE']['DIST_THRESHOLD']][:len(self.class_names)]
+        if self.stage == 'two_stage':
+            second = stage['SECOND_STAGE']
+            self.point_thr = np.array(second['POINT_THRESHOLD'])
+            self.score_thr = np.array(second['SCORE_THRESHOLD'])
+            self.second_dist_thr = [float(v) for v in second['DIST_THRESHOLD']][:len(self.class_names)]
+
+        mg = _lower(model_cfg.TRACK_MERGE)
+        self.merge_enable = bool(mg['enable'])
+        if self.merge_enable:
+            by_name = dict(zip(mg['class_name'], mg['class_threshold']))
+            missing = [n for n in self.class_names if n not in by_name]
+            if missing:
+                raise DetZeroHipError('TRACK_MERGE has no threshold for %s' % ', '.join(missing))
+            self.merge_thr = [float(by_name[n]) for n in self.class_names]
+        self.reverse_enable = bool(_lower(model_cfg.REVERSE_TRACKING)['enable'])
+
+    # ---- a frame's detections ------------------------------------------------------------------
+    def _codes(self, names):
+        try:
+            return np.array([self.class_code[n] for n in names], dtype=np.int32)
+        except KeyError as e:
+            raise DetZeroHipError('detection class %s is not in DATA_ASSOCIATION.CLASS_NAME %s' % (e, self.class_names))
+
+    def _upload(self, ops, det_data):
+        """-> class codes; the num_points default of track_manager.py:166-167 is written into det_data as the reference does."""
+        one = self.stage == 'one_stage'
+        if not one and 'num_points' not in det_data:
+            det_data['num_points'] = np.zeros_like(det_data['score'])
+        cls = self._codes(det_data['name'])
+        npts = np.zeros(len(cls), dtype=np.int32) if one else det_data['num_points']
+        ops.set_detections(det_rows(det_data['boxes_global'], cls, det_data['score'], npts))
+        return cls
+
+    # ---- association (data_association.py) -------------------------------------------------------
+    def _one_stage(self, ops, row_idx, col_idx, thr):
+        if len(row_idx) == 0 or len(col_idx) == 0:
+            cost = np.ones((len(row_idx), len(col_idx)), dtype=np.float32)
+        else:
+            cost = ops.affinity(row_idx, col_idx, self.metric, self.distinguish_class, thr)
+        return GNN_assignment(cost)
+
+    def _stage_masks(self, det_data, cls):
+        score_thr, point_thr = self.score_thr[cls], self.point_thr[cls]
+        enough_points = np.greater_equal(det_data['num_points'], point_thr)
+        return np.greater_equal(det_data['score'], score_thr) & enough_points, enough_points
+
+    def _two_stage(self, ops, det_data, cls, row_idx):
+        first_mask, enough_points = self._stage_masks(det_data, cls)
+        if len(row_idx) == 0:
+            det_unmatch = np.flatnonzero(enough_points)
+            return np.zeros((0, 2), dtype=int), np.arange(0), det_unmatch, np.zeros(0, dtype=int)
+        first_det = np.flatnonzero(first_mask)
+        first, trk_free, det_free = self._one_stage(ops, row_idx, first_det, self.dist_thr)
+        first[:, 1] = first_det[first[:, 1]]
+        first_det_free = first_det[det_free]
+        second_det = np.flatnonzero(~first_mask)
+        second_trk = np.sort(np.asarray(trk_free, dtype=int))       # flatnonzero of the mask the reference builds
+        second, trk_free, _ = self._one_stage(ops, row_idx[second_trk], second_det, self.second_dist_thr)
+        second[:, 0] = second_trk[second[:, 0]]
+        second[:, 1] = second_det[second[:, 1]]
+        matched = np.concatenate((first, second), axis=0)
+        stage = np.zeros(matched.shape[0], dtype=int)
+        stage[first.shape[0]:] = 1
+        # the second stage's unmatched detections never spawn (data_association.py:121-123)
+        det_unmatch = first_det_free[enough_points[first_det_free]]
+        return matched, second_trk[trk_free], det_unmatch, stage
+
+    def _only_two_stage(self, ops, det_data, cls, row_idx):
+        first_mask, enough_points = self._stage_masks(det_data, cls)
+        if len(row_idx) == 0:
+            return np.zeros((0, 2), dtype=int), np.arange(0), np.flatnonzero(enough_points)
+        second_det = np.flatnonzero(~first_mask)
+        second, trk_free, det_free = self._one_stage(ops, row_idx, second_det, self.second_dist_thr)
+        second[:, 1] = second_det[second[:, 1]]
+        return second, trk_free, second_det[det_free]
+
+    # ---- the two per-frame modules ---------------------------------------------------------------
+    def _merge_and_log(self, ops, ordinal):
+        if self.merge_enable and ops.n:
+            ops.merge(self.merge_thr)
+            ops.compact(True, -1)
+        ops.log(ordinal)        # every live track: the BIRTH_AGE / DEATH_AGE output rule of track_manager.py:202-205 is AB3DMOT's
+
+    def online_track_module(self, ops, ordinal, det_data, track_id_count):
+        n = ops.n
+        ops.predict(self.gate_class)
+        cls = self._upload(ops, det_data)
+        rows = np.arange(n)
+        if self.stage == 'one_stage':
+            matched, _, det_unmatch = self._one_stage(ops, rows, np.arange(len(cls)), self.dist_thr)
+            stage = np.zeros(matched.shape[0], dtype=int)
+        else:
+            matched, _, det_unmatch, stage = self._two_stage(ops, det_data, cls, rows)
+        ops.update(np.concatenate((matched, stage[:, None]), axis=1), self.r)
+        ids = np.arange(track_id_count, track_id_count + len(det_unmatch))
+        ops.spawn('det', det_unmatch, ids, self.p, self.q, self.delta_t)
+        self._merge_and_log(ops, ordinal)
+        if self.death_age != -1:
+            ops.compact(False, self.death_age)
+        return track_id_count + len(det_unmatch)
+
+    def reverse_tracking_module(self, ops, ordinal, det_data, fwd_rows, fwd_start, fwd_ids):
+        """fwd_rows: rows of the forward log at this frame in track order; the ones that do not start here join the association as
+        extra rows, the ones that start here become reverse tracks once the frame is done (track_manager.py:218-260)."""
+        n = ops.n
+        ops.predict(self.gate_class)
+        cls = self._upload(ops, det_data)
+        if self.stage != 'two_stage':
+            raise DetZeroHipError('REVERSE_TRACKING needs the two_stage association (only_two_stage reads its SECOND_STAGE thresholds)')
+        going = fwd_rows[~fwd_start]
+        rows = np.concatenate((np.arange(n), -going - 1)).astype(int)
+        matched, _, _ = self._only_two_stage(ops, det_data, cls, rows)
+        matched = matched[matched[:, 0] < n]
+        ops.update(np.concatenate((matched, np.ones((matched.shape[0], 1), dtype=int)), axis=1), self.r)
+        self._merge_and_log(ops, ordinal)
+        ops.spawn('ext', fwd_rows[fwd_start], fwd_ids[fwd_start], self.p, self.q, REVERSE_DELTA_T)
+
+    # ---- log rows -> the reference's object-level structure -------------------------------------------
+    def _tracks_of(self, rows, frame_list, data_dict, dtypes):
+        """{track id: dict} in the order in which the ids first appear in the log."""
+        out = {}
+        if len(rows) == 0:
+            return out
+        ids = rows[:, ROW_ID]
+        _, first = np.unique(ids, return_index=True)
+        names = np.array(self.class_names)
+        for at in np.sort(first):
+            sel = np.flatnonzero(ids == ids[at])
+            r = rows[sel]
+            frames = [frame_list[o] for o in r[:, ROW_FRAME]]
+            out[int(ids[at])] = {
+                'boxes_global': r[:, :9].copy().view(np.float32),
+                'name': np.array([names[c] for c in r[:, ROW_CLS]]),
+                'score': r[:, ROW_SCORE].copy().view(np.float32).astype(dtypes['score']),
+                'sample_idx': np.array(frames),
+                'hit': r[:, ROW_HIT].astype(np.int64),
+                'num_points': r[:, ROW_NPTS].astype(dtypes['num_points']),
+                'obj_ids': r[:, ROW_ID].astype(np.int64),
+                'pose': np.array([data_dict[f]['pose'] for f in frames]),
+            }
+        return out
+
+    def forward(self, data_dict):
+        frame_list = sorted(list(data_dict.keys()), key=int)
+        ops = self.ops if self.ops is not None else self.ops_factory()
+        self.ops = ops
+        ops.start_pass()
+        track_id_count = self.init_track_id
+        dtypes = {'score': np.float32, 'num_points': np.int64}
+        for ordinal, frm_id in enumerate(frame_list):
+            track_id_count = self.online_track_module(ops, ordinal, data_dict[frm_id], track_id_count)
+            if len(data_dict[frm_id]['score']):
+                dtypes['score'] = np.asarray(data_dict[frm_id]['score']).dtype
+                if self.stage != 'one_stage':
+                    dtypes['num_points'] = np.asarray(data_dict[frm_id]['num_points']).dtype
+        rows, handle = ops.fetch_log()
+        tk_result = self._tracks_of(rows, frame_list, data_dict, dtypes)
+        if not self.reverse_enable:
+            return tk_result
+
+        # forward results per frame in track order, with the flag of each track's first frame (track_manager.py:117-128)
+        ids = rows[:, ROW_ID] if len(rows) else np.zeros(0, dtype=np.int32)
+        _, first = np.unique(ids, return_index=True)
+        is_start = np.zeros(len(rows), dtype=bool)
+        is_start[first] = True
+        rank = {int(ids[at]): k for k, at in enumerate(np.sort(first))}
+        order = np.array([rank[int(i)] for i in ids], dtype=int)
+        ops.start_pass(ext=handle)
+        for ordinal in range(len(frame_list) - 1, -1, -1):
+            at = np.flatnonzero(rows[:, ROW_FRAME] == ordinal) if len(rows) else np.zeros(0, dtype=int)
+            at = at[np.argsort(order[at], kind='stable')]
+            self.reverse_tracking_module(ops, ordinal, data_dict[frame_list[ordinal]], at, is_start[at], ids[at].astype(np.int64))
+        back, _ = ops.fetch_log()
+        back_tracks = self._tracks_of(back, frame_list, data_dict, dtypes)
+        for tk_id, early in back_tracks.items():
+            # the reverse pass inserts every row at the front (track_manager.py:134-141): the last one processed comes first
+            for key, val in tk_result[tk_id].items():
+                tk_result[tk_id][key] = np.concatenate((early[key][::-1].astype(val.dtype), val), axis=0)
+        return tk_result
+
+
+# ------------------------------------------------------------------------------------------------
+# PostProcessor (post_process.py), host numpy as in the reference
+# ------------------------------------------------------------------------------------------------
+def _trailing_misses(hit):
+    """Indices from the end back to (not including) the last row with hit >= 1."""
+    idx = []
+    for i in range(len(hit) - 1, -1, -1):
+        if hit[i] >= 1:
+            break
+        idx.append(i)
+    return idx
+
+
+class PostProcessor:
+    """``processor_configs.CONFIG_LIST``: entries with ``.NAME`` in {empty_track_delete, velocity_optimize, motion_classify,
+    static_drift_eliminate, box_size_update}, applied in order to the whole ``{track_id: track}`` dict, in place.  ``overlap_fn``
+    = the all-pairs BEV overlap of motion_classify (default: the HIP kernel behind track_adapter.bev_overlap_gpu)."""
+
+    def __init__(self, processor_configs, overlap_fn=None):
+        self.overlap_fn = overlap_fn if overlap_fn is not None else track_adapter.bev_overlap_gpu
+        self.post_process_queue = []
+        for cfg in processor_configs.CONFIG_LIST:
+            if not hasattr(self, cfg.NAME):
+                raise DetZeroHipError('unknown post-processor %s' % cfg.NAME)
+            self.post_process_queue.append((getattr(self, cfg.NAME), cfg))
+
+    def forward(self, data_dict):
+        for fn, cfg in self.post_process_queue:
+            data_dict = fn(data_dict, cfg)
+        return data_dict
+
+    def empty_track_delete(self, data_dict, config):
+        """Tracks with fewer than LEAST_AGE hit frames go; the others lose their leading and trailing missed frames (END_REMOVE)."""
+        for tk_id in list(data_dict.keys()):
+            tk = data_dict[tk_id]
+            hit = tk['hit']
+            hits = int(np.sum(hit > 0))
+            if hits < config.LEAST_AGE:
+                data_dict.pop(tk_id)
+                continue
+            if hits != len(hit) and config.END_REMOVE:
+                lead = []
+                for i in range(len(hit)):
+                    if hit[i] >= 1:
+                        break
+                    lead.append(i)
+                drop = lead + _trailing_misses(hit)
+                for key in tk.keys():
+                    tk[key] = np.delete(tk[key], drop, axis=0)
+        return data_dict
+
+    def velocity_optimize(self, data_dict, config):
+        """The first HEADER_LENGTH velocities (all but the last of a shorter track) from the displacement to the next frame at 10 Hz."""
+        for tk in data_dict.values():
+            boxes = tk['boxes_global']
+            n = len(boxes)
+            if n < 2:
+                continue
+            for i in range(config.HEADER_LENGTH if n > config.HEADER_LENGTH else n - 1):
+                boxes[i, 7:9] = (boxes[i + 1, :2] - boxes[i, :2]) * 10.
+        return data_dict
+
+    def motion_classify(self, data_dict, config):
+        """'dynamic' when two of the track's updated boxes overlap by 1e-4 m^2 or less, else 'static'."""
+        for tk in data_dict.values():
+            at = np.flatnonzero(tk['hit'] == 1)
+            state = 'static'
+            if len(at) >= 2:
+                boxes = np.ascontiguousarray(tk['boxes_global'][at, :7], dtype=np.float32)
+                if np.any(self.overlap_fn(boxes, boxes) <= 1e-4):
+                    state = 'dynamic'
+            tk['state'] = state
+        return data_dict
+
+    def static_drift_eliminate(self, data_dict, config):
+        """A static Vehicle's trailing missed frames take the box of its best-scored updated frame."""
+        for tk in data_dict.values():
+            if tk['state'] == 'static' and tk['name'][0] == 'Vehicle':
+                at = np.flatnonzero(tk['hit'] == 1)
+                best = at[np.argsort(tk['score'][at])[-1]]
+                for i in _trailing_misses(tk['hit']):
+                    tk['boxes_global'][i] = tk['boxes_global'][best].copy()
+        return data_dict
+
+    def box_size_update(self, data_dict, config):
+        for tk in data_dict.values():
+            scores, boxes = tk['score'], tk['boxes_global']
+            if config.METHOD == 'max_score_box':
+                at = np.where(scores == np.max(scores))[0]
+                size = np.zeros(3, dtype=np.float32)
+                for i in at:
+                    size += boxes[i, 3:6]
+                boxes[:, 3:6] = size / len(at)
+            elif config.METHOD == 'score_weigthed_box':
+                size = np.zeros(3, dtype=np.float32)
+                for i in range(len(scores)):
+                    size += scores[i] * boxes[i, 3:6]
+                boxes[:, 3:6] = size / np.sum(scores)
+            elif config.METHOD == 'largest_box':
+                boxes[:, 3:6] = boxes[np.argsort(boxes[:, 3] * boxes[:, 4] * boxes[:, 5])[-1], 3:6].copy()
+        return data_dict
+
+
+TRACKING_MODULES = {'TrackManager': TrackManager, 'PostProcessor': PostProcessor}
+
+
+# ------------------------------------------------------------------------------------------------
+# model
+# ------------------------------------------------------------------------------------------------
+class DetZeroTracker:
+    """TRACKING then POST_PROCESS over one sequence (detzero_tracker.py:4-46)."""
+
+    def __init__(self, model_cfg, logger=None):
+        self.model_cfg = model_cfg
+        self.logger = logger
+        self.module_list = []
+        if model_cfg.get('TRACKING', None) is not None:
+            self.module_list.append(TRACKING_MODULES[model_cfg.TRACKING.NAME](model_cfg=model_cfg.TRACKING))
+        if model_cfg.get('POST_PROCESS', None) is not None:
+            self.module_list.append(TRACKING_MODULES[model_cfg.POST_PROCESS.NAME](processor_configs=model_cfg.POST_PROCESS))
+
+    def forward(self, data_dict):
+        for module in self.module_list:
+            data_dict = module.forward(data_dict=data_dict)
+        return data_dict
+
+
+__all__ = {'DetZeroTracker': DetZeroTracker}
+
+
+def build_model(model_cfg, logger=None):
+    return __all__[model_cfg.NAME](model_cfg=model_cfg, logger=logger)
+
+
+def _banner(text, total=100):
+    return text.center(max(total, len(text)), '-')
+
+
+def run_model(model, dataloader, dataset, workers, cfgs=None, logger=None):
+    """Tracks every sequence of every batch, one after another in this process (``workers`` is accepted for the reference's
+    signature; no process pool ever opens the GPU), and writes tracking-<split>-<time>.pkl and drop-<split>-<time>.pkl."""
+    if dataset.assign_mode:
+        raise DetZeroHipError('assign mode (split %r: assign_track_target on ground truth) is not provided by the HIP tracker; '
+                              'run with --split test' % getattr(dataset, 'split', None))
+    if logger is not None:
+        logger.info(_banner('Running Tracking Module!'))
+    track_data, drop_data = {}, {}
+    for seq_names, data_dicts in dataloader:
+        outputs = [model.forward(seq) for seq in data_dicts['detection']]
+        track_data.update(dict(zip(seq_names, outputs)))
+        drop_data.update(dict(zip(seq_names, data_dicts['det_drop'])))
+    with open(dataset.get_track_path(), 'wb') as f:
+        pickle.dump(track_data, f)
+    with open(dataset.get_drop_path(), 'wb') as f:
+        pickle.dump(drop_data, f)
+    if logger is not None:
+        logger.info(_banner('Tracking module running finished!'))
+
+
+# ------------------------------------------------------------------------------------------------
+# dataset
+# ------------------------------------------------------------------------------------------------
+class WaymoTrackDataset:
+    """Detection results (a list of frame records or ``{sequence: {sample_idx: frame}}``) -> one item per sequence:
+    ``(sequence_name, {'detection': processed frames, 'det_drop': removed boxes})`` (waymo_dataset.py:13-109)."""
+
+    def __init__(self, dataset_cfg, data_path, log_time, split, root_path=None, logger=None, overlap_fn=None, count_fn=None):
+        self.dataset_cfg = dataset_cfg
+        self.det_path = data_path
+        self.root_path = root_path if root_path is not None else dataset_cfg.DATA_PATH
+        self.logger = logger
+        self.split = split
+        self.logtime = log_time
+        self.data_processor = track_adapter.DataProcessor(dataset_cfg.DATA_PROCESSOR,
+                                                          os.path.join(self.root_path, dataset_cfg.PROCESSED_DATA_TAG), overlap_fn, count_fn)
+        if logger:
+            logger.info(_banner('Initialize %s' % dataset_cfg.DATASET))
+        track_path = os.path.join(self.root_path, 'tracking')
+        os.makedirs(track_path, exist_ok=True)
+        self.track_module_path = defaultdict(dict)
+        self.track_module_path['tracking'] = os.path.join(track_path, '-'.join(['tracking', split, log_time]))
+        self.track_module_path['det_drop'] = os.path.join(track_path, '-'.join(['drop', split, log_time]))
+        self.track_module_path['detection'] = data_path
+        self.gt_path = os.path.join(self.root_path, 'waymo_infos_%s.pkl' % split)
+        with open(data_path, 'rb') as f:
+            raw = pickle.load(f)
+        if isinstance(raw, list):
+            raw = track_adapter.sequence_list_to_dict(raw)
+        elif not isinstance(raw, dict):
+            raise TypeError('The format of detection results must be List or Dict.')
+        self.seq_name_list = list(raw.keys())
+        self.seq_det_infos = [raw[s] for s in self.seq_name_list]
+
+    @property
+    def assign_mode(self):
+        return self.split != 'test'
+
+    def __len__(self):
+        return len(self.seq_name_list)
+
+    def __getitem__(self, idx):
+        det, drop = self.data_processor.forward(data_dict=self.seq_det_infos[idx])
+        return self.seq_name_list[idx], {'detection': det, 'det_drop': drop}
+
+    @staticmethod
+    def collate_batch(batch_list):
+        names, dicts = [], defaultdict(list)
+        for name, sample in batch_list:
+            names.append(name)
+            for k, v in sample.items():
+                dicts[k].append(v)
+        return names, dicts
+
+    def get_track_path(self):
+        return self.track_module_path['tracking'] + '.pkl'
+
+    def get_drop_path(self):
+        return self.track_module_path['det_drop'] + '.pkl'
+
+
+class SequenceLoader:
+    """In-process iterable over batches of sequences: no worker processes, no start method set."""
+
+    def __init__(self, dataset, batch_size):
+        self.dataset, self.batch_size = dataset, max(int(batch_size), 1)
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        for i in range(0, len(self.dataset), self.batch_size):
+            yield self.dataset.collate_batch([self.dataset[j] for j in range(i, min(i + self.batch_size, len(self.dataset)))])
+
+
+DATASETS = {'WaymoTrackDataset': WaymoTrackDataset}
+
+
+def build_dataloader(dataset_cfg, log_time, data_path, batch_size, workers, split, logger, root_path=None):
+    dataset = DATASETS[dataset_cfg.DATASET](dataset_cfg=dataset_cfg, data_path=data_path, split=split, root_path=root_path,
+                                            log_time=log_time, logger=logger)
+    return dataset, SequenceLoader(dataset, batch_size)

@@ -829,6 +829,74 @@ int dz_self_attention_split_supported(int l, int e);
 int dz_self_attention_split(const float *q, const float *x, const unsigned char *key_padding_mask, int r, int l, int e, float *out,
                             int math, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tracking module (csrc/track.hip): the per-track and per-pair arithmetic of tracking/detzero_track/models/tracking_modules
+ * (kalman_filter.py KalmanFilter, data_association.py one_stage + distance.py GNN_assignment's masking, track_manager.py
+ * overlap_track_merge) on a device-resident track table of ONE sequence.  Frame order, the index bookkeeping of the association
+ * stages and linear_sum_assignment stay on the host.
+ *
+ * dz_track_table: struct of arrays, `cap` rows each, rows [0, n) live, list order = the reference's `tracks` list.  The size and
+ * heading of a track are columns 3:7 of its box at every point of the reference's code, so they are not stored twice.
+ * A "row buffer" (detections of a frame, log, forward-pass results) is an array of DZ_TRACK_ROW_WORDS 32-bit words per row:
+ *   [0:9] box f32 | [9] score f32 | [10] hit i32 | [11] num_points i32 | [12] track id i32 | [13] class code i32 |
+ *   [14] frame ordinal i32 | [15] 0
+ * All entry points: n == 0 (m == 0) launches nothing; DZ_ERR_UNSUPPORTED where 32-bit offsets would overflow, for more than
+ * DZ_TRACK_MAX_CLASSES classes and for an unknown metric. */
+#define DZ_TRACK_ROW_WORDS 16
+#define DZ_TRACK_MAX_CLASSES 8
+typedef struct {
+    float *x;            /* (cap,5)  state [x, y, z, vx, vy] */
+    float *P;            /* (cap,25) */
+    float *Q;            /* (cap,25) */
+    float *dt;           /* (cap)    delta_t: F = I with F[0][3] = F[1][4] = dt */
+    float *box;          /* (cap,9)  [x, y, z, dx, dy, dz, heading, vx, vy] */
+    int *cls;            /* (cap)    class code */
+    float *score;        /* (cap) */
+    float *update_score; /* (cap) */
+    int *num_points;     /* (cap) */
+    int *hit;            /* (cap) */
+    int *miss;           /* (cap) */
+    int *id;             /* (cap) */
+    int cap;             /* rows allocated in every array; n (and n + m of dz_track_spawn) beyond it is DZ_ERR_INVALID */
+} dz_track_table;
+/* KalmanFilter.predict (kalman_filter.py:85-108) on rows [0, n), one thread per track, fp32: class `gate_class` (Vehicle; -1 = no
+ * class) with |v| <= max(size) / 2 predicts with v = 0; x = F x, P = F P F^T + Q, Q *= 1.5, miss += 1, hit = 0,
+ * box = [x0:3, size, heading, vx, vy]. */
+int dz_track_predict(const dz_track_table *t, int n, int gate_class, void *stream);
+/* Association cost matrix (data_association.py:36-58 + distance.py:22): out (nr, nc) f32,
+ *   aff = metric(row box, col box); 0 where the classes differ (distinguish_class) ; 0 where aff < thr[row class];
+ *   cost = 1 - aff; cost >= 1 -> 5000.
+ * Rows: row_idx[r] >= 0 is table row row_idx[r] (< n), row_idx[r] < 0 is row (-row_idx[r] - 1) of the row buffer `ext` of n_ext rows
+ * (the forward results that join the reverse pass).  Columns: rows col_idx[c] of the row buffer `det` of n_det rows.  A pair with
+ * an index outside its buffer reads nothing and costs 5000.  h_thr: host array of n_cls thresholds.  metric: DZ_TRACK_AFF_IOU_BEV (the pair
+ * body of dz_boxes_iou_bev), DZ_BOXM_IOU3D, DZ_BOXM_GIOU3D (the pair body of dz_boxes_pairwise_metric): bit-identical to those. */
+#define DZ_TRACK_AFF_IOU_BEV 16
+int dz_track_affinity(const dz_track_table *t, int n, const int *ext, int n_ext, const int *row_idx, int nr, const int *det, int n_det,
+                      const int *col_idx, int nc, int metric, int distinguish_class, const float *h_thr, int n_cls, float *out,
+                      void *stream);
+/* KalmanFilter.update (kalman_filter.py:110-146) for m matches, one thread each: match (m,3) int32 [table row, det row, stage].
+ * Stage 0: S = H P H^T + r I, K = P H^T S^-1 (cofactor inverse), x += K (z - H x), P -= K H P, x[0:3] = z, box = [det 0:7, v],
+ * class / score / num_points from the detection, update_score = max(score, 0.03), hit = 1, miss = 0.  Stage 1 (second stage):
+ * hit = 2, miss = 0, score and num_points only.  A table row may appear in one match only. */
+int dz_track_update(const dz_track_table *t, int n, const int *det, int n_det, const int *match, int m, float r, void *stream);
+/* Append m tracks at rows [n, n + m) from rows src_idx (device, each < n_src) of the row buffer `src`, with the
+ * constructor's matrices (kalman_filter.py:10-58): P = diag(p0 x3, p1 x2), Q = diag(q0 x3, q1 x2), x = [box 0:3, 0, 0],
+ * box = [box 0:7, 0, 0], hit = 1, miss = 0, update_score = score, id = ids[k], delta_t = dt. */
+int dz_track_spawn(const dz_track_table *t, int n, const int *src, int n_src, const int *src_idx, const int *ids, int m, float p0,
+                   float p1, float q0, float q1, float dt, void *stream);
+/* TrackManager.overlap_track_merge (track_manager.py:262-310): bits (n, ceil(n/64)) 64-bit words, bit (i, j) = same class and
+ * overlap_bev(i, j) / (dx_i * dy_i + 1e-9) >= thr[class i]; then the reference's greedy sweep in one workgroup (the lowest id of a
+ * row's remaining set is kept, the rest of the set is removed, the set's columns are cleared).  removed (n) int32 0 / 1.
+ * Workspace: dz_track_merge_workspace_bytes(n).  Every threshold must be > 0 (a cleared column then never passes), n <= 32768. */
+size_t dz_track_merge_workspace_bytes(int n);
+int dz_track_merge(const dz_track_table *t, int n, const float *h_thr, int n_cls, int *removed, void *ws, size_t ws_bytes, void *stream);
+/* Stable removal: rows with removed[i] != 0 (removed may be NULL) or, when death_age != -1, miss >= death_age, are dropped; the
+ * survivors are copied in order into `dst` (another table, never `src`).  *d_count (device) = the new count. */
+int dz_track_compact(const dz_track_table *src, int n, const int *removed, int death_age, const dz_track_table *dst, int *d_count,
+                     void *stream);
+/* info() of rows [0, n) (kalman_filter.py:61-72) as rows [log_n, log_n + n) of the row buffer `log`, frame ordinal `frame`. */
+int dz_track_log(const dz_track_table *t, int n, int frame, int *log, long log_n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,78 @@
+#!/usr/bin/env python
+"""Tracker throughput on one sequence, for the record: the device ops (csrc/track.hip) and the numpy restatement of the same seven
+ops (tests/track_ref.py) under the same orchestration (detzero_amd.track_models.TrackManager, shipped waymo_detzero_track values:
+two-stage IoUBEV association, TRACK_MERGE, REVERSE_TRACKING, DEATH_AGE -1) and the same input.
+
+    python tools/bench_track.py [--frames 200] [--objects 150] [--steps 3] [--no-numpy]
+
+Input: one seeded sequence (detzero_amd.synth.synth_track_sequence) of --frames frames with about --objects detections each.
+Prints one JSON line: sequences/s and ms per frame-pass of both, the number of tracks, and whether the two results agree.
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MODEL = {
+    'FILTER': {'NAME': 'KalmanFilter', 'X_DIM': 5, 'Z_DIM': 3, 'Q': [5, 15], 'P': [50, 1000], 'R': 0.1, 'DELTA_T': 0.1},
+    'TRACK_AGE': {'BIRTH_AGE': 1, 'DEATH_AGE': -1},
+    'DATA_ASSOCIATION': {'CLASS_NAME': ['Vehicle', 'Pedestrian', 'Cyclist'], 'DISTINGUISH_CLASS': True, 'DISTANCE_METHOD': 'IoUBEV',
+                         'ASSIGNMENT_METHOD': 'GNN',
+                         'STAGE': {'NAME': 'two_stage', 'FIRST_STAGE': {'DIST_THRESHOLD': [0.2, 0.1, 0.1]},
+                                   'SECOND_STAGE': {'SCORE_THRESHOLD': [0.1, 0.1, 0.1], 'POINT_THRESHOLD': [0, 0, 0],
+                                                    'DIST_THRESHOLD': [0.3, 0.15, 0.15]}}},
+    'TRACK_MERGE': {'ENABLE': True, 'CLASS_NAME': ['Vehicle', 'Pedestrian', 'Cyclist'], 'CLASS_THRESHOLD': [0.5, 0.4, 0.4]},
+    'REVERSE_TRACKING': {'ENABLE': True},
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, default=200)
+    ap.add_argument('--objects', type=int, default=150)
+    ap.add_argument('--steps', type=int, default=3)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--no-numpy', action='store_true')
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from detzero_amd.config import AttrDict
+    from detzero_amd.synth import TRACK_EVENTS, synth_track_sequence
+    from detzero_amd.track_models import TrackManager
+
+    seq = synth_track_sequence(args.seed, args.frames, args.objects, events=TRACK_EVENTS)
+    dets = sum(len(f['score']) for f in seq.values())
+    cfg = AttrDict(MODEL)
+
+    manager = TrackManager(cfg)
+    result = manager.forward(copy.deepcopy(seq))            # warm-up: library load, allocator
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        result = manager.forward(copy.deepcopy(seq))
+    torch.cuda.synchronize()
+    hip_s = (time.perf_counter() - t0) / args.steps
+    passes = args.frames * 2
+    out = {'frames': args.frames, 'detections_per_frame': round(dets / args.frames, 1), 'tracks': len(result),
+           'rows': int(sum(len(t['hit']) for t in result.values())),
+           'hip_sequences_per_s': round(1.0 / hip_s, 3), 'hip_ms_per_frame_pass': round(1e3 * hip_s / passes, 3)}
+    if not args.no_numpy:
+        from tests import track_ref
+        t0 = time.perf_counter()
+        ref = TrackManager(cfg, ops_factory=track_ref.NumpyTrackOps).forward(copy.deepcopy(seq))
+        np_s = time.perf_counter() - t0
+        same = list(ref) == list(result) and all(np.array_equal(ref[k]['hit'], result[k]['hit']) for k in ref)
+        worst = max((float(np.abs(ref[k]['boxes_global'] - result[k]['boxes_global']).max()) for k in ref), default=0.0) if same else None
+        out.update({'numpy_sequences_per_s': round(1.0 / np_s, 4), 'numpy_ms_per_frame_pass': round(1e3 * np_s / passes, 3),
+                    'same_tracks_and_hits': same, 'max_box_difference': worst})
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
