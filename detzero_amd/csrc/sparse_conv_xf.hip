@@ -96,6 +96,7 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xf(SpConvXFArgs a) {
     const int nk = a.cin / 16;
     const srsrc_t prsrc = make_srsrc(a.in, a.in_bytes), crsrc = make_srsrc(a.w, a.w_bytes);
     const unsigned int row_bytes = (unsigned int)a.cin * 4u;
+    const unsigned int in_rows = a.in_bytes / row_bytes;
 
     // the zero rows of the two window buffers
     if (tid < 32) reinterpret_cast<unsigned int *>(smem + C::OFF_WIN + (tid >> 4) * C::WIN_BYTES + RCAP * 64)[tid & 15] = 0u;
@@ -189,7 +190,10 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xf(SpConvXFArgs a) {
             constexpr int tx = decltype(tx_t)::value;
             const int idx = rank + (tx == 0 ? -1 : tx == 1 ? 0 : (int)((e >> 30) & 1u));       // input row of the tap
             const int off = idx - lo;
-            const bool valid = ((e >> (29 + tx)) & 1u) != 0u && (GM || (unsigned int)off < (unsigned int)n);
+            // (gather mode reads the row through a plain pointer: a rank at or past the input's rows - a level that overflowed its
+            // calibrated capacity keeps such ranks in its index - has no row to read and adds nothing, as in the staged mode,
+            // whose buffer loads return zeros there)
+            const bool valid = ((e >> (29 + tx)) & 1u) != 0u && (GM ? (unsigned int)idx < in_rows : (unsigned int)off < (unsigned int)n);
             if (__ballot(valid) == 0ull) return;            // none of the fragment's rows has this tap
             float4 x0, x1;
             if constexpr (GM) {

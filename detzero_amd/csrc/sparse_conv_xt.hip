@@ -100,6 +100,7 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXTArgs a) {
     const int nk = a.cin / 16;
     const srsrc_t prsrc = make_srsrc(a.in, a.in_bytes), crsrc = make_srsrc(a.w, a.w_bytes);
     const unsigned int row_bytes = (unsigned int)a.cin * 4u;
+    const unsigned int in_rows = a.in_bytes / row_bytes;
     const unsigned int wrow_bytes = (unsigned int)a.cin * 6u;           // a weight row: cin / 8 groups of 48 bytes
 
     // the zero rows of the two window buffers
@@ -210,7 +211,10 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXTArgs a) {
         auto tap = [&](int t, int tx) {
             const int idx = rank + (tx == 0 ? -1 : tx == 1 ? 0 : (int)((e >> 30) & 1u));       // input row of the tap
             const int off = idx - lo;
-            const bool valid = ((e >> (29 + tx)) & 1u) != 0u && (GM || (unsigned int)off < (unsigned int)n);
+            // (gather mode reads the row through a plain pointer: a rank at or past the input's rows - a level that overflowed its
+            // calibrated capacity keeps such ranks in its index - has no row to read and adds nothing, as in the staged mode,
+            // whose buffer loads return zeros there)
+            const bool valid = ((e >> (29 + tx)) & 1u) != 0u && (GM ? (unsigned int)idx < in_rows : (unsigned int)off < (unsigned int)n);
             if (__ballot(valid) == 0ull) return;            // none of the fragment's rows has this tap
             float4 x0, x1;
             if constexpr (GM) {
