@@ -14,6 +14,7 @@
 #pragma clang fp contract(off)
 
 #include "box_geom.h"
+#include "class_thr.h"
 
 namespace dz {
 
@@ -23,16 +24,6 @@ constexpr int ROW_SCORE = 9, ROW_HIT = 10, ROW_NPTS = 11, ROW_ID = 12, ROW_CLS =
 constexpr int MERGE_ROWS_PER_WAVE = 16;
 constexpr int MERGE_MAX_TRACKS = 32768;
 constexpr int MERGE_MAX_WORDS = MERGE_MAX_TRACKS / 64;
-
-struct ClassThr { float v[DZ_TRACK_MAX_CLASSES]; };
-
-// thr.v[c] by a select chain: a dynamically indexed by-value struct would go through scratch memory (box_geom.h, rect_overlap)
-__device__ __forceinline__ float thr_of(const ClassThr &thr, int c) {
-    float t = thr.v[0];
-#pragma unroll
-    for (int k = 1; k < DZ_TRACK_MAX_CLASSES; ++k) t = c == k ? thr.v[k] : t;
-    return t;
-}
 
 // ------------------------------------------------------------------------------------------
 // predict

@@ -246,6 +246,10 @@ _SIGS = {
     'dz_track_merge': (c_int, [_TT, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'dz_track_compact': (c_int, [_TT, c_int, c_void_p, c_int, _TT, c_void_p, c_void_p]),
     'dz_track_log': (c_int, [_TT, c_int, c_int, c_void_p, ctypes.c_long, c_void_p]),
+    'dz_traj_pair_table': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dz_traj_pair_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

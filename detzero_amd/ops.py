@@ -1443,6 +1443,79 @@ def track_log_nosync(table, n, frame, log, log_n):
     L.check(L.load().dz_track_log(ctypes.byref(table.c), int(n), int(frame), L.ptr(log), int(log_n), L.stream()), 'dz_track_log')
 
 
+# ------------------------------------------------------------------------------------------------
+# trajectory-pair table (csrc/traj_pair.hip): ground-truth trajectories against tracks over a whole sequence
+# ------------------------------------------------------------------------------------------------
+def _traj_sides(a_box, a_cls, a_slot, b_box, b_cls, b_slot, n_cls, what):
+    """Shapes, dtypes and - one host read for both sides - the index ranges: a slot outside [-1, rows) or a ground-truth class
+    outside the threshold table is refused here, before any launch.  -> (n_a, a_rows, n_b, b_rows, n_frames)."""
+    L.require_cuda(a_box, a_cls, a_slot, b_box, b_cls, b_slot)
+    for box, cls, slot, side in ((a_box, a_cls, a_slot, 'a'), (b_box, b_cls, b_slot, 'b')):
+        if box.dtype != torch.float32 or box.dim() != 2 or box.shape[1] != 7:
+            raise L.DetZeroHipError('%s: %s_box is (rows, 7) float32, got %s %s' % (what, side, tuple(box.shape), box.dtype))
+        if cls.dtype != torch.int32 or cls.dim() != 1 or cls.shape[0] != box.shape[0]:
+            raise L.DetZeroHipError('%s: %s_cls is (rows,) int32, one per box' % (what, side))
+        if slot.dtype != torch.int32 or slot.dim() != 2:
+            raise L.DetZeroHipError('%s: %s_slot is (n_frames, n) int32' % (what, side))
+    if a_slot.shape[0] != b_slot.shape[0]:
+        raise L.DetZeroHipError('%s: %d frames on side a, %d on side b' % (what, a_slot.shape[0], b_slot.shape[0]))
+    probes, names = [], []
+    for t, name, hi in ((a_slot, 'a_slot', a_box.shape[0]), (b_slot, 'b_slot', b_box.shape[0]), (a_cls, 'a_cls', n_cls)):
+        if t.numel():
+            probes += [t.min(), t.max()]
+            names.append((name, -1 if name != 'a_cls' else 0, hi))
+    if probes:
+        seen = torch.stack(probes).cpu().tolist()
+        for k, (name, lo, hi) in enumerate(names):
+            if seen[2 * k] < lo or seen[2 * k + 1] >= hi:
+                raise L.DetZeroHipError('%s: %s holds %d..%d, outside [%d, %d)' % (what, name, seen[2 * k], seen[2 * k + 1], lo, hi))
+    return a_slot.shape[1], a_box.shape[0], b_slot.shape[1], b_box.shape[0], a_slot.shape[0]
+
+
+def _traj_metric(metric, what):
+    if int(metric) not in (TRACK_AFF_IOU_BEV, BOXM_IOU3D):
+        raise L.DetZeroHipError('%s: metric %s (TRACK_AFF_IOU_BEV or BOXM_IOU3D)' % (what, metric))
+    return int(metric)
+
+
+def traj_pair_table(a_box, a_cls, a_slot, b_box, b_cls, b_slot, metric, distinguish_class, thr):
+    """dz_traj_pair_table: a = ground-truth trajectories, b = tracks; *_box (rows,7) f32, *_cls (rows,) i32, *_slot (n_frames, n) i32
+    frame-major, -1 = no box at that frame.  -> (sum_all, sum_hit) f32, (n_hit, n_same) i32, each (n_a, n_b), on the device."""
+    metric = _traj_metric(metric, 'traj_pair_table')
+    thr = [float(v) for v in thr]
+    if not 1 <= len(thr) <= TRACK_MAX_CLASSES or not all(v > 0 for v in thr):
+        raise L.DetZeroHipError('traj_pair_table: thresholds %s (1..%d of them, every one > 0)' % (thr, TRACK_MAX_CLASSES))
+    n_a, a_rows, n_b, b_rows, n_frames = _traj_sides(a_box, a_cls, a_slot, b_box, b_cls, b_slot, len(thr), 'traj_pair_table')
+    dev = a_box.device
+    sums = torch.zeros((2, n_a, n_b), dtype=torch.float32, device=dev)
+    counts = torch.zeros((2, n_a, n_b), dtype=torch.int32, device=dev)
+    rc = L.load().dz_traj_pair_table(L.ptr(a_box), L.ptr(a_cls), L.ptr(a_slot), n_a, a_rows, L.ptr(b_box), L.ptr(b_cls), L.ptr(b_slot), n_b,
+                                     b_rows, n_frames, metric, int(bool(distinguish_class)), _track_thr(thr), len(thr), L.ptr(sums[0]),
+                                     L.ptr(sums[1]), L.ptr(counts[0]), L.ptr(counts[1]), L.stream())
+    L.check(rc, 'dz_traj_pair_table')
+    return sums[0], sums[1], counts[0], counts[1]
+
+
+def traj_pair_rows(a_box, a_cls, a_slot, b_box, b_cls, b_slot, metric, distinguish_class, pairs):
+    """dz_traj_pair_rows: pairs (n_pairs,2) i32 device [trajectory, track] -> (n_pairs, n_frames) f32, the class-masked per-frame
+    value at the frames a pair shares, 0 elsewhere."""
+    metric = _traj_metric(metric, 'traj_pair_rows')
+    n_a, a_rows, n_b, b_rows, n_frames = _traj_sides(a_box, a_cls, a_slot, b_box, b_cls, b_slot, TRACK_MAX_CLASSES, 'traj_pair_rows')
+    L.require_cuda(pairs)
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise L.DetZeroHipError('traj_pair_rows: pairs is (n_pairs, 2) int32')
+    n_pairs = pairs.shape[0]
+    rows = torch.zeros((n_pairs, n_frames), dtype=torch.float32, device=a_box.device)
+    if n_pairs:
+        lo, hi = torch.stack([pairs.min(dim=0).values, pairs.max(dim=0).values]).cpu().tolist()
+        if min(lo) < 0 or hi[0] >= n_a or hi[1] >= n_b:
+            raise L.DetZeroHipError('traj_pair_rows: a pair outside the %d x %d table' % (n_a, n_b))
+    rc = L.load().dz_traj_pair_rows(L.ptr(a_box), L.ptr(a_cls), L.ptr(a_slot), n_a, a_rows, L.ptr(b_box), L.ptr(b_cls), L.ptr(b_slot), n_b,
+                                    b_rows, n_frames, metric, int(bool(distinguish_class)), L.ptr(pairs), n_pairs, L.ptr(rows), L.stream())
+    L.check(rc, 'dz_traj_pair_rows')
+    return rows
+
+
 PROFILER = None
 
 

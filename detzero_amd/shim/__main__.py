@@ -1,6 +1,7 @@
 """``python -m detzero_amd.shim``                      prints the two directories to put on PYTHONPATH;
 ``python -m detzero_amd.shim <script.py> [args ...]``  runs one of the reference's tools (detection/tools/test.py,
-refining/tools/test.py, tracking/tools/run_track.py) unchanged, from the current directory, with the shim packages installed."""
+refining/tools/test.py, tracking/tools/run_track.py with any --split, tracking/tools/eval_track.py) unchanged, from the current
+directory, with the shim packages installed."""
 import os
 import runpy
 import sys

@@ -187,12 +187,8 @@ TRACK_EVENTS = {
 }
 
 
-def synth_track_sequence(seed, n_frames=24, n_objects=20, origin=(3000.0, -2000.0, 40.0), events=None, sequence_name='synthetic'):
-    """One sequence of processed detection frames as the tracker takes them: ``{str(sample_idx): frame}`` with float32
-    ``boxes_global`` (N,7) in global coordinates around ``origin``, ``name``, ``score``, ``num_points`` and ``pose``.  Objects sit on a
-    16 m lattice and move along their heading: vehicles parked, crawling (below the tracker's speed gate) or driving, pedestrians,
-    cyclists.  ``events`` (see TRACK_EVENTS) scripts gaps, late starts, low scores, near-duplicates and false positives."""
-    rng = np.random.default_rng(seed)
+def _track_objects(rng, n_objects, origin, events):
+    """The first draws of a tracker sequence: the objects' classes, headings, sizes, start points and velocities."""
     ev = {'missing': {}, 'late': {}, 'low': {}, 'chain': {}, 'dup': {}, 'false_pos': [], 'empty': []}
     ev.update(events or {})
     sizes = {0: (4.6, 2.0, 1.7), 1: (0.8, 0.8, 1.75), 2: (1.8, 0.7, 1.6)}
@@ -207,6 +203,43 @@ def synth_track_sequence(seed, n_frames=24, n_objects=20, origin=(3000.0, -2000.
     start = np.array(origin)[None, :] + np.stack([(np.arange(n_objects) % side) * 16.0, (np.arange(n_objects) // side) * 16.0,
                                                    rng.uniform(-0.5, 0.5, size=n_objects)], axis=1)
     vel = np.stack([np.cos(heading), np.sin(heading), np.zeros(n_objects)], axis=1) * speed[:, None]
+    return ev, sizes, cls, heading, size, start, vel
+
+
+def synth_track_ground_truth(seed, n_frames=24, n_objects=20, origin=(3000.0, -2000.0, 40.0), events=None, sequence_name='synthetic'):
+    """The ground truth of ``synth_track_sequence`` with the same arguments (it replays that function's first draws): the objects'
+    noise-free boxes in every frame as ``waymo_infos``-style records ``{str(sample_idx): info}`` with ``annos`` (name, obj_ids
+    'obj_<k>', gt_boxes_global (N,9) [box7, vx, vy], gt_boxes_lidar (N,9) through the inverse pose, difficulty 0, num_points_in_gt
+    100), ``pose``, ``sequence_name`` and ``sample_idx``.  ``events`` only matter where they fix an object's class and motion
+    (chain, late); gaps, duplicates and false positives are detection noise and leave the ground truth alone."""
+    from .track_adapter import transform_boxes3d
+    rng = np.random.default_rng(seed)
+    _, _, cls, heading, size, start, vel = _track_objects(rng, n_objects, origin, events)
+    out = {}
+    for f in range(n_frames):
+        pose = np.eye(4)
+        pose[:3, 3] = np.array(origin) + np.array([0.5 * f, 0.0, 0.0])
+        centre = start + vel * (0.1 * f)
+        boxes = np.concatenate([centre, size, heading[:, None], vel[:, :2]], axis=1).astype(np.float32)
+        lidar = boxes.copy()
+        lidar[:, :7] = transform_boxes3d(boxes[:, :7], pose, inverse=True)
+        out[str(f)] = {
+            'annos': {'name': np.array([TRACK_CLASSES[c] for c in cls], dtype='<U10'),
+                      'obj_ids': np.array(['obj_%d' % k for k in range(n_objects)]),
+                      'gt_boxes_global': boxes, 'gt_boxes_lidar': lidar,
+                      'difficulty': np.zeros(n_objects, dtype=np.int64), 'num_points_in_gt': np.full(n_objects, 100, dtype=np.int64)},
+            'pose': pose, 'sequence_name': sequence_name, 'sample_idx': f,
+        }
+    return out
+
+
+def synth_track_sequence(seed, n_frames=24, n_objects=20, origin=(3000.0, -2000.0, 40.0), events=None, sequence_name='synthetic'):
+    """One sequence of processed detection frames as the tracker takes them: ``{str(sample_idx): frame}`` with float32
+    ``boxes_global`` (N,7) in global coordinates around ``origin``, ``name``, ``score``, ``num_points`` and ``pose``.  Objects sit on a
+    16 m lattice and move along their heading: vehicles parked, crawling (below the tracker's speed gate) or driving, pedestrians,
+    cyclists.  ``events`` (see TRACK_EVENTS) scripts gaps, late starts, low scores, near-duplicates and false positives."""
+    rng = np.random.default_rng(seed)
+    ev, sizes, cls, heading, size, start, vel = _track_objects(rng, n_objects, origin, events)
     out = {}
     for f in range(n_frames):
         rows = []         # (box7, class, score, points)

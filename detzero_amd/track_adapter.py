@@ -43,6 +43,45 @@ def dict_to_sequence_list(data):
     return [frame for seq in data.values() for frame in seq.values()]
 
 
+def tracklets_to_frames(data_dict):
+    """``{'source': {track id: track}, 'reference': {sample_idx: frame}}`` -> one record per reference frame, in the reference's
+    key order, with the tracks that have a box there in ascending id order (data_utils.py:33-76): sequence_name, sample_idx,
+    obj_ids, name, boxes_lidar (N,7) f32, score, pose.  A track without ``boxes_lidar`` gets it from ``boxes_global`` through the
+    inverse of the frame's pose, one box at a time as the reference does.  A frame that no track visits has empty arrays."""
+    source, reference = data_dict['source'], data_dict['reference']
+    frame_objects, row_of = {}, {}
+    for obj_id, obj in source.items():
+        rows = row_of[obj_id] = {}
+        for at, sample_idx in enumerate(obj['sample_idx']):
+            frame_objects.setdefault(sample_idx, set()).add(obj_id)
+            rows.setdefault(sample_idx, at)         # the first row of a sample_idx, as the reference's np.where(...)[0][0]
+    out = []
+    for frm_id in list(reference.keys()):
+        pose = reference[frm_id]['pose']
+        to_lidar = None                 # the frame's inverse pose, made once: what transform_boxes3d(..., inverse=True) makes per box
+        object_ids = np.array(sorted(frame_objects.get(frm_id, ())))
+        n = len(object_ids)
+        boxes_lidar = np.zeros((n, 7), dtype=np.float32)
+        boxes_global = np.zeros((n, 7), dtype=np.float32)
+        score = np.zeros(n, dtype=np.float32)
+        name = np.full(n, None, dtype=object)
+        for k, obj_id in enumerate(object_ids):
+            obj = source[obj_id]
+            at = row_of[obj_id][frm_id]
+            if 'boxes_lidar' in obj:
+                boxes_lidar[k] = obj['boxes_lidar'][at, :7]
+            else:
+                boxes_global[[k]] = obj['boxes_global'][[at], :7]
+                if to_lidar is None:
+                    to_lidar = get_inverse_transform_mat(pose)
+                boxes_lidar[k] = transform_boxes3d(boxes_global[[k]], to_lidar).reshape(-1)
+            score[k] = obj['score'][at]
+            name[k] = obj['name'][at]
+        out.append({'sequence_name': reference[frm_id]['sequence_name'], 'sample_idx': frm_id, 'obj_ids': object_ids, 'name': name,
+                    'boxes_lidar': boxes_lidar, 'score': score, 'pose': pose})
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # geometry (transform_utils.py)
 # ------------------------------------------------------------------------------------------------

@@ -26,8 +26,10 @@ Arithmetic is fp32, which is what the reference computes when its detections are
 transform_to_global produces) are rounded to fp32 when a frame is uploaded.  The size and heading of a track equal columns 3:7 of
 its box wherever the reference reads them, so the table stores the box only.
 
-Not covered (DetZeroHipError naming it): FILTER.NAME AB3DMOT, DISTANCE_METHOD IoU2D, and assign mode (every split but 'test':
-``assign_track_target``) - run with ``--split test``.
+Assign mode (every split but 'test') matches each sequence's tracks to the ground truth: track_assign.py, on the trajectory-pair
+kernel (csrc/traj_pair.hip).
+
+Not covered (DetZeroHipError naming it): FILTER.NAME AB3DMOT and DISTANCE_METHOD IoU2D.
 """
 import os
 import pickle
@@ -546,17 +548,27 @@ def _banner(text, total=100):
     return text.center(max(total, len(text)), '-')
 
 
-def run_model(model, dataloader, dataset, workers, cfgs=None, logger=None):
+def run_model(model, dataloader, dataset, workers, cfgs=None, logger=None, assign_ops=None):
     """Tracks every sequence of every batch, one after another in this process (``workers`` is accepted for the reference's
-    signature; no process pool ever opens the GPU), and writes tracking-<split>-<time>.pkl and drop-<split>-<time>.pkl."""
+    signature; no process pool ever opens the GPU), and writes tracking-<split>-<time>.pkl and drop-<split>-<time>.pkl.  In assign
+    mode (every split but 'test') each sequence's tracks are matched to the ground truth (track_assign.assign_track_target, with
+    ``cfgs.REFINING.IOU_THRESHOLDS``) and the tracking pickle holds the ``{'label', 'unlabel'}`` dicts instead (models/__init__.py:26-56).
+    ``assign_ops`` = the ops object of the assignment (default: track_assign.HipTrajOps)."""
     if dataset.assign_mode:
-        raise DetZeroHipError('assign mode (split %r: assign_track_target on ground truth) is not provided by the HIP tracker; '
-                              'run with --split test' % getattr(dataset, 'split', None))
+        from . import track_assign
+        refining = cfgs.get('REFINING', None) if cfgs is not None else None
+        iou_thresholds = refining.get('IOU_THRESHOLDS', None) if refining is not None else None
+        if iou_thresholds is None:
+            raise DetZeroHipError('assign mode (split %r): assign_track_target needs cfgs.REFINING.IOU_THRESHOLDS; pass the tracker '
+                                  'config, or run with --split test' % getattr(dataset, 'split', None))
     if logger is not None:
         logger.info(_banner('Running Tracking Module!'))
     track_data, drop_data = {}, {}
     for seq_names, data_dicts in dataloader:
         outputs = [model.forward(seq) for seq in data_dicts['detection']]
+        if dataset.assign_mode:
+            outputs = [track_assign.assign_track_target(item, iou_thresholds=iou_thresholds, ops=assign_ops)
+                       for item in zip(data_dicts['detection'], outputs, data_dicts['gt'])]
         track_data.update(dict(zip(seq_names, outputs)))
         drop_data.update(dict(zip(seq_names, data_dicts['det_drop'])))
     with open(dataset.get_track_path(), 'wb') as f:
@@ -592,6 +604,7 @@ class WaymoTrackDataset:
         self.track_module_path['det_drop'] = os.path.join(track_path, '-'.join(['drop', split, log_time]))
         self.track_module_path['detection'] = data_path
         self.gt_path = os.path.join(self.root_path, 'waymo_infos_%s.pkl' % split)
+        self.gt_infos = None
         with open(data_path, 'rb') as f:
             raw = pickle.load(f)
         if isinstance(raw, list):
@@ -608,9 +621,23 @@ class WaymoTrackDataset:
     def __len__(self):
         return len(self.seq_name_list)
 
+    def _load_gt_infos(self):
+        """waymo_infos_<split>.pkl, read at the first item of an assign-mode dataset rather than in the constructor (the
+        reference's init_infos reads it there): building a dataset for its paths or its mode needs no ground truth."""
+        with open(self.gt_path, 'rb') as f:
+            gt_infos = track_adapter.sequence_list_to_dict(pickle.load(f))
+        if len(gt_infos.keys()) != len(self.seq_name_list):
+            raise ValueError('Ground-truth infomation loading falied.')
+        self.gt_infos = [gt_infos[s] for s in self.seq_name_list]
+
     def __getitem__(self, idx):
         det, drop = self.data_processor.forward(data_dict=self.seq_det_infos[idx])
-        return self.seq_name_list[idx], {'detection': det, 'det_drop': drop}
+        data_dict = {'detection': det, 'det_drop': drop}
+        if self.assign_mode:
+            if self.gt_infos is None:
+                self._load_gt_infos()
+            data_dict['gt'] = self.gt_infos[idx]
+        return self.seq_name_list[idx], data_dict
 
     @staticmethod
     def collate_batch(batch_list):

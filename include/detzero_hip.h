@@ -897,6 +897,32 @@ int dz_track_compact(const dz_track_table *src, int n, const int *removed, int d
 /* info() of rows [0, n) (kalman_filter.py:61-72) as rows [log_n, log_n + n) of the row buffer `log`, frame ordinal `frame`. */
 int dz_track_log(const dz_track_table *t, int n, int frame, int *log, long log_n, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Trajectory-pair table of one sequence (csrc/traj_pair.hip): the sums and counts that assign_track_target
+ * (tracking/.../tracking_modules/target_assign.py:44-75) and TrackRecall.eval_single_seq (utils/track_recall.py:187-203 through
+ * track_calculation.py:84-123) both take per (ground-truth trajectory, track) pair over the frames the two share.
+ * Side a = ground-truth trajectories, side b = tracks.
+ *   a_box (a_rows,7) f32, a_cls (a_rows) i32 class codes in [0, n_cls).
+ *   a_slot (n_frames, n_a) i32, FRAME-MAJOR: a_slot[f * n_a + i] = row of trajectory i at frame ordinal f, or -1 when it has no
+ *   box there.  The same for b.  A slot outside [-1, rows) is never followed (the frame counts as absent).
+ *   For every (i, j), walking f = 0 .. n_frames-1 ASCENDING, at frames where both slots are >= 0:
+ *     v = metric(a row, b row); distinguish_class && classes differ -> v = 0
+ *     n_same += 1; sum_all += v            (fp32, one plain add per frame, in frame order: no atomics, the same bytes on every run)
+ *     v >= thr[class of the a row] -> n_hit += 1; sum_hit += v
+ *   out: sum_all, sum_hit f32 (n_a, n_b); n_hit, n_same i32 (n_a, n_b).
+ * metric: DZ_TRACK_AFF_IOU_BEV (v = element of dz_boxes_iou_bev bit for bit) or DZ_BOXM_IOU3D (of dz_boxes_pairwise_metric).
+ * h_thr: host array of n_cls (1..DZ_TRACK_MAX_CLASSES) thresholds, every one > 0.  n_a or n_b == 0: no launch, DZ_OK.
+ * DZ_ERR_INVALID: another metric, a threshold <= 0, a negative size, n_frames * n_a, n_frames * n_b, rows * 7 or n_a * n_b >= 2^31. */
+int dz_traj_pair_table(const float *a_box, const int *a_cls, const int *a_slot, int n_a, int a_rows, const float *b_box,
+                       const int *b_cls, const int *b_slot, int n_b, int b_rows, int n_frames, int metric, int distinguish_class,
+                       const float *h_thr, int n_cls, float *sum_all, float *sum_hit, int *n_hit, int *n_same, void *stream);
+/* Per-frame rows of listed pairs: pairs (n_pairs,2) i32 on the device, [i, j]; rows (n_pairs, n_frames) f32 = the masked v above at
+ * the frames the pair shares, 0 elsewhere and for a pair outside the table (the iou_mat_dict[frame][gt, track] the reference reads
+ * at target_assign.py:104-111).  n_pairs or n_frames == 0: no launch.  DZ_ERR_INVALID as above and for n_pairs * n_frames >= 2^31. */
+int dz_traj_pair_rows(const float *a_box, const int *a_cls, const int *a_slot, int n_a, int a_rows, const float *b_box,
+                      const int *b_cls, const int *b_slot, int n_b, int b_rows, int n_frames, int metric, int distinguish_class,
+                      const int *pairs, int n_pairs, float *rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
