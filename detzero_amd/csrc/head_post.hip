@@ -20,6 +20,7 @@
 #pragma clang fp contract(off)
 
 #include "box_geom.h"
+#include "pib_test.h"
 
 namespace dz {
 
@@ -439,7 +440,7 @@ __global__ __launch_bounds__(NT) void k_decode_selected(DecodeArgs a) {
 __global__ __launch_bounds__(256) void k_points_in_boxes(const float *__restrict__ boxes, const float *__restrict__ pts,
                                                          int t, int m, int *__restrict__ mask) {
     // block = 256 points of one batch item; boxes staged in LDS in chunks of 64 with cos/sin hoisted
-    __shared__ float sb[64 * 9];
+    __shared__ float sb[PIB_STAGE_BOXES * PIB_BOX_FLOATS];
     const int b = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const float *bx = boxes + (size_t)b * t * 7;
@@ -453,24 +454,13 @@ __global__ __launch_bounds__(256) void k_points_in_boxes(const float *__restrict
         __syncthreads();
         if ((int)threadIdx.x < nb) {
             const float *q = bx + (size_t)(base + threadIdx.x) * 7;
-            float *d = sb + threadIdx.x * 9;
-            for (int j = 0; j < 7; ++j) d[j] = q[j];
-            d[7] = cosf(-q[6]);
-            d[8] = sinf(-q[6]);
+            pib_stage_box(q, sb + threadIdx.x * PIB_BOX_FLOATS);
         }
         __syncthreads();
         if (i < m) {
             for (int k = 0; k < nb; ++k) {
-                const float *q = sb + k * 9;
-                int in = 0;
-                if (!((double)fabsf(z - q[2]) > (double)q[5] / 2.0)) {
-                    const float sx = x - q[0], sy = y - q[1];
-                    const float lx = sx * q[7] + sy * (-q[8]);
-                    const float ly = sx * q[8] + sy * q[7];
-                    const bool inx = (double)fabsf(lx) < (double)q[3] / 2.0 + (double)1e-5f;
-                    const bool iny = (double)fabsf(ly) < (double)q[4] / 2.0 + (double)1e-5f;
-                    in = (inx && iny) ? 1 : 0;
-                }
+                const float *q = sb + k * PIB_BOX_FLOATS;
+                const int in = pib_inside(x, y, z, q) ? 1 : 0;
                 mask[((size_t)b * t + base + k) * m + i] = in;
             }
         }
@@ -484,7 +474,7 @@ __global__ __launch_bounds__(256) void k_points_in_boxes(const float *__restrict
 // and one gather writes every object's points back to back; per-object offsets are the ranks at the row starts.
 __global__ __launch_bounds__(256) void k_points_in_boxes_bits(const float *__restrict__ boxes, const float *__restrict__ pts,
                                                               int t, int m, int row_words, uint32_t *__restrict__ bitmap) {
-    __shared__ float sb[64 * 9];
+    __shared__ float sb[PIB_STAGE_BOXES * PIB_BOX_FLOATS];
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     float x = 0.f, y = 0.f, z = 0.f;
@@ -494,21 +484,12 @@ __global__ __launch_bounds__(256) void k_points_in_boxes_bits(const float *__res
         __syncthreads();
         if ((int)threadIdx.x < nb) {
             const float *q = boxes + (size_t)(base + threadIdx.x) * 7;
-            float *d = sb + threadIdx.x * 9;
-            for (int j = 0; j < 7; ++j) d[j] = q[j];
-            d[7] = cosf(-q[6]);
-            d[8] = sinf(-q[6]);
+            pib_stage_box(q, sb + threadIdx.x * PIB_BOX_FLOATS);
         }
         __syncthreads();
         for (int k = 0; k < nb; ++k) {
-            const float *q = sb + k * 9;
-            bool in = false;
-            if (i < m && !((double)fabsf(z - q[2]) > (double)q[5] / 2.0)) {       // same test as k_points_in_boxes
-                const float sx = x - q[0], sy = y - q[1];
-                const float lx = sx * q[7] + sy * (-q[8]);
-                const float ly = sx * q[8] + sy * q[7];
-                in = ((double)fabsf(lx) < (double)q[3] / 2.0 + (double)1e-5f) && ((double)fabsf(ly) < (double)q[4] / 2.0 + (double)1e-5f);
-            }
+            const float *q = sb + k * PIB_BOX_FLOATS;
+            const bool in = i < m && pib_inside(x, y, z, q);                       // same test as k_points_in_boxes
             const unsigned long long bits = __ballot(in);
             if (lane == 0) {
                 uint32_t *w = bitmap + (size_t)(base + k) * row_words + (i >> 5);
@@ -523,7 +504,7 @@ __global__ __launch_bounds__(256) void k_points_in_boxes_bits(const float *__res
 // test, one popcount of the ballot per wavefront and box, one atomicAdd per wavefront that saw a point - no (T, M) mask at all
 __global__ __launch_bounds__(256) void k_points_in_boxes_count(const float *__restrict__ boxes, const float *__restrict__ pts,
                                                                int t, int m, int *__restrict__ counts) {
-    __shared__ float sb[64 * 9];
+    __shared__ float sb[PIB_STAGE_BOXES * PIB_BOX_FLOATS];
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     float x = 0.f, y = 0.f, z = 0.f;
@@ -533,21 +514,12 @@ __global__ __launch_bounds__(256) void k_points_in_boxes_count(const float *__re
         __syncthreads();
         if ((int)threadIdx.x < nb) {
             const float *q = boxes + (size_t)(base + threadIdx.x) * 7;
-            float *d = sb + threadIdx.x * 9;
-            for (int j = 0; j < 7; ++j) d[j] = q[j];
-            d[7] = cosf(-q[6]);
-            d[8] = sinf(-q[6]);
+            pib_stage_box(q, sb + threadIdx.x * PIB_BOX_FLOATS);
         }
         __syncthreads();
         for (int k = 0; k < nb; ++k) {
-            const float *q = sb + k * 9;
-            bool in = false;
-            if (i < m && !((double)fabsf(z - q[2]) > (double)q[5] / 2.0)) {       // same test as k_points_in_boxes
-                const float sx = x - q[0], sy = y - q[1];
-                const float lx = sx * q[7] + sy * (-q[8]);
-                const float ly = sx * q[8] + sy * q[7];
-                in = ((double)fabsf(lx) < (double)q[3] / 2.0 + (double)1e-5f) && ((double)fabsf(ly) < (double)q[4] / 2.0 + (double)1e-5f);
-            }
+            const float *q = sb + k * PIB_BOX_FLOATS;
+            const bool in = i < m && pib_inside(x, y, z, q);                       // same test as k_points_in_boxes
             const unsigned long long bits = __ballot(in);
             if (lane == 0 && bits) atomicAdd(&counts[base + k], __popcll(bits));
         }

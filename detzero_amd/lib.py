@@ -21,6 +21,7 @@ class DetZeroHipError(RuntimeError):
 
 
 c_int, c_float, c_size_t, c_void_p, c_double = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_double
+c_longlong = ctypes.c_longlong
 _I3 = c_int * 3
 _F3 = c_float * 3
 _F6 = c_float * 6
@@ -229,6 +230,11 @@ _SIGS = {
     'dz_crop_points_workspace_bytes': (c_size_t, [c_int] * 3),
     'dz_crop_points_in_boxes': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_void_p, c_size_t, c_void_p]),
+    'dz_seq_crop_chunk_points': (c_int, []),
+    'dz_seq_crop_count': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_longlong, c_void_p, c_longlong, c_void_p]),
+    'dz_seq_crop_fill': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p]),
     'dz_mha_core': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
                             c_void_p]),
     'dz_linear_forward': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,

@@ -61,6 +61,43 @@ class PackedTracks:
         self.obj_box_offsets = up(obj_off)
         self.obj_cls = up(np.asarray(self.classes, dtype=np.int32))
 
+    @classmethod
+    def from_crop(cls, crop, boxes_global, scores, names):
+        """The same batch from a device crop (object_crop.crop_sequence with an OBJECT-MAJOR rank: segment = box, the boxes of object 0
+        in frame order, then object 1, ...): the points never leave the device, only the per-box counts come to the host.
+        boxes_global / scores / names: per object, what the constructor reads from a track's keys of those names."""
+        self = cls.__new__(cls)
+        dev = crop.rows.device
+        self.device = dev
+        self.batch = len(boxes_global)
+        if self.batch == 0:
+            raise L.DetZeroHipError('PackedTracks: empty batch of object tracks')
+        boxes = [np.asarray(b, dtype=np.float64)[:, :7] for b in boxes_global]
+        self.box_num = [b.shape[0] for b in boxes]
+        for b, s in zip(boxes, scores):
+            if b.shape[0] != len(s):
+                raise L.DetZeroHipError('object track with %d boxes, %d scores' % (b.shape[0], len(s)))
+        if sum(self.box_num) != crop.num_boxes:
+            raise L.DetZeroHipError('PackedTracks.from_crop: %d boxes, %d crop segments' % (sum(self.box_num), crop.num_boxes))
+        obj_off = np.zeros(self.batch + 1, dtype=np.int32)
+        np.cumsum(self.box_num, out=obj_off[1:])
+        flat = crop.counts()
+        self.counts = [[int(n) for n in flat[obj_off[i]:obj_off[i + 1]]] for i in range(self.batch)]
+        self.obj_box_start = obj_off[:-1].tolist()
+        self.scores = [np.asarray(s) for s in scores]
+        self.classes = [CLASS_ID[n] if isinstance(n, str) else int(n) for n in names]
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self.pts = crop.rows.contiguous() if crop.total else up(np.zeros((1, 4)))
+        self.box_offsets = crop.offsets.to(torch.int32).contiguous()
+        self.traj_host = np.concatenate(boxes, axis=0) if boxes else np.zeros((1, 7))
+        self.traj = up(self.traj_host)
+        self.score = up(np.concatenate(self.scores).astype(np.float64) if boxes else np.zeros(1))
+        self.obj_box_offsets = up(obj_off)
+        self.obj_cls = up(np.asarray(self.classes, dtype=np.int32))
+        return self
+
 
 class DeviceDraw:
     """Pass as `rng` to grm_features / prm_features / crm_features to draw the fixed-size selections on the device

@@ -1218,6 +1218,129 @@ def crop_points_in_boxes_nosync(xyz, boxes, payload, cap):
     return out, index, offsets, d_total
 
 
+def seq_crop_chunk_points():
+    """Points per chunk of the sequence crop (one workgroup of dz_seq_crop_count / dz_seq_crop_fill)."""
+    return int(L.load().dz_seq_crop_chunk_points())
+
+
+class SeqCropPlan:
+    """Checked geometry of one sequence crop (seq_crop_plan): host arrays, all int32.  `upload(device)` makes the device copies."""
+
+    def __init__(self, m, nb, pt_off, box_off, rank, row_off, chunk_frame, chunk_first):
+        self.m, self.nb, self.n_frames = int(m), int(nb), len(pt_off) - 1
+        self.pt_off, self.box_off, self.rank, self.row_off = pt_off, box_off, rank, row_off
+        self.chunk_frame, self.chunk_first = chunk_frame, chunk_first
+        self.n_chunks, self.n_entries = int(chunk_frame.shape[0]), int(row_off[-1])
+        self.dev = None
+
+    def upload(self, device):
+        if self.dev is None or self.dev[0] != device:
+            names = ('pt_off', 'box_off', 'rank', 'row_off', 'chunk_frame', 'chunk_first')
+            self.dev = (device, {k: torch.from_numpy(getattr(self, k)).to(device) for k in names})
+        return self.dev[1]
+
+
+def seq_crop_rank(rank, nb):
+    """rank (or None for the identity) as a checked int64 permutation of 0..nb-1; DetZeroHipError otherwise."""
+    if rank is None:
+        return np.arange(nb, dtype=np.int64)
+    rk = np.asarray(rank)
+    if rk.ndim != 1 or rk.shape[0] != nb or rk.dtype.kind not in 'iu':
+        raise L.DetZeroHipError('seq_crop: rank must be a 1-D integer array of %d entries' % nb)
+    rk = rk.astype(np.int64)
+    if nb and (rk.min() < 0 or rk.max() >= nb or (np.bincount(rk, minlength=nb) != 1).any()):
+        raise L.DetZeroHipError('seq_crop: rank is not a permutation of 0..%d' % (nb - 1))
+    return rk
+
+
+def seq_crop_plan(pt_off, box_off, rank, m, nb, chunk=None):
+    """Host side of the sequence crop: checks pt_off / box_off (F+1 ascending offsets from 0 to m / nb) and rank (a permutation of
+    0..nb-1, or None for the identity), then lays out the chunks (`chunk` consecutive points of one frame that has boxes) and the count
+    table (row rank[b] = one entry per chunk of box b's frame).  Raises DetZeroHipError on anything the kernels could not follow safely:
+    nothing is launched from an unchecked array.  No device is touched (`chunk` defaults to the library's chunk size)."""
+    def bad(msg):
+        raise L.DetZeroHipError('seq_crop: ' + msg)
+    m, nb = int(m), int(nb)
+    if m < 0 or nb < 0:
+        bad('negative size (m=%d, boxes=%d)' % (m, nb))
+    if m >= 2 ** 31 or nb >= 2 ** 31:
+        bad('%d points / %d boxes reach 2^31' % (m, nb))
+    offs = []
+    for name, off, end in (('pt_off', pt_off, m), ('box_off', box_off, nb)):
+        o = np.asarray(off)
+        if o.ndim != 1 or o.shape[0] < 1 or o.dtype.kind not in 'iu':
+            bad('%s must be a 1-D integer array of F+1 entries' % name)
+        o = o.astype(np.int64)
+        if o[0] != 0 or (np.diff(o) < 0).any():
+            bad('%s does not ascend from 0' % name)
+        if o[-1] != end:
+            bad('%s ends at %d, not at %d' % (name, o[-1], end))
+        offs.append(o)
+    p_off, b_off = offs
+    if p_off.shape[0] != b_off.shape[0]:
+        bad('pt_off has %d frames, box_off %d' % (p_off.shape[0] - 1, b_off.shape[0] - 1))
+    nf = p_off.shape[0] - 1
+    rk = seq_crop_rank(rank, nb)
+    chunk = int(chunk) if chunk is not None else seq_crop_chunk_points()
+    n_pts, n_box = np.diff(p_off), np.diff(b_off)
+    nch = np.where(n_box > 0, (n_pts + chunk - 1) // chunk, 0)              # frames without boxes (or points) have no chunk
+    chunk_first = np.zeros(nf + 1, dtype=np.int64)
+    np.cumsum(nch, out=chunk_first[1:])
+    frames = np.arange(nf, dtype=np.int64)
+    row_len = np.zeros(nb, dtype=np.int64)
+    row_len[rk] = np.repeat(nch, n_box)
+    row_off = np.zeros(nb + 1, dtype=np.int64)
+    np.cumsum(row_len, out=row_off[1:])
+    if row_off[-1] >= 2 ** 31 or chunk_first[-1] >= 2 ** 31:
+        bad('%d count-table entries / %d chunks reach 2^31: split the sequence' % (row_off[-1], chunk_first[-1]))
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return SeqCropPlan(m, nb, i32(p_off), i32(b_off), i32(rk), i32(row_off), i32(np.repeat(frames, nch)), i32(chunk_first))
+
+
+def seq_crop(xyz, boxes, payload, plan, want_index=False):
+    """xyz (M,3) f32, boxes (B,7) f32 (enlarged, frame-major), payload (M,W) of any 4-byte-multiple dtype, plan = seq_crop_plan(...)
+    -> (out (total,W) payload dtype, index (total,) i32 or None, seg_off (B+1,) i32, total): the payload rows of the points inside
+    each box, segment rank[b] after segment, ascending point index within a segment.  Two launches around one prefix (torch.cumsum);
+    ONE host sync, for the total, and `out` is allocated exactly."""
+    lib = L.load()
+    L.require_cuda(xyz, boxes, payload)
+    if not isinstance(plan, SeqCropPlan):
+        raise L.DetZeroHipError('seq_crop: plan must come from seq_crop_plan')
+    if xyz.dtype != torch.float32 or boxes.dtype != torch.float32 or xyz.dim() != 2 or boxes.dim() != 2 or payload.dim() != 2:
+        raise L.DetZeroHipError('seq_crop: xyz (M,3) and boxes (B,7) must be float32, payload (M,W)')
+    if tuple(xyz.shape) != (plan.m, 3) or tuple(boxes.shape) != (plan.nb, 7) or payload.shape[0] != plan.m:
+        raise L.DetZeroHipError('seq_crop: %s points / %s boxes / %s payload rows do not match the plan (%d points, %d boxes)'
+                                % (tuple(xyz.shape), tuple(boxes.shape), payload.shape[0], plan.m, plan.nb))
+    row_bytes = payload.shape[1] * payload.element_size()
+    if row_bytes == 0 or row_bytes % 4:
+        raise L.DetZeroHipError('seq_crop: payload rows of %d bytes are no whole 32-bit words' % row_bytes)
+    dev = xyz.device
+    d = plan.upload(dev)
+    geom = (L.ptr(xyz), plan.m, L.ptr(d['pt_off']), L.ptr(boxes), plan.nb, L.ptr(d['box_off']), L.ptr(d['rank']), L.ptr(d['row_off']),
+            plan.n_frames, L.ptr(d['chunk_frame']), L.ptr(d['chunk_first']), plan.n_chunks)
+    index = None
+    if plan.n_entries == 0:
+        out = torch.empty((0, payload.shape[1]), dtype=payload.dtype, device=dev)
+        if want_index:
+            index = torch.empty((0,), dtype=torch.int32, device=dev)
+        return out, index, torch.zeros((plan.nb + 1,), dtype=torch.int32, device=dev), 0
+    counts = torch.zeros((plan.n_entries,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.dz_seq_crop_count(*geom, L.ptr(counts), plan.n_entries, L.stream()), 'dz_seq_crop_count')
+        incl = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(incl[-1].item())                                         # the one sync
+        if total >= 2 ** 31:
+            raise L.DetZeroHipError('seq_crop: %d kept rows reach 2^31: split the sequence' % total)
+        prefix = (incl - counts).to(torch.int32)
+        seg_off = torch.cat([prefix, incl[-1:].to(torch.int32)])[d['row_off'].long()].contiguous()
+        out = torch.empty((total, payload.shape[1]), dtype=payload.dtype, device=dev)
+        if want_index:
+            index = torch.empty((total,), dtype=torch.int32, device=dev)
+        L.check(lib.dz_seq_crop_fill(*geom, L.ptr(counts), L.ptr(prefix), plan.n_entries, L.ptr(payload), row_bytes // 4, L.ptr(out),
+                                     L.ptr(index), total, L.stream()), 'dz_seq_crop_fill')
+    return out, index, seg_off, total
+
+
 def mha_core(q, k, v, key_padding_mask, heads, scale, math=0):
     """q (B,Lq,E), k/v (B,Lk,E), mask (B,Lk) bool/uint8 or None -> (B,Lq,E).  math 0: exact fp32 (dz_mha_core); 1 / 2: operands as
     16-bit pairs on the 16-bit matrix cores (dz_mha_core_split).  The split cores stay within their bound (tests/test_gpu_refine_kernels.py:

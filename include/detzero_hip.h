@@ -617,6 +617,32 @@ int dz_crop_points_in_boxes(const float *xyz, int m, const float *boxes, int t, 
                             void *out, int *out_index, int *offsets, int *d_total, int cap, void *ws, size_t ws_bytes,
                             void *stream);
 
+/* Segmented object crop over the frames of a sequence (csrc/seq_crop.hip): the crop above for F frames at once, in two
+ * passes without a (T, M) bitmap and without a capacity.
+ *   xyz (m,3) f32: the points of all frames back to back; pt_off (n_frames+1) i32: first point of every frame;
+ *   boxes (nb,7) f32 (already enlarged), frame-major; box_off (n_frames+1) i32: first box of every frame;
+ *   rank (nb) i32: a permutation of 0..nb-1, the output segment of box b (identity = (frame, box) order);
+ *   A chunk is dz_seq_crop_chunk_points() consecutive points of one frame; only frames with boxes and points have chunks.
+ *   chunk_frame (n_chunks) i32: frame of every chunk, ascending; chunk_first (n_frames+1) i32: first chunk of every frame;
+ *   row_off (nb+1) i32: first entry of every segment's row in the count table - row rank[b] holds one entry per chunk
+ *   of box b's frame, row_off[nb] = n_entries.
+ * dz_seq_crop_count writes counts (n_entries) i32: points of the chunk inside the box.  The caller forms the exclusive
+ * prefix over counts (same shape) and its total: prefix[row_off[r]] is the first output row of segment r.
+ * dz_seq_crop_fill writes out (total, payload_words) 32-bit words: payload (m, payload_words) rows of the kept points,
+ * segment after segment, ascending point index within a segment; out_index (total) i32 or NULL: the source point.
+ * No atomics: the same bytes on every run.  The caller guarantees that rank is a permutation and that the offset arrays
+ * ascend and end at m / nb (ops.seq_crop_plan checks it); the kernels clamp what they read from them and write no row
+ * at or beyond total.  DZ_ERR_INVALID: a negative size, m / nb / n_chunks / n_entries / total >= 2^31, a null pointer
+ * with chunks to work on.  n_chunks == 0 (no frame, no boxes or no points) launches nothing. */
+int dz_seq_crop_chunk_points(void);
+int dz_seq_crop_count(const float *xyz, long long m, const int *pt_off, const float *boxes, long long nb, const int *box_off,
+                      const int *rank, const int *row_off, int n_frames, const int *chunk_frame, const int *chunk_first,
+                      long long n_chunks, int *counts, long long n_entries, void *stream);
+int dz_seq_crop_fill(const float *xyz, long long m, const int *pt_off, const float *boxes, long long nb, const int *box_off,
+                     const int *rank, const int *row_off, int n_frames, const int *chunk_frame, const int *chunk_first,
+                     long long n_chunks, const int *counts, const int *prefix, long long n_entries, const void *payload,
+                     int payload_words, void *out, int *out_index, long long total, void *stream);
+
 /* multi_head_attention_forward core (refining/detzero_refine/models/transformer/
  * multi_head_attention.py:207-288): q (B,Lq,E), k,v (B,Lk,E) already projected, E = heads*32;
  * key_padding_mask (B,Lk) u8 (1 = ignore) or NULL; out (B,Lq,E).  softmax(q*scale . k^T) . v */
