@@ -8,7 +8,10 @@
 // misses only m.l + l.m + l.l, at most 2^-26 of |x.w|: fp32-class arithmetic, in another accumulation order than k_conv2d.
 // Saturation: x is clamped to +-bf16-max (0x7F7F) before the FIRST rounding only (the rule of MathF16::split), so a finite fp32
 // near the top of the range gets no inf limb: the rest goes to m and l, and the sum stays exact.
-// Tiny values: for |x| < 2^-100 the l limb is a bf16 subnormal; whether the bf16 MFMA keeps subnormal inputs has not been measured.
+// Tiny values: for |x| < 2^-100 the l limb (below 2^-109 the m limb too) is a bf16 subnormal.  Measured on an MI355X: the bf16 MFMA
+// KEEPS subnormal inputs - with inputs of exponent [-120, -104] against one-hot weights every output equals (h + m + l) . w bit for
+// bit, none the value with those limbs flushed (test_subnormal_limbs_are_measured).  Below 2^-110 the split itself
+// stops being exact (bf16's quantum there is 2^-133): the result is then within 2^-133 |w| of x . w.
 //
 // No tensor format: activations stay the fp32 zero-bordered channel-last images of the f32 engine (same HBM bytes).  The scheme
 // is conv3x3_h.hip's: a 512-thread workgroup owns 8 rows x 32 columns of output pixels x BC output channels and keeps the tile's

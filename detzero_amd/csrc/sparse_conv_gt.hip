@@ -27,8 +27,10 @@
 //        l.h  h.l  m.m  m.h  h.m  h.h          (smallest first, the order of conv3x3_t.hip and sparse_conv_xt.hip)
 // added onto the element's ONE accumulator; dropped: m.l + l.m + l.l, at most 2^-26 of |x.w|.  A skipped tap would have added exact
 // zeros.  Two launches agree bit for bit.
-// Tiny values: for |x| < 2^-100 the l limb is a bf16 subnormal; whether the bf16 MFMA keeps subnormal inputs has not been measured
-//  - the tests keep their data inside exponents [-40, 16].
+// Tiny values: for |x| < 2^-100 the l limb (below 2^-109 the m limb too) is a bf16 subnormal.  Measured on an MI355X: the bf16 MFMA
+// KEEPS subnormal inputs - with inputs of exponent [-120, -104] against one-hot weights every output equals (h + m + l) . w bit for
+// bit, none the value with those limbs flushed (test_subnormal_limbs_are_measured).  Below 2^-110 the split itself
+// stops being exact (bf16's quantum there is 2^-133): the result is then within 2^-133 |w| of x . w.
 #include "hgemm.h"
 #include "limb3.h"
 

@@ -6,8 +6,10 @@
 // Why: per (tap, 32-channel fragment) k_spconv_xf issues 8 fp32 MFMAs of 64 cycles (512 cycles) for a 16-channel chunk; the six bf16
 // terms   l.h  h.l  m.m  m.h  h.m  h.h   (weight limb . input limb, smallest first - the order of conv3x3_t.hip)
 // are six MFMAs of 32 cycles (192 cycles) for the same chunk.  Dropped: m.l + l.m + l.l, at most 2^-26 of |x.w|.
-// Tiny values: for |x| < 2^-100 the l limb is a bf16 subnormal; whether the bf16 MFMA keeps subnormal inputs has not been measured
-//  - the tests keep their data inside exponents [-40, 16].
+// Tiny values: for |x| < 2^-100 the l limb (below 2^-109 the m limb too) is a bf16 subnormal.  Measured on an MI355X: the bf16 MFMA
+// KEEPS subnormal inputs - with inputs of exponent [-120, -104] against one-hot weights every output equals (h + m + l) . w bit for
+// bit, none the value with those limbs flushed (test_subnormal_limbs_are_measured).  Below 2^-110 the split itself
+// stops being exact (bf16's quantum there is 2^-133): the result is then within 2^-133 |w| of x . w.
 //
 // Everything the index decides is k_spconv_xf's, unchanged: the unit (WP x 32 rows = dz_spconv_x_tile_rows), the windows and the
 // zero row behind them, the gather-mode arm for a window longer than RCAP (same taps, same order), the packed-table decode, the

@@ -424,7 +424,7 @@ const char *dz_conv2d_variant_split(const dz_conv2d_desc *h_desc, int out_f32);
  * h + m + l with h = rn(x), m = rn(x - h), l = x - h - m (8 + 8 + 8 = 24 bits; x is clamped to +-bf16-max before the first rounding
  * only, so no limb is inf); a product is h.h + h.m + m.h + h.l + l.h + m.m, six bf16 MFMAs whose products are exact in fp32 - the
  * dropped terms are at most 2^-26 of |x.w|.  fp32-class results in another accumulation order than dz_conv2d_forward's.  For
- * |x| < 2^-100 the l limb is a bf16 subnormal; whether the matrix pipe keeps it has not been measured.
+ * |x| < 2^-100 the l limb is a bf16 subnormal; the matrix pipe keeps it (measured).
  *   desc->w = the weights split at plan time: (9, cout_pad, cin / 8, 3, 8) bf16 - per output-channel row and group of 8 input
  *   channels 16 bytes of h, 16 of m, 16 of l (ops.pack_weight_limb3).  Epilogue and write contract as dz_conv2d_forward.
  * dz_conv3x3_limb3_supported (host only, no GPU needed) is 1 exactly for kh == kw == 3, stride 1, groups 1, cin % 32 == 0,

@@ -1,4 +1,6 @@
-"""Every dense-convolution kernel instance against a float64 reference (csrc/conv2d.hip, conv2d_h.hip, conv3x3_h.hip).
+"""Every dense-convolution kernel instance against a float64 reference (csrc/conv2d.hip, conv2d_h.hip, conv3x3_h.hip; the bf16x3 engine
+of the f32 mode, k_conv3x3_t of csrc/conv3x3_t.hip, has its cases in tests/test_gpu_conv3x3_limb3.py and joins the production replay
+here: test_production_layers_on_the_bf16x3_engine).
 
 Which instance runs a layer depends on the launch's size, not only on the layer (conv2d_select, conv2d_h_select and
 conv3x3_h_variant score tile counts against the chip), so the cases here are chosen by shape: every case names the variant
@@ -168,17 +170,61 @@ def selected_variant(case):
     return lib.dz_conv2d_variant(ctypes.byref(d)).decode()
 
 
+LIMB3_VARIANTS = {'k_conv3x3_t<8x32x128>', 'k_conv3x3_t<8x32x64>'}
+
+
+def _limb3(case):
+    """The case runs on the bf16x3 engine of the f32 mode (production replay: the launches recorded with f32_engine='bf16x3')."""
+    return getattr(case, 'f32_engine', None) == 'bf16x3'
+
+
 def _launch(case, ptrs, math):
     lib = L.load()
     d = _cdesc(case.desc, ptrs)
     if case.sparse:
         d.in_row_channels, d.in_rows = case.desc['cin'] // 2, case.in_rows
-    if math:
+    if _limb3(case):
+        assert not math
+        rc = lib.dz_conv3x3_limb3_forward(ctypes.byref(d), L.stream())
+    elif math:
         rc = lib.dz_conv2d_forward_split(ctypes.byref(d), math, 1 if case.out_f32 else 0, L.stream())
     else:
         rc = lib.dz_conv2d_forward(ctypes.byref(d), L.stream())
     msg = lib.dz_last_error()
     return rc, (msg.decode() if msg else '')
+
+
+# the launch rule of the bf16x3 engine, restated (csrc/conv3x3_t.hip launch_t3; test_limb3_launch_rule_is_the_library_s reads the
+# constants back from the source): 32 workgroup slots per XCD; a layer of `nty` channel tiles that does not divide them and has at
+# least LIMB3_SPLIT_PAIR_TILES (pixel tile, channel tile) pairs runs as two launches over 2^k and nty - 2^k channel tiles
+LIMB3_SLOTS, LIMB3_SPLIT_PAIR_TILES = 32, 5000
+
+
+def limb3_launches(desc):
+    """(launches, pair tiles, workgroups per XCD of each launch) of dz_conv3x3_limb3_forward for a descriptor it supports."""
+    bc = 128 if desc['cout_pad'] % 128 == 0 else 64
+    nty = desc['cout_pad'] // bc
+    pair_tiles = desc['batch'] * -(-desc['wo'] // 32) * -(-desc['ho'] // 8) * nty
+    parts = [nty]
+    if LIMB3_SLOTS % nty != 0 and nty < LIMB3_SLOTS and pair_tiles >= LIMB3_SPLIT_PAIR_TILES:
+        a = 1
+        while a * 2 <= nty:
+            a *= 2
+        if LIMB3_SLOTS % a == 0 and LIMB3_SLOTS % (nty - a) == 0:
+            parts = [a, nty - a]
+    return len(parts), pair_tiles, [max(LIMB3_SLOTS // ny * ny, ny) for ny in parts]
+
+
+def test_limb3_launch_rule_is_the_library_s():
+    """limb3_launches restates launch_t3: its two constants are the source's, and the rule gives the head's 64 -> 384 layer two launches
+    from 5000 pair tiles on and one launch of 30 workgroups per XCD below."""
+    import os
+    src = open(os.path.join(os.path.dirname(os.path.abspath(L.__file__)), 'csrc', 'conv3x3_t.hip')).read()
+    assert 'const int slots = %d;' % LIMB3_SLOTS in src and 'pair_tiles >= %d)' % LIMB3_SPLIT_PAIR_TILES in src
+    d = dict(cout_pad=384, batch=7, ho=64, wo=960)
+    assert limb3_launches(d) == (2, 5040, [32, 32])
+    assert limb3_launches(dict(d, batch=1, ho=8 * 34 * 7 * 7, wo=32)) == (1, 4998, [30])
+    assert limb3_launches(dict(d, cout_pad=192)) == (2, 5040, [32, 32]) and limb3_launches(dict(d, cout_pad=256)) == (1, 3360, [32])
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -226,10 +272,14 @@ def run_case(case, dev, seed=None):
     """Launch `case` twice into sentinel-filled buffers; check determinism, the result against float64 and the sentinel outside
     the written region.  Returns (variant, worst normalised error)."""
     mode, math, dd = case.mode, ops.math_id(case.mode), case.desc
-    name = selected_variant(case)
+    if _limb3(case):
+        assert L.load().dz_conv3x3_limb3_supported(ctypes.byref(_cdesc(dd))) == 1, case.label
+        name = L.load().dz_conv3x3_limb3_variant(ctypes.byref(_cdesc(dd))).decode()
+    else:
+        name = selected_variant(case)
     if case.expect is not None:
         assert name == case.expect, (case.label, mode, name, case.expect)
-    assert name in ALL_VARIANTS[mode], (case.label, mode, name)
+    assert name in (LIMB3_VARIANTS if _limb3(case) else ALL_VARIANTS[mode]), (case.label, mode, name)
     gen = torch.Generator(device=dev)
     gen.manual_seed(zlib.crc32(('%s|%s' % (case.label, mode)).encode()) if seed is None else seed)
     B, ho, wo, cin, groups, cp = dd['batch'], dd['ho'], dd['wo'], dd['cin'], dd['groups'], dd['cout_pad']
@@ -264,7 +314,8 @@ def run_case(case, dev, seed=None):
         wk = ops.pack_weight_split(w32, sv, cout_mult=cp)                    # (groups, taps, cp, cin) pair16
         w64 = _decode(wk, mode).transpose(-1, -2)
     else:
-        wk = w32.contiguous()
+        # (bf16x3: the three limbs of a weight sum to it exactly - the reference is the fp32 operands')
+        wk = ops.pack_weight_limb3(w32[0]) if _limb3(case) else w32.contiguous()
         w64 = w32.double()
     w64 = w64.reshape(groups, kh, kw, cin, cp)
     nss = cp if phase else groups * cp
@@ -458,15 +509,22 @@ FRAMES = ('single', 'ref_batch', 'dense_group', 'sub_pass')
 
 
 @functools.lru_cache(maxsize=None)
-def production_cases(mode, frames):
+def production_cases(mode, frames, dense_engine='mfma32', full_head=False):
     """The dense layers FramePipeline.dense_stage launches for a pass of the 0.1 m Waymo detector (188 x 188 BEV),
     recorded as the descriptors det_modules.conv_layer hands to ops.conv2d (the images live on the meta device: nothing runs),
-    distinct geometries only.  Split modes read the first convolution's input as sparse rows (in_rowidx) with tile lists."""
+    distinct geometries only.  Split modes read the first convolution's input as sparse rows (in_rowidx) with tile lists.
+    dense_engine: the f32 mode's engine of the 3 x 3 stride-1 layers (centerpoint.set_dense_engine); a launch the detector hands
+    f32_engine='bf16x3' is recorded as such (case.f32_engine) and replayed through dz_conv3x3_limb3_forward.
+    full_head: the pass with FramePipeline.head_at_candidates off - the head writes full maps, so all six branches' hidden layer (64 ->
+    384) runs as one launch instead of the two score branches' (64 -> 128)."""
     from detzero_amd import centerpoint
     from detzero_amd.synth import VOXEL_SIZE_01
     from tests.util import make_model
     model, cfg, info = make_model(VOXEL_SIZE_01, seed=0)
+    centerpoint.set_dense_engine(model, dense_engine)
     pipe = centerpoint.FramePipeline(model, info, math=mode)
+    if full_head:
+        pipe.head_at_candidates = False
     nb = {'single': 1, 'ref_batch': 8, 'dense_group': pipe.dense_group, 'sub_pass': 32}[frames]
     stride = int(model.dense_head.feature_map_stride)
     gx, gy = int(info.grid_size[0]), int(info.grid_size[1])
@@ -475,8 +533,8 @@ def production_cases(mode, frames):
     meta = torch.device('meta')
     rec = []
 
-    def fake_conv2d(desc, math=0, out_f32=False, tiles=None):
-        rec.append((dict(desc), int(math), bool(out_f32), tiles is not None))
+    def fake_conv2d(desc, math=0, out_f32=False, tiles=None, f32_engine=None):
+        rec.append((dict(desc), int(math), bool(out_f32), tiles is not None, f32_engine))
 
     def fake_row_index(level, feat_rows, pad=1):
         return torch.empty((nb, h + 2 * pad, w + 2 * pad, 2), dtype=torch.int32, device=meta)
@@ -503,10 +561,10 @@ def production_cases(mode, frames):
     assert rec, 'dense_stage launched no convolution'
     cases, seen = [], set()
     skip = ('inp', 'out', 'w', 'scale', 'shift', 'in_rowidx', 'in_tiles')
-    for desc, math, out_f32, tiles in rec:
+    for desc, math, out_f32, tiles, f32_engine in rec:
         geo = {k: v for k, v in desc.items() if k not in skip}
         key = (tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in geo.items())), out_f32, tiles,
-               desc.get('scale') is not None, desc.get('shift') is not None)
+               desc.get('scale') is not None, desc.get('shift') is not None, f32_engine)
         if key in seen:
             continue
         seen.add(key)
@@ -518,9 +576,10 @@ def production_cases(mode, frames):
             geo['batch'], geo['ho'], geo['wo'], geo['cin'] * (1 if geo['phase_groups'] else geo['groups']),
             geo['g_cout'][0] if geo['phase_groups'] else sum(geo['g_cout'][:geo['groups']]),
             geo['kh'], geo['stride'], ' phases' if geo['phase_groups'] else '',
-            ' phase (%d, %d)' % (geo['out_dy'] - 1, geo['out_dx'] - 1) if geo['out_sy'] > 1 and not geo['phase_groups'] else '', ' sparse-in' if sparse else '', ' tiles' if tiles else '')
+            ' phase (%d, %d)' % (geo['out_dy'] - 1, geo['out_dx'] - 1) if geo['out_sy'] > 1 and not geo['phase_groups'] else '', ' sparse-in' if sparse else '', ' tiles' if tiles else '') + (' ' + f32_engine if f32_engine else '')
         cases.append(types.SimpleNamespace(label=label, mode=mode, desc=geo, out_f32=out_f32, scale=desc.get('scale') is not None,
-                                           shift=desc.get('shift') is not None, tiles=tiles, sparse=sparse, in_rows=in_rows, expect=None))
+                                           shift=desc.get('shift') is not None, tiles=tiles, sparse=sparse, in_rows=in_rows, expect=None,
+                                           f32_engine=f32_engine))
     return cases
 
 
@@ -530,6 +589,52 @@ def production_cases(mode, frames):
 def test_production_layers_vs_float64(mode, frames, device):
     cases = production_cases(mode, frames)
     print('\n  %s pass [%s]: %d distinct dense launches' % (frames, mode, len(cases)))
+    for c in cases:
+        run_case(c, device)
+    torch.cuda.empty_cache()
+
+
+def test_production_layers_recorded_for_the_bf16x3_engine():
+    """The f32 pass recorded with the dense engine 'bf16x3' (host only): the same layers as with 'mfma32', the 3 x 3 stride-1 ones handed
+    to the bf16x3 engine.  With the head at candidates (the default) no layer has three channel tiles; with full head maps the head's
+    64 -> 384 layer is among them - at dense_group frames above the two-launch threshold of launch_t3, at one frame below it."""
+    for frames in ('single', 'dense_group'):
+        plain, limb = production_cases('f32', frames), production_cases('f32', frames, 'bf16x3')
+        assert all(c.f32_engine is None for c in plain)
+        assert [c.desc for c in plain] == [c.desc for c in limb]
+        assert not any(limb3_launches(c.desc)[0] == 2 for c in limb if c.f32_engine)
+        limb = _bf16x3_production(frames)
+        on = [c for c in limb if c.f32_engine == 'bf16x3']
+        assert on and all(c.desc['kh'] == 3 and c.desc['stride'] == 1 and c.desc['groups'] == 1 for c in on)
+        assert all(c.f32_engine == 'bf16x3' for c in limb if c.desc['kh'] == 3 and c.desc['stride'] == 1 and c.desc['groups'] == 1 and c.desc['cout_pad'] % 64 == 0)
+        split = [c for c in on if limb3_launches(c.desc)[0] == 2]
+        print('  %s: %d of %d launches on the bf16x3 engine, %d as two launches' % (frames, len(on), len(limb), len(split)))
+        assert bool(split) == (frames == 'dense_group'), (frames, [(c.label, limb3_launches(c.desc)) for c in on])
+        assert all(c.desc['cout_pad'] == 384 for c in split)
+
+
+def _bf16x3_production(frames):
+    """Distinct launches of the f32 pass with the dense engine 'bf16x3': the default pass (head at candidates) and the pass with full
+    head maps."""
+    cases, seen = [], set()
+    for c in production_cases('f32', frames, 'bf16x3') + production_cases('f32', frames, 'bf16x3', True):
+        if c.label not in seen:
+            seen.add(c.label)
+            cases.append(c)
+    return cases
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('frames', ('single', 'dense_group'))
+def test_production_layers_on_the_bf16x3_engine(frames, device):
+    """test_production_layers_vs_float64 for the launches the f32 detector hands its bf16x3 dense engine (k_conv3x3_t), with the head at
+    candidates and with full head maps: the same float64 reference and bound.  At dense_group frames the full-map head's 384-channel
+    layer runs as launch_t3's two launches (asserted from the launcher's rule); the layers that stay on k_conv2d are the f32 row's of
+    test_production_layers_vs_float64."""
+    cases = [c for c in _bf16x3_production(frames) if c.f32_engine == 'bf16x3']
+    nsplit = sum(limb3_launches(c.desc)[0] == 2 for c in cases)
+    print('\n  %s pass [f32, bf16x3 dense engine]: %d distinct launches on k_conv3x3_t, %d of them as two launches' % (frames, len(cases), nsplit))
+    assert cases and (nsplit >= 1 or frames != 'dense_group'), (frames, [(c.label, limb3_launches(c.desc)) for c in cases])
     for c in cases:
         run_case(c, device)
     torch.cuda.empty_cache()

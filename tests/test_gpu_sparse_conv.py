@@ -1,5 +1,7 @@
 """Every sparse-convolution kernel instance against a float64 reference (csrc/sparse_conv.hip, sparse_conv_h.hip, sparse_conv_w.h,
-sparse_conv_x.hip, sparse_conv_xf.hip), the sparse counterpart of tests/test_gpu_dense_conv.py.
+sparse_conv_x.hip, sparse_conv_xf.hip and the bf16x3 x-run kernel k_spconv_xt of sparse_conv_xt.hip; the bf16x3 gather kernel k_spconv_gt
+of sparse_conv_gt.hip has its edge table in tests/test_gpu_spconv_gather_limb3.py and joins the detector-launch replay here), the sparse
+counterpart of tests/test_gpu_dense_conv.py.
 
 Which kernel runs a layer depends on its channels, on the form of its neighbour table (plain, packed, packed with x-run windows) and
 on whether the table comes with tile masks, so every case names the (instance, arm) the dispatch code must report for it and
@@ -20,6 +22,14 @@ Every launch goes twice into a buffer of (cap + TAIL) rows filled with the dense
 for word, rows < m lose it, the two launches agree bit for bit.  Input rows >= m_in and residual rows >= m are NaN (level buffers come
 from torch.empty: an absent neighbour must fetch zeros, never a row).  Every case runs with scale, shift, residual and ReLU all on, and
 with all of them off (null pointers, relu = 0).
+
+The bf16x3 kernels (engine keys 'xt', 'gt') read fp32 rows and limb weights that sum to the fp32 weights exactly, so their float64
+reference is the fp32 operands' and their bound BOUND['f32'].
+
+The three x-run families switch arm per (unit, z slab) at `window rows <= staging capacity`: the edges 'window=rcap' and 'window=rcap+1'
+run each of them on a constructed level (window_coords) whose longest window is exactly the capacity (the last direct-to-LDS run ends
+at the slot before the zero row) and exactly one row more (the smallest window of the gather-mode arm); the condition is asserted from
+the windows the library built.
 """
 import functools
 import json
@@ -57,7 +67,7 @@ LAYERS = ((16, 16, 'subm'), (16, 32, 'down'), (32, 32, 'subm'), (32, 64, 'down')
 # what the default build can launch: (instance [+ arm of k_spconv_h], arm of the case) per math mode
 #   fp32 gather: arm = layer kind; k_spconv_h: ring (tile masks given) / lds (tile_masks = NULL through the C ABI - the small-channel
 #   k_spconv_h tiles are reached this way too, k_spconv_w needs the masks); k_spconv_w: plain / packed table;
-#   x-run: tap-set order or not x staged / gather-mode windows
+#   x-run (k_spconv_x, k_spconv_xf, k_spconv_xt): tap-set order or not x staged / gather-mode windows
 # ------------------------------------------------------------------------------------------------------------------------
 ALL_VARIANTS = {m: set() for m in MODES}
 ALL_VARIANTS['f32'] |= {('k_spconv<128x16x16>', 'subm'), ('k_spconv<128x32x16>', 'down'), ('k_spconv<128x32x32>', 'subm'),
@@ -73,6 +83,7 @@ for _m in SPLIT:
 for _c in (32, 64, 128):
     for _arm in ('sort staged', 'sort gathermode', 'nosort staged', 'nosort gathermode'):
         ALL_VARIANTS['f32'].add(('k_spconv_xf<%d>' % _c, _arm))
+        ALL_VARIANTS['f32'].add(('k_spconv_xt<%d>' % _c, _arm))
         for _m in SPLIT:
             ALL_VARIANTS[_m].add(('k_spconv_x<%d>' % _c, _arm))
 
@@ -85,7 +96,11 @@ for _c in (32, 64, 128):
 M_EDGES = ('m=1', 'm=tile-1', 'm=tile', 'm=tile+1')
 EDGES_REQUIRED = M_EDGES + ('dead tiles', 'm=cap', 'overflow', 'zero', 'unequal', 'isolated')
 XCD_TILES = (1, 16, 17, 127, 128, 129)          # row tiles around the XCD deal of k_spconv_h (XRUN = 16 tiles x 8 XCDs)
-FAMILIES = ('k_spconv', 'k_spconv_h', 'k_spconv_w', 'k_spconv_x', 'k_spconv_xf')
+FAMILIES = ('k_spconv', 'k_spconv_h', 'k_spconv_w', 'k_spconv_x', 'k_spconv_xf', 'k_spconv_xt')
+XRUN_ENGINES = ('x', 'xf', 'xt')                # engine keys of the x-run families (pair16, fp32 MFMA, bf16x3)
+LIMB3_ENGINES = ('xt', 'gt')                    # engine keys whose weights are pack_weight_limb3(w, cout_mult=32)
+# the staging boundary of the x-run families: the longest (unit, slab) window of the level is exactly the staging capacity / one row more
+WINDOW_EDGES = ('window=rcap', 'window=rcap+1')
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -99,6 +114,8 @@ def expected_name(engine, cin, cout, kvol, masks):
         return 'k_spconv_x<%d>' % cout
     if engine == 'xf':
         return 'k_spconv_xf<%d>' % cout
+    if engine == 'xt':
+        return 'k_spconv_xt<%d>' % cout
     if engine == 'packed':
         return 'k_spconv_w<%dx%d>' % (cin, cout)
     cp = max(cout, 32)
@@ -118,6 +135,10 @@ def reported_name(engine, cin, cout, kvol, masks, cap):
         return lib.dz_spconv_x_variant(cin, cout).decode()
     if engine == 'xf':
         return lib.dz_spconv_x_f32_variant(cin, cout).decode()
+    if engine == 'xt':
+        return lib.dz_spconv_x_limb3_variant(cin, cout).decode()
+    if engine == 'gt':
+        return lib.dz_spconv_limb3_variant(cin, cout).decode()
     if engine == 'packed':
         return lib.dz_spconv_variant_split_packed(cin, cout).decode()
     return lib.dz_spconv_variant_split_arm(cin, cout, kvol, 1 if masks else 0, kvol * max(cap, 1) * 4).decode()
@@ -137,6 +158,13 @@ def family(name):
     return name[:name.index('<')]
 
 
+def window_capacity(engine, cin, cout):
+    """Staging capacity of an x-run engine's kernel for the width: a (unit, slab) window of more rows runs in gather mode."""
+    lib = L.load()
+    fn = {'x': lib.dz_spconv_x_window_rows, 'xf': lib.dz_spconv_x_f32_window_rows, 'xt': lib.dz_spconv_x_limb3_window_rows}[engine]
+    return fn(cin, cout)
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # cases
 # ------------------------------------------------------------------------------------------------------------------------
@@ -147,11 +175,11 @@ def sp_case(engine, mode, cin, cout, kind, edge, masks=True, sort=False, sweep=F
         arm = kind
     elif engine == 'packed':
         arm = 'packed'
-    elif engine in ('x', 'xf'):
-        arm = ('sort ' if sort else 'nosort ') + ('gathermode' if edge in ('xgather', 'unequal') else 'staged')
+    elif engine in XRUN_ENGINES:
+        arm = ('sort ' if sort else 'nosort ') + ('gathermode' if edge in ('xgather', 'unequal', 'window=rcap+1') else 'staged')
     else:
         arm = 'plain' if name.startswith('k_spconv_w') else kind
-    label = '%s %d->%d %s %s%s' % (engine, cin, cout, kind, edge, '' if engine not in ('x', 'xf') else (' sort' if sort else ' nosort'))
+    label = '%s %d->%d %s %s%s' % (engine, cin, cout, kind, edge, '' if engine not in XRUN_ENGINES else (' sort' if sort else ' nosort'))
     if engine == 'split':
         label += ' masks' if masks else ' nomasks'
     return types.SimpleNamespace(label=label, engine=engine, mode=mode, cin=cin, cout=cout, kind=kind, kvol=kvol, edge=edge, masks=masks,
@@ -184,14 +212,19 @@ def _coverage_cases():
         for sort in (True, False):
             for edge in ('xgather', 'plain', 'unequal'):
                 cs.append(sp_case('xf', 'f32', c, c, 'subm', edge, sort=sort))
+                cs.append(sp_case('xt', 'f32', c, c, 'subm', edge, sort=sort))
                 for mode in SPLIT:
                     cs.append(sp_case('x', mode, c, c, 'subm', edge, sort=sort))
+            # ... and at the staging boundary itself
+            for edge in WINDOW_EDGES:
+                for engine, mode in (('x', 'f16x2'), ('xf', 'f32'), ('xt', 'f32')):
+                    cs.append(sp_case(engine, mode, c, c, 'subm', edge, sort=sort))
     # per instance: the exact-m edges of its row tile and the rest of EDGES_REQUIRED, on its submanifold layer (16 -> 32: the instance
     # has no submanifold layer in the backbone; the kernel does not know - run as one), f32 / f16x2
     inst = {}
     for cin, cout, kind in LAYERS:
-        for engine, mode in (('f32', 'f32'), ('split', 'f16x2'), ('packed', 'f16x2'), ('x', 'f16x2'), ('xf', 'f32')):
-            if engine == 'packed' and cout > 32 or engine in ('x', 'xf') and (cin != cout or cin < 32):
+        for engine, mode in (('f32', 'f32'), ('split', 'f16x2'), ('packed', 'f16x2'), ('x', 'f16x2'), ('xf', 'f32'), ('xt', 'f32')):
+            if engine == 'packed' and cout > 32 or engine in XRUN_ENGINES and (cin != cout or cin < 32):
                 continue
             for masks in ((True, False) if engine == 'split' else (True,)):
                 name = expected_name(engine, cin, cout, 27, masks)
@@ -289,6 +322,87 @@ def _make_level(coords, batch, shape, cap, dev):
     return lvl
 
 
+def host_windows(coords, shape, unit):
+    """Rows of the (unit, z offset) windows of a level's submanifold 3 x 3 x 3 table, on the host: per unit of `unit` consecutive rows
+    (canonical order) and z offset the span first .. last input row its nine taps of that offset reference, 0 where there is none - what
+    k_xwin computes from the packed table.  (units, 3) int64."""
+    m = coords.shape[0]
+    c = coords.astype(np.int64)
+    d, h, w = shape
+    batch = int(c[:, 0].max()) + 1 if m else 1
+    grid = np.full(batch * d * h * w, -1, dtype=np.int64)
+    grid[((c[:, 0] * d + c[:, 1]) * h + c[:, 2]) * w + c[:, 3]] = np.arange(m)
+    units = -(-m // unit)
+    out = np.zeros((units, 3), dtype=np.int64)
+    first = np.arange(units) * unit
+    for tz in range(3):
+        lo = np.full(m, np.iinfo(np.int64).max)
+        hi = np.full(m, -1)
+        z = c[:, 1] + tz - 1
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                y, x = c[:, 2] + dy, c[:, 3] + dx
+                ok = (z >= 0) & (z < d) & (y >= 0) & (y < h) & (x >= 0) & (x < w)
+                idx = np.where(ok, grid[np.where(ok, ((c[:, 0] * d + z) * h + y) * w + x, 0)], -1)
+                lo = np.where(idx >= 0, np.minimum(lo, idx), lo)
+                hi = np.maximum(hi, idx)
+        ulo, uhi = np.minimum.reduceat(lo, first), np.maximum.reduceat(hi, first)
+        out[:, tz] = np.where(uhi >= 0, uhi - ulo + 1, 0)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def window_coords(rcap, unit, target):
+    """A one-frame level of three identical z slabs whose longest (unit, slab) window has exactly `target` (rcap or rcap + 1) rows.
+    Every line of a slab holds the cells x < W, so the unit of rows (y0, x0) .. (y1, x1) references, in each slab it has neighbours in,
+    the rows (y0 - 1, x0 - 1) .. (y1 + 1, x1 + 1): unit + (cells of line y0 - 1) + (cells of line y1) + 2 of them (one fewer per end
+    whose corner lies outside the line).  W = (rcap - unit - 2) / 2 gives rcap; for rcap + 1 one line holds one cell more (the grid is
+    W + 1 wide), so a unit that ends in that line or starts in the line after it is one row over and no unit two.  The height and the
+    long line are searched on the host model (host_windows) until the longest window is `target` - the GPU's own windows are what the
+    case asserts.  Returns (coords, shape)."""
+    assert target in (rcap, rcap + 1) and (rcap - unit - 2) % 2 == 0 and rcap - unit - 2 >= 6, (rcap, unit, target)
+    w = (rcap - unit - 2) // 2
+    h0 = -(-3 * unit // w) + 3
+    for h in range(h0, h0 + 6):
+        for long_line in ((None,) if target == rcap else range(1, h - 1)):
+            shape = [3, h, w + 1]
+            cells = [(0, z, y, x) for z in range(3) for y in range(h) for x in range(w + (1 if y == long_line else 0))]
+            coords = np.array(cells, dtype=np.int32)
+            wins = host_windows(coords, shape, unit)
+            if int(wins.max()) == target and int((wins == target).sum()) >= 1:
+                return coords, shape
+    raise AssertionError(('no level of full slabs with a longest window of %d rows' % target, rcap, unit))
+
+
+def subm_coords(case, tile, rng):
+    """Coordinates of a submanifold case's level (host only): (coords, batch, shape)."""
+    edge = case.edge
+    batch = 1
+    if edge in ('unequal', 'xgather'):
+        batch, shape = (2, [4, 40, 56]) if edge == 'unequal' else (1, [4, 48, 64])
+        cells, slab = shape[0] * shape[1] * shape[2], shape[1] * shape[2]
+        lin = [b * cells + z * slab + np.nonzero(rng.random(slab) < UNEQUAL[(b + z) % 4])[0] for b in range(batch) for z in range(shape[0])]
+        coords = _lin_to_coords(np.unique(np.concatenate(lin)), shape)
+    elif edge == 'isolated':
+        shape = [7, 31, 46]
+        g = np.stack(np.meshgrid(np.arange(1, 7, 3), np.arange(1, 31, 3), np.arange(1, 46, 3), indexing='ij'), -1).reshape(-1, 3)
+        g = g[rng.random(g.shape[0]) < 0.8]
+        coords = np.concatenate([np.zeros((g.shape[0], 1), np.int64), g], 1).astype(np.int32)
+    elif edge == 'plain':
+        shape = [5, 30, 44]
+        coords = _coords_density(rng, 1, shape, 0.25)
+    elif edge in WINDOW_EDGES:
+        rcap = window_capacity(case.engine, case.cin, case.cout)
+        coords, shape = window_coords(rcap, tile, rcap + (1 if edge == 'window=rcap+1' else 0))
+    else:
+        coords, shape = _coords_exact(rng, edge_rows(edge, tile))
+    return coords, batch, shape
+
+
+def case_rng(case):
+    return np.random.default_rng(zlib.crc32(('%s|%s' % (case.label, case.mode)).encode()))
+
+
 def edge_rows(edge, tile):
     """Rows of the output level an exact-m edge asks for (None: the edge does not fix m)."""
     if edge.startswith('tiles='):
@@ -304,22 +418,7 @@ def build_geometry(case, tile, rng, dev):
     edge = case.edge
     subm = case.kind == 'subm'
     if subm:
-        batch = 1
-        if edge in ('unequal', 'xgather'):
-            batch, shape = (2, [4, 40, 56]) if edge == 'unequal' else (1, [4, 48, 64])
-            cells, slab = shape[0] * shape[1] * shape[2], shape[1] * shape[2]
-            lin = [b * cells + z * slab + np.nonzero(rng.random(slab) < UNEQUAL[(b + z) % 4])[0] for b in range(batch) for z in range(shape[0])]
-            coords = _lin_to_coords(np.unique(np.concatenate(lin)), shape)
-        elif edge == 'isolated':
-            shape = [7, 31, 46]
-            g = np.stack(np.meshgrid(np.arange(1, 7, 3), np.arange(1, 31, 3), np.arange(1, 46, 3), indexing='ij'), -1).reshape(-1, 3)
-            g = g[rng.random(g.shape[0]) < 0.8]
-            coords = np.concatenate([np.zeros((g.shape[0], 1), np.int64), g], 1).astype(np.int32)
-        elif edge == 'plain':
-            shape = [5, 30, 44]
-            coords = _coords_density(rng, 1, shape, 0.25)
-        else:
-            coords, shape = _coords_exact(rng, edge_rows(edge, tile))
+        coords, batch, shape = subm_coords(case, tile, rng)
         m = coords.shape[0]
         cap = m + {'dead tiles': 2 * tile + 3, 'm=cap': 0, 'overflow': 0}.get(edge, 0 if edge.startswith('m=') else 7)
         lvl = _make_level(coords, batch, shape, cap, dev)
@@ -353,7 +452,7 @@ def build_geometry(case, tile, rng, dev):
 def gpu_tables(case, lvl_in, lvl_out, d_m, sort):
     """The table the case's engine reads, built by the library: (nbr, xwin or None)."""
     k, s, p = KINDS[case.kind]
-    if case.engine in ('f32', 'split'):
+    if case.engine in ('f32', 'split', 'gt'):
         return lvl_in.neighbors_to(lvl_out, k, s, p), None
     nbr = lvl_in.neighbors_to(lvl_out, k, s, p, packed=True)
     assert getattr(nbr, 'packed', False), 'the library did not build a packed table for this layer'
@@ -398,9 +497,16 @@ def launch(case, x, in_rows, nbr, xwin, masks, cap, d_m, w, sc, sh, res, relu, o
     elif case.engine == 'packed':
         rc = lib.dz_spconv_forward_split_packed(p(x), in_rows, case.cin, p(nbr), p(masks), cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
                                                 case.cout, math, L.stream())
+    elif case.engine == 'gt':
+        assert masks is not None and not getattr(nbr, 'packed', False), (case.label, 'k_spconv_gt reads a plain table with tile masks')
+        rc = lib.dz_spconv_forward_limb3(p(x), in_rows, case.cin, p(nbr), p(masks), case.kvol, cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
+                                         case.cout, L.stream())
     else:
         tabx = xwin[2] if xwin[3] is not None else nbr
-        if case.engine == 'x':
+        if case.engine == 'xt':
+            rc = lib.dz_spconv_forward_x_limb3(p(x), in_rows, case.cin, p(tabx), p(xwin[3]), p(xwin[0]), xwin[1], cap, p(d_m), p(w), p(sc), p(sh), p(res),
+                                               relu, p(out), case.cout, L.stream())
+        elif case.engine == 'x':
             rc = lib.dz_spconv_forward_split_x(p(x), in_rows, case.cin, p(tabx), p(xwin[3]), p(xwin[0]), xwin[1], cap, p(d_m), p(w), p(sc), p(sh), p(res),
                                                relu, p(out), case.cout, math, L.stream())
         else:
@@ -441,7 +547,8 @@ def convolve_and_check(case, lvl_in, lvl_out, nbr, xwin, tab, m_in, counter, dev
         wk = ops.pack_weight_split(w32, ops.storage_math(math))                   # (kvol, cout_pad, cin) pair16
         w64 = _decode(wk, mode).transpose(-1, -2)[..., :cout].contiguous()
     else:
-        x, r, wk = x32.clone(), r32.clone(), w32.contiguous()
+        # (bf16x3: the three limbs of a weight sum to it exactly - the reference is the fp32 operands')
+        x, r, wk = x32.clone(), r32.clone(), (ops.pack_weight_limb3(w32, cout_mult=32) if case.engine in LIMB3_ENGINES else w32.contiguous())
         w64 = w32.double()
     del x32, r32
     x.view(torch.int32)[m_in:] = POISON
@@ -489,19 +596,30 @@ def run_case(case, dev):
     """Build the case's levels and tables, check the tables against the oracle, convolve.  Returns (name, worst e)."""
     name = case.expect
     tile = tile_rows(name, case.cin, case.cout)
-    rng = np.random.default_rng(zlib.crc32(('%s|%s' % (case.label, case.mode)).encode()))
-    lvl_in, lvl_out, cin_, cout_, counter = build_geometry(case, tile, rng, dev)
+    lvl_in, lvl_out, cin_, cout_, counter = build_geometry(case, tile, case_rng(case), dev)
     k, s, p = KINDS[case.kind]
     tab = _t(osp.neighbor_table(cin_, lvl_in.shape, cout_, k, s, p), dev)
     m_in = cin_.shape[0]
     d_m = lvl_out.d_m if counter is None else torch.tensor([counter], dtype=torch.int32, device=dev)
     nbr, xwin = gpu_tables(case, lvl_in, lvl_out, d_m, case.sort)
-    if case.engine in ('x', 'xf') and case.edge in ('xgather', 'unequal', 'plain') and counter is None:
-        lib = L.load()
-        rcap = (lib.dz_spconv_x_window_rows if case.engine == 'x' else lib.dz_spconv_x_f32_window_rows)(case.cin, case.cout)
+    if case.engine in XRUN_ENGINES and case.edge in ('xgather', 'unequal', 'plain') + WINDOW_EDGES and counter is None:
+        rcap = window_capacity(case.engine, case.cin, case.cout)
         nt = (lvl_out.cap + xwin[1] - 1) // xwin[1]
-        longest = int(xwin[0][:nt * 6].view(-1, 3, 2)[..., 1].max())
+        wins = xwin[0][:nt * 6].view(-1, 3, 2)[..., 1]
+        longest = int(wins.max())
         assert rcap > 0 and (longest > rcap) == ('gathermode' in case.arm), (case.label, longest, rcap)
+        if case.edge in WINDOW_EDGES:
+            # the staging boundary, read back from the windows the library built
+            target = rcap + (1 if case.edge == 'window=rcap+1' else 0)
+            hit = int((wins == target).sum())
+            print('  %-44s windows of the library: longest %d, %d of exactly %d rows (staging capacity %d)' % (case.label, longest, hit, target, rcap))
+            assert hit >= 1, (case.label, 'no window of exactly %d rows' % target, longest, rcap)
+            if case.edge == 'window=rcap':
+                assert longest == rcap, (case.label, 'a window longer than the staging capacity', longest, rcap)
+            host = np.zeros((nt, 3), dtype=np.int64)
+            hw = host_windows(cin_, lvl_in.shape, xwin[1])
+            host[:hw.shape[0]] = hw
+            assert np.array_equal(wins.cpu().numpy().astype(np.int64), host), (case.label, 'the windows differ from the host model')
     name, worst, tr, res = convolve_and_check(case, lvl_in, lvl_out, nbr, xwin, tab, m_in, counter, dev)
     if case.edge == 'overflow':
         # the overflowed counter must give exactly what the exact counter gives
@@ -549,6 +667,35 @@ def test_case_table_covers_every_variant():
     lib = L.load()
     assert lib.dz_spconv_variant_split(64, 64) == b'k_spconv_h<256x64x32>' and lib.dz_spconv_variant_split(128, 128) == b'k_spconv_h<256x128x32>'
     assert lib.dz_spconv_variant_split(16, 16) == b'k_spconv_w<16x16>' and lib.dz_spconv_variant_split(48, 48) == b'none'
+
+
+def test_xrun_cases_reach_their_arm_on_the_host_model():
+    """The window model of the host (host_windows: first .. last referenced row per unit and z offset) on every x-run case whose arm
+    depends on the level: the longest window is above the kernel's staging capacity exactly where the case says 'gathermode'; a
+    'window=rcap' level holds a window of exactly the capacity and none longer, a 'window=rcap+1' level one of exactly one row more
+    and none longer.  (The GPU cases assert the same from the windows the library builds, and those against this model.)"""
+    seen = set()
+    for c in COVERAGE:
+        if c.engine not in XRUN_ENGINES or c.edge not in ('xgather', 'unequal', 'plain') + WINDOW_EDGES:
+            continue
+        unit = tile_rows(c.expect, c.cin, c.cout)
+        rcap = window_capacity(c.engine, c.cin, c.cout)
+        coords, batch, shape = subm_coords(c, unit, case_rng(c))
+        wins = host_windows(coords, shape, unit)
+        longest = int(wins.max())
+        assert rcap > 0 and (longest > rcap) == ('gathermode' in c.arm), (c.label, c.mode, longest, rcap)
+        if c.edge in WINDOW_EDGES:
+            target = rcap + (1 if c.edge == 'window=rcap+1' else 0)
+            assert longest == target and int((wins == target).sum()) >= 1, (c.label, longest, target)
+            assert 1000 <= coords.shape[0] <= 8000, (c.label, coords.shape[0])
+            seen.add((c.engine, c.cout, c.sort, c.edge))
+    assert seen == {(e, w, s, edge) for e in XRUN_ENGINES for w in (32, 64, 128) for s in (True, False) for edge in WINDOW_EDGES}
+    # the model itself, on levels small enough to check by hand: one line of 6 cells in units of 2 rows (rows 0, 1 reference rows 0..2,
+    # rows 2, 3 rows 1..4, rows 4, 5 rows 3..5); two slabs of one 3-cell line each in units of 3 rows (each slab sees itself and the other)
+    line = np.array([(0, 0, 0, x) for x in range(6)], dtype=np.int32)
+    assert host_windows(line, [1, 1, 6], 2).tolist() == [[0, 3, 0], [0, 4, 0], [0, 3, 0]]
+    slabs = np.array([(0, z, 0, x) for z in range(2) for x in range(3)], dtype=np.int32)
+    assert host_windows(slabs, [2, 1, 3], 3).tolist() == [[0, 3, 3], [3, 3, 0]]
 
 
 # every variable the sparse-convolution launch code once read, at a value that used to select another instance, tile or schedule
@@ -733,6 +880,11 @@ def _infer_geometry(kvol, lvl_in, lvl_out):
 
 BACKBONE = [('f32', 'gather'), ('f32', 'xrun'), ('f16x2', 'gather'), ('f16x2', 'xrun'), ('bf16x2', 'gather'), ('bf16x2', 'xrun'),
             ('f16', 'gather'), ('f16', 'xrun')]
+# the bf16x3 engines of the f32 mode, 'f32_engine+f32_gather' (no '+': the default gather arithmetic); the last row is the configuration
+# DESIGN.md section 8 quotes.  These rows run 40 000-point frames (the tables, perms and calibrated capacities under test have the same
+# structure there), one frame and two
+BACKBONE_LIMB3 = ('xrun_bf16x3', 'gather+bf16x3', 'xrun_bf16x3+bf16x3')
+BACKBONE += [('f32', e) for e in BACKBONE_LIMB3]
 
 
 @pytest.mark.gpu
@@ -741,36 +893,46 @@ def test_backbone_launches_vs_float64(mode, engine, device):
     """The 21 sparse convolutions SparseBackbone.run_pyramid launches for masked_frame(0, 160000) at 0.1 m, one frame (worst-case level
     capacities: m far below cap) and four frames (calibrated capacities): ops.spconv_forward is replaced by a recorder while
     run_pyramid runs, then every recorded launch - the same table object, levels, channel counts, residual and ReLU flags - is replayed
-    through convolve_and_check with random operands.  f32: `engine` is the f32_engine."""
+    through convolve_and_check with random operands.  f32: `engine` is the f32_engine.
+    The rows of BACKBONE_LIMB3 (f32_engine 'xrun_bf16x3' and / or f32_gather 'bf16x3'): masked_frame(i, 40000), one frame and two; a
+    launch the backbone hands one of the two keywords is replayed through that kernel's entry point (k_spconv_xt on the windows and
+    tap-set order the pipeline built, k_spconv_gt on the plain table and its tile masks)."""
     from detzero_amd.centerpoint import FramePipeline, set_sparse_engine
     from detzero_amd.synth import VOXEL_SIZE_01
     from tests.util import make_model, masked_frame
     model, cfg, info = make_model(VOXEL_SIZE_01, seed=0)
     model = model.to(device)
     bb = model.backbone3d
-    before = (bb.engine, bb.f32_engine)
+    before = (bb.engine, bb.f32_engine, bb.f32_gather)
     math = ops.math_id(mode)
     real = ops.spconv_forward
+    limb3 = engine in BACKBONE_LIMB3
+    f32_engine, f32_gather = (engine.split('+') + ['mfma32'])[:2]
     try:
         if mode == 'f32':
-            set_sparse_engine(model, before[0], f32_engine=engine)
+            set_sparse_engine(model, before[0], f32_engine=f32_engine, f32_gather=f32_gather)
         else:
             set_sparse_engine(model, engine)
-        for nb in (1, 4):
-            frames = [torch.from_numpy(masked_frame(i, 160000)).to(device) for i in range(nb)]
+        for nb in ((1, 2) if limb3 else (1, 4)):
+            frames = [torch.from_numpy(masked_frame(i, 40000 if limb3 else 160000)).to(device) for i in range(nb)]
             pipe = FramePipeline(model, info, math=mode)
             if nb > 1:
                 pipe.calibrate(frames[:1], margin=1.5)
             prep = pipe.prepare(frames, overlap=False)
             rec = []
 
-            def recorder(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None):
+            def recorder(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None,
+                         f32_engine=None, f32_gather=None):
                 if math:
                     ci, co = w_taps.shape[2], (int(cout) if cout is not None else scale.shape[0])
+                elif f32_engine == 'xrun_bf16x3' or f32_gather == 'bf16x3':
+                    # limb weights (kvol, cout_pad, cin * 3 / 2), padded to 32 output channels
+                    ci, co = w_taps.shape[2] * 2 // 3, (int(cout) if cout is not None else w_taps.shape[1])
                 else:
                     ci, co = w_taps.shape[1], w_taps.shape[2]
                 rec.append(dict(nbr=nbr, out_level=out_level, in_level=in_level if in_level is not None else out_level, cin=ci, cout=co,
-                                residual=residual is not None, relu=bool(relu), math=int(math), in_rows=feats.shape[0]))
+                                residual=residual is not None, relu=bool(relu), math=int(math), in_rows=feats.shape[0],
+                                f32_engine=f32_engine, f32_gather=f32_gather))
                 return torch.empty((nbr.shape[1], co), dtype=torch.float32, device=feats.device)
             ops.spconv_forward = recorder
             try:
@@ -781,7 +943,7 @@ def test_backbone_launches_vs_float64(mode, engine, device):
             assert len(rec) == 21 and all(r['math'] == math for r in rec)
             print('\n  %d frame(s) [%s, %s]: 21 launches' % (nb, mode, engine))
             stage = {}
-            names = set()
+            names, launched = set(), []
             for i, r in enumerate(rec):
                 nbr, lvl_in, lvl_out = r['nbr'], r['in_level'], r['out_level']
                 packed = getattr(nbr, 'packed', False)
@@ -789,6 +951,13 @@ def test_backbone_launches_vs_float64(mode, engine, device):
                 kind = _infer_geometry(kvol, lvl_in, lvl_out)
                 xwin = getattr(nbr, 'xwin', None) if (packed and r['cin'] == r['cout']) else None
                 eng = ('x' if math else 'xf') if xwin is not None else 'packed' if packed else 'split' if math else 'f32'
+                assert r['f32_engine'] in (None, 'xrun_bf16x3') and r['f32_gather'] in (None, 'bf16x3') and not (r['f32_engine'] and r['f32_gather'])
+                if r['f32_engine'] == 'xrun_bf16x3':
+                    assert not math and xwin is not None, 'the bf16x3 x-run engine was asked for on a table without windows'
+                    eng = 'xt'
+                elif r['f32_gather'] == 'bf16x3':
+                    assert not math and not packed and getattr(nbr, 'tile_masks', None) is not None
+                    eng = 'gt'
                 assert r['in_rows'] == lvl_in.cap or lvl_in is lvl_out
                 li = stage.setdefault(id(lvl_out), len(stage))
                 case = types.SimpleNamespace(label='backbone %df #%02d %d->%d %s%s%s' % (nb, i, r['cin'], r['cout'], kind, ' +res' if r['residual'] else '',
@@ -800,10 +969,17 @@ def test_backbone_launches_vs_float64(mode, engine, device):
                 assert r['relu'], 'every layer of the backbone ends in a ReLU'
                 name, _, _, _ = convolve_and_check(case, lvl_in, lvl_out, nbr, xwin, tab, lvl_in.num_active(), None, device, seed=1000 * nb + i)
                 names.add(name)
+                launched.append(name)
             # the engine really was the one asked for
-            assert any(n.startswith('k_spconv_x') for n in names) == (engine == 'xrun'), sorted(names)
+            if limb3:
+                nxt = sum(n.startswith('k_spconv_xt<') for n in launched)
+                assert nxt == (12 if f32_engine == 'xrun_bf16x3' else 0), launched
+                rest = 'k_spconv_gt<' if f32_gather == 'bf16x3' else 'k_spconv<'
+                assert all(n.startswith('k_spconv_xt<') or n.startswith(rest) for n in launched), launched
+            else:
+                assert any(n.startswith('k_spconv_x') for n in names) == (engine == 'xrun'), sorted(names)
             del prep, rec
             torch.cuda.empty_cache()
     finally:
         ops.spconv_forward = real
-        set_sparse_engine(model, before[0], f32_engine=before[1])
+        set_sparse_engine(model, before[0], f32_engine=before[1], f32_gather=before[2])

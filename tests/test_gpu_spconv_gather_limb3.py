@@ -16,7 +16,7 @@ import torch
 from detzero_amd import lib as L
 from detzero_amd import ops
 from oracle import sparse as osp
-from tests.test_gpu_conv3x3_limb3 import _patterned, _pow2
+from tests.test_gpu_conv3x3_limb3 import _patterned, _patterned_tiny, _pow2, _subnormal_report
 from tests.test_gpu_sparse_conv import (KINDS, LAYERS, POISON, SENTINEL, TAIL, build_geometry, check_tables, edge_rows, normalised_error,
                                         ref64)
 from tests.test_gpu_xrun import K3, P1, S1, _level, _t
@@ -322,6 +322,27 @@ def test_mm_term_bit_exact(cin, cout, kind, device):
     exp = _one_hot_expect(x, tab[:, :m], tap, ci, val)
     assert bool((exp != 0).any())
     _same_bits(_gt(case, x, lvl_out, nbr, w)[:m], exp, 'm.m term %d->%d %s' % (cin, cout, kind))
+
+
+def test_subnormal_limbs_are_measured(device):
+    """One one-hot launch of the 64 -> 128 down-convolution with features of exponent [-120, -104]: their m and / or l limbs are bf16
+    subnormals while every product (weights +-1, 0.5, 2) stays a normal fp32.  Asserted: |got - x w| <= 2^-124, which holds whether or
+    not the matrix pipe flushes subnormal inputs; printed (and recorded in DESIGN.md 2a-ter): the share of bit-exact outputs."""
+    cin, cout, kind = 64, 128, 'down'
+    case, lvl_in, lvl_out, cin_, nbr, tab, m = _geometry(cin, cout, kind, device, 43 * cin + cout)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(25 + cin)
+    m_in = cin_.shape[0]
+    x = torch.zeros((lvl_in.cap, cin), device=device)
+    x[:m_in] = _patterned_tiny((m_in, cin), gen, device)
+    ar = torch.arange(cout, device=device)
+    tap, ci = ar % case.kvol, (ar * 7 + 3) % cin
+    val = torch.tensor([1.0, -1.0, 0.5, 2.0, -2.0], device=device)[ar % 5]
+    w = torch.zeros((case.kvol, cin, cout), device=device)
+    w[tap, ci, ar] = val
+    got = _gt(case, x, lvl_out, nbr, w)[:m]
+    xsel = _one_hot_expect(x, tab[:, :m], tap, ci, torch.ones_like(val))
+    _subnormal_report('k_spconv_gt %d->%d %s' % (cin, cout, kind), got, xsel, val)
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -1,13 +1,15 @@
 """GPU (MI355X): the bf16x3 x-run sparse convolution of the exact-fp32 mode (csrc/sparse_conv_xt.hip, dz_spconv_forward_x_limb3:
 submanifold 3 x 3 x 3 convolutions at 32 / 64 / 128 channels from the packed table + windows of the x-run engines, every operand as
 three exact bf16 limbs) against a float64 evaluation of the same rulebook, the fp32 gather kernel and k_spconv_xf; its limb terms
-bit for bit on one-product outputs; its write contract, its refusals, and the detector on it.
+bit for bit on one-product outputs; the same on inputs whose lower limbs are bf16 subnormals (a measurement: asserted to 2^-124 only);
+its write contract, its refusals, and the detector on it.  (Its row-count edges, the staging boundary and the detector's own launches
+are cases of tests/test_gpu_sparse_conv.py.)
 Levels are built as in tests/test_gpu_xrun.py (`_level`), tables and the float64 reference as in tests/test_gpu_xrun_f32.py."""
 import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_conv3x3_limb3 import _patterned, _pow2
+from tests.test_gpu_conv3x3_limb3 import _patterned, _patterned_tiny, _pow2, _subnormal_report
 from tests.test_gpu_xrun import K3, P1, S1, _level, _t
 from tests.test_gpu_xrun_f32 import SENTINEL, _inputs, _ref64, _stage_rows, _tables
 
@@ -129,6 +131,29 @@ def test_input_limbs_bit_exact(device, channels, monkeypatch):
         w[tap, ci, torch.arange(channels, device=device)] = val
         got = _xt(x, xt, lvl, w)[:m]
         _same_bits(got, _one_hot_expect(x, tab, tap, ci, val), 'input limbs %d ch, launch %d' % (channels, k))
+
+
+def test_subnormal_limbs_are_measured(device, monkeypatch):
+    """test_input_limbs_bit_exact's launches at 64 channels with features of exponent [-120, -104]: their m and / or l limbs are bf16
+    subnormals while every product (weights +-1, 0.5, 2) stays a normal fp32.  Asserted: |got - x w| <= 2^-124, which holds whether or
+    not the matrix pipe flushes subnormal inputs; printed (and recorded in DESIGN.md 2a-ter): the share of bit-exact outputs."""
+    channels = 64
+    lvl, coords, m = _small_level(device, 43 * channels)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(25 + channels)
+    x = torch.zeros((lvl.cap, channels), device=device)
+    x[:m] = _patterned_tiny((m, channels), gen, device)
+    plain, xt = _tables(lvl, channels, True, monkeypatch)
+    tab = plain[:, :m]
+    ar = torch.arange(channels, device=device)
+    tap, ci = ar % 27, (ar * 7 + 3) % channels
+    val = torch.tensor([1.0, -1.0, 0.5, 2.0, -2.0], device=device)[ar % 5]
+    w = torch.zeros((27, channels, channels), device=device)
+    w[tap, ci, ar] = val
+    got = _xt(x, xt, lvl, w)[:m]
+    xsel = _one_hot_expect(x, tab, tap, ci, torch.ones_like(val))
+    # (rows without the tap's neighbour hold an exact zero: no subnormal limb, not counted)
+    _subnormal_report('k_spconv_xt<%d>' % channels, got, xsel, val)
 
 
 @pytest.mark.parametrize('channels', COVERED)
