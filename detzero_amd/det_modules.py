@@ -528,47 +528,31 @@ class VoxelResBackBone8x(_Cached):
     def _res_block(self, x, nbr, level, params, e=0, name=None, stage=None):
         """(all tensors of a level - block inputs, hidden activations, the residual - share the level's exponent e)"""
         c1, c2 = params
-        (p1, kw1), (p2, kw2) = self._sub_p(c1, nbr, e), self._sub_p(c2, nbr, e)
-        y = self._audit('%s.conv1' % name, stage, ops.spconv_forward(x, nbr, level, *p1, None, True, math=self.math, **kw1), level, e)
-        return self._audit('%s.conv2' % name, stage, ops.spconv_forward(y, nbr, level, *p2, x, True, math=self.math, **kw2), level, e)
+        y = self._audit('%s.conv1' % name, stage, self._conv(x, nbr, level, c1, e, e), level, e)
+        return self._audit('%s.conv2' % name, stage, self._conv(y, nbr, level, c2, e, e, residual=x), level, e)
 
     def _conv(self, x, nbr, level, entry, e_in, e_out, **kw):
-        """A convolution of the gather path without residual (conv_input, the down-convolutions, conv_out)."""
-        params, more = self._gather_p(entry, nbr, self._p(entry, e_in, e_out), x.shape[0])
-        return ops.spconv_forward(x, nbr, level, *params, None, True, math=self.math, **kw, **more)
+        """One convolution + BatchNorm + ReLU of plan entry `entry` over table `nbr`, on the engine ops.spconv_route gives it."""
+        params, more = self._route_p(entry, nbr, e_in, e_out, x.shape[0])
+        return ops.spconv_forward(x, nbr, level, *params, relu=True, math=self.math, **kw, **more)
 
-    def _sub_p(self, entry, nbr, e):
-        """((weights, scale, shift), further keywords of ops.spconv_forward) of a submanifold convolution over table `nbr`: `_p`'s and
-        none (the call is the one made without this engine), except in f32 mode with the fp32 engine 'xrun_bf16x3' on a table with x-run
-        windows and a width k_spconv_xt covers - then the weights are the entry's limb form (packed once, cached in the plan entry)
-        and the keyword names the engine.  A width it does not cover stays on k_spconv_xf."""
-        w, scale, shift = self._p(entry, e, e)
-        if self.math or self.f32_engine != 'xrun_bf16x3' or getattr(nbr, 'xwin', None) is None:
-            return self._gather_p(entry, nbr, (w, scale, shift))
+    def _route_p(self, entry, nbr, e_in, e_out, in_rows):
+        """((weights, scale, shift), further keywords of ops.spconv_forward) of a convolution over table `nbr`.  The backbone's engine
+        switches are preferences, so ops.spconv_route is asked first: `_p`'s parameters and no keyword, unless the route reads limb
+        weights - then the entry's limb form (packed once, cached in the plan entry; both bf16x3 kernels read it) and the keyword
+        that names the engine.  (The split modes have one weight form and no keyword: nothing to ask.  In f32 spconv_forward resolves
+        once more to check the keyword: a few host-side library queries per layer, nothing on the device.)"""
+        w, scale, shift = self._p(entry, e_in, e_out)
+        if self.math:
+            return (w, scale, shift), {}
         cin, cout = int(w.shape[1]), int(w.shape[2])
-        if cin != cout or ops.L.load().dz_spconv_x_limb3_window_rows(cin, cout) == 0:
-            return self._gather_p(entry, nbr, (w, scale, shift))
+        route = ops.spconv_route(nbr, cin, cout, 0, self.f32_engine, getattr(self, 'f32_gather', 'mfma32'), in_rows)
+        if route.weights != 'limb3':
+            return (w, scale, shift), {}
         if 'w_xlimb3' not in entry:
             entry['w_xlimb3'] = ops.pack_weight_limb3(entry['w'], cout_mult=32)
-        return (entry['w_xlimb3'], scale, shift), {'f32_engine': 'xrun_bf16x3'}
-
-    def _gather_p(self, entry, nbr, params, in_rows=0):
-        """(`params`, further keywords of ops.spconv_forward) of a convolution that runs on the gather path over table `nbr`: `params`
-        ((weights, scale, shift) of `_p`) and none, except in f32 mode with the gather arithmetic 'bf16x3' on a plain table with tile
-        masks and a layer k_spconv_gt covers, all inside the 2 GiB buffer window - then the weights are the entry's limb form (packed
-        once, cached in the plan entry: the layout of `_sub_p`'s, one copy serves both kernels) and the keywords name the arithmetic and
-        the true output width.  Anything else keeps the call made without it."""
-        if self.math or getattr(self, 'f32_gather', 'mfma32') != 'bf16x3' or getattr(nbr, 'packed', False) or getattr(nbr, 'tile_masks', None) is None:
-            return params, {}
-        w, scale, shift = params
-        cin, cout = int(w.shape[1]), int(w.shape[2])
-        limit = 1 << 31
-        if (ops.L.load().dz_spconv_limb3_tile_rows(cin, cout) == 0 or nbr.numel() * 4 >= limit or nbr.shape[1] * cout * 4 >= limit
-                or int(in_rows) * cin * 4 >= limit):
-            return params, {}
-        if 'w_xlimb3' not in entry:
-            entry['w_xlimb3'] = ops.pack_weight_limb3(entry['w'], cout_mult=32)
-        return (entry['w_xlimb3'], scale, shift), {'f32_gather': 'bf16x3', 'cout': cout}
+        more = {'f32_engine': 'xrun_bf16x3'} if route.engine == 'xrun_bf16x3' else {'f32_gather': 'bf16x3', 'cout': cout}
+        return (entry['w_xlimb3'], scale, shift), more
 
     def build_pyramid(self, voxel_features, voxel_coords, batch_size, d_n=None, overlap=True, side_key=0, caps=None, level1=None,
                       staggered=False, exact=False):
@@ -620,11 +604,10 @@ class VoxelResBackBone8x(_Cached):
             # (asked BEFORE the packed table is built: a width / capacity the x-run kernel does not cover would otherwise build the
             # table twice - packed for nothing, then plain)
             if (xrun and src is dst and cout in xrun_couts and tuple(k) == (3, 3, 3) and dst.cap < (1 << 29)
-                    and ops.L.load().dz_spconv_x_tile_rows(int(cout), int(cout)) != 0
-                    and (self.math != 0 or ops.L.load().dz_spconv_x_f32_window_rows(int(cout), int(cout)) != 0)):
+                    and ops.xrun_unit(cout, cout, self.math) != 0):
                 # submanifold table of a level the x-run kernel covers: packed words + the tiles' windows
                 nbr = ops.neighbors_xrun(dst, cout)          # (one launch: packed table + windows + tap-set order)
-                if getattr(nbr, 'xwin', None) is not None:
+                if nbr.xwin is not None:
                     return nbr
             nbr = src.neighbors_to(dst, k, s, p, packed=pack and cout <= 32)
             return ops.build_tiles(nbr, dst) if tiled and cout in self.tile_couts and k[0] * k[1] * k[2] >= 3 else nbr
@@ -632,17 +615,9 @@ class VoxelResBackBone8x(_Cached):
         def hand_over(step):                        # tensors born on the side stream are consumed on the main stream
             nbr_d, nbr_s, lvl, _ = step
             # (the level's bitmap / prefix / workspace too: the dense BEV hand-over and the PDV lookups read them on the main stream)
-            for t in (nbr_d, nbr_s, lvl.coords, lvl.d_m, lvl.bitmap, lvl.prefix, lvl.ws):
-                if t is not None:
-                    t.record_stream(main)
-                    if getattr(t, 'tile_masks', None) is not None:
-                        t.tile_masks.record_stream(main)
-                    for tt in getattr(t, 'tiles', None) or ():
-                        tt.record_stream(main)
-                    if getattr(t, 'xwin', None) is not None:
-                        for tt in t.xwin:
-                            if torch.is_tensor(tt):
-                                tt.record_stream(main)
+            tables = [t for nbr in (nbr_d, nbr_s) if nbr is not None for t in nbr.tensors()]
+            for t in tables + [lvl.coords, lvl.d_m, lvl.bitmap, lvl.prefix, lvl.ws]:
+                t.record_stream(main)
         ch = self.channels
         with torch.cuda.stream(side):
             nbr1 = table(lvl1, lvl1, K3, S1, P1, ch[0])

@@ -8,6 +8,7 @@ returns capacity-sized tensors plus the device count (graph-capturable).
 """
 import ctypes
 import os
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -162,6 +163,47 @@ def voxelize_dynamic(points_b, pc_range, voxel_size, batch_size):
 LAYOUT_LINEAR, LAYOUT_BRICK = 0, 1
 
 
+class XWindows(NamedTuple):
+    """What build_windows / neighbors_xrun add to a packed submanifold table for the x-run kernels."""
+    windows: torch.Tensor                   # per unit of tile_rows output rows and z offset the range of input rows + the tile-queue words
+    tile_rows: int                          # the unit: dz_spconv_x_tile_rows(channels, channels)
+    sorted_table: Optional[torch.Tensor]    # the table in tap-set order, or None (the kernels then read `words`)
+    perm: Optional[torch.Tensor]            # row map of that order, or None
+
+
+# (what build_tiles adds for the tile-resident convolution: include/detzero_hip.h)
+Tiles = NamedTuple('Tiles', [('halo', torch.Tensor), ('tinfo', torch.Tensor), ('ltab', torch.Tensor), ('rowmap', torch.Tensor)])
+
+
+class NeighborTable:
+    """A neighbour table and what was built from it; spconv_route picks the engine from these fields.  words: (kvol, cap) i32 input
+    row per tap and output row (-1 = none), or packed the (9, cap) words of a 27-tap table (dz_build_neighbors_packed); kvol: the
+    true tap count in both forms; tile_masks: per-32-row tap masks; xwin: None or XWindows; tiles: None or Tiles."""
+
+    def __init__(self, words, kvol=None, packed=False, tile_masks=None, xwin=None, tiles=None):
+        self.words, self.packed = words, bool(packed)
+        self.kvol = int(kvol) if kvol is not None else 27 if packed else int(words.shape[0])
+        self.tile_masks, self.xwin, self.tiles = tile_masks, xwin, tiles
+
+    shape = property(lambda self: self.words.shape)
+    device = property(lambda self: self.words.device)
+
+    def numel(self):
+        return self.words.numel()
+
+    # the two reads callers written for the tensor form make of a table: its address (L.ptr(table)) and rows of its words (a bare
+    # tensor, not a table).  Nothing that acts on a tensor (record_stream, clone, cpu, to) exists here: that goes through tensors()
+    def data_ptr(self):
+        return self.words.data_ptr()
+
+    def __getitem__(self, index):
+        return self.words[index]
+
+    def tensors(self):
+        """Every tensor the table owns (what a stream hand-over has to record)."""
+        return [t for t in (self.words, self.tile_masks, *(self.xwin or ()), *(self.tiles or ())) if torch.is_tensor(t)]
+
+
 class SparseLevel:
     """One resolution level of the sparse tensor: bitmap + popcount prefix + coordinates of the rows.
     Plays the role of spconv's SparseConvTensor.indices / indice_dict (backbone3d.py:302-307).
@@ -227,10 +269,9 @@ class SparseLevel:
         return out
 
     def neighbors_to(self, out_level, k, s, p, packed=False):
-        """(kvol, out_level.cap) i32 neighbour table: rows of THIS level feeding each output row.
-        packed=True asks for the packed form of a 27-tap table (dz_build_neighbors_packed: (9, cap) words, `.packed` = True,
-        `.kvol` = 27) - what the small-channel split-math convolutions read; windows / layouts it does not cover come back
-        unpacked."""
+        """NeighborTable of (kvol, out_level.cap) i32 words, with its tile masks: rows of THIS level feeding each output row.
+        packed=True asks for the packed form of a 27-tap table (dz_build_neighbors_packed: (9, cap) words) - what the small-channel
+        split-math convolutions read; windows / layouts it does not cover come back unpacked."""
         lib = L.load()
         kvol = k[0] * k[1] * k[2]
         cap = max(out_level.cap, 1)
@@ -241,16 +282,13 @@ class SparseLevel:
             nbr = torch.empty((9, cap), dtype=torch.int32, device=self.coords.device)
             rc = lib.dz_build_neighbors_packed(*args, L.ptr(nbr), L.ptr(masks), L.stream())
             if rc == 0:
-                nbr.tile_masks = masks
-                nbr.packed, nbr.kvol = True, 27
-                return nbr
+                return NeighborTable(nbr, packed=True, tile_masks=masks)
             if rc != L.ERR_UNSUPPORTED:
                 L.check(rc, 'dz_build_neighbors_packed')
         nbr = torch.empty((kvol, cap), dtype=torch.int32, device=self.coords.device)
         rc = lib.dz_build_neighbors(*args, L.ptr(nbr), L.ptr(masks), L.stream())
         L.check(rc, 'dz_build_neighbors')
-        nbr.tile_masks = masks        # per-32-row tap masks ride along with the table (consumed by spconv_forward)
-        return nbr
+        return NeighborTable(nbr, tile_masks=masks)
 
 
 FUSED_XWIN = os.environ.get('DZ_TUNE_FUSED_XWIN', '1') != '0'      # development switch: 0 = table and windows by two launches (r04)
@@ -269,24 +307,31 @@ def neighbors_xrun(level, channels):
     dev = level.coords.device
     masks = torch.empty((lib.dz_tile_masks_words(cap),), dtype=torch.int32, device=dev)
     nbr = torch.empty((9, cap), dtype=torch.int32, device=dev)
-    win = torch.empty((lib.dz_spconv_x_windows_words(cap, tr),), dtype=torch.int32, device=dev)
-    sort = XRUN_SORT and channels >= XRUN_SORT_MIN_CHANNELS
-    nbr_sorted = torch.empty_like(nbr) if sort else None
-    perm = torch.empty((cap,), dtype=torch.int32, device=dev) if sort else None
+    xwin = _empty_xwin(lib, nbr, tr, channels)
     rc = lib.dz_build_neighbors_packed_x(L.ptr(level.coords), L.ptr(level.d_m), level.cap, L.ptr(level.bitmap), L.ptr(level.prefix), level.batch,
-                                         *level.shape, L.ptr(nbr), L.ptr(masks), tr, L.ptr(win), L.ptr(nbr_sorted), L.ptr(perm), L.stream())
+                                         *level.shape, L.ptr(nbr), L.ptr(masks), tr, L.ptr(xwin.windows), L.ptr(xwin.sorted_table),
+                                         L.ptr(xwin.perm), L.stream())
     L.check(rc, 'dz_build_neighbors_packed_x')
-    nbr.tile_masks = masks
-    nbr.packed, nbr.kvol = True, 27
-    nbr.xwin = (win, tr, nbr_sorted, perm)
-    return nbr
+    return NeighborTable(nbr, packed=True, tile_masks=masks, xwin=xwin)
+
+
+def _as_table(nbr):
+    """`nbr`, or for a bare tensor of table words (a slice, a copy; packed where the caller marked it `.packed = True`, the form
+    before NeighborTable) a table of them.  Unmarked (9, n) words are refused: that is the shape of a packed table's slice, which
+    must not count as a plain one."""
+    if isinstance(nbr, NeighborTable):
+        return nbr
+    if 'packed' not in vars(nbr) and nbr.shape[0] == 9:
+        raise L.DetZeroHipError('bare (9, n) table words: a slice of a packed table? wrap them - NeighborTable(words, packed=True)')
+    return NeighborTable(nbr, packed=vars(nbr).get('packed', False))
 
 
 def unpack_table(nbr):
-    """The (27, cap) form of a packed neighbour table (tests, statistics); other tables are returned as they are."""
-    if not getattr(nbr, 'packed', False):
-        return nbr
-    e = nbr.to(torch.int64) & 0xFFFFFFFF
+    """The (27, cap) words of a packed NeighborTable (tests, statistics); the words of other tables are returned as they are."""
+    nbr = _as_table(nbr)
+    if not nbr.packed:
+        return nbr.words
+    e = nbr.words.to(torch.int64) & 0xFFFFFFFF
     r = e & 0x1FFFFFFF
     left, cen, right = (e >> 29) & 1, (e >> 30) & 1, (e >> 31) & 1
     minus = torch.full_like(r, -1)
@@ -295,19 +340,19 @@ def unpack_table(nbr):
 
 
 def table_pairs(nbr, m):
-    """Number of (input, output) pairs of the first m output rows of a neighbour table (host sync)."""
-    if getattr(nbr, 'packed', False):
-        e = nbr[:, :m].to(torch.int64) & 0xFFFFFFFF
+    """Number of (input, output) pairs of the first m output rows of a NeighborTable (host sync)."""
+    nbr = _as_table(nbr)
+    if nbr.packed:
+        e = nbr.words[:, :m].to(torch.int64) & 0xFFFFFFFF
         return int((((e >> 29) & 1) + ((e >> 30) & 1) + ((e >> 31) & 1)).sum().item())
-    return int((nbr[:, :m] >= 0).sum().item())
+    return int((nbr.words[:, :m] >= 0).sum().item())
 
 
 def build_tiles(nbr, out_level):
     """Tile form of a neighbour table for the tile-resident convolution (dz_spconv_tiles_forward): per tile of
     dz_spconv_tile_rows() output rows the list of distinct input rows (halo), the tile record (slots = non-empty taps, halo
     size, fragment slot masks), the local uint16 table and the tap-set order of the tile's rows (include/detzero_hip.h).
-    Attached to the table as ``nbr.tiles`` = (halo, tinfo, ltab, rowmap) - spconv_forward picks the tile kernel whenever it is
-    there (split math modes)."""
+    Filled in as ``nbr.tiles`` (Tiles) - spconv_route picks the tile kernel whenever it is there (split math modes)."""
     lib = L.load()
     kvol, cap = nbr.shape
     tr = lib.dz_spconv_tile_rows()
@@ -317,9 +362,9 @@ def build_tiles(nbr, out_level):
     tinfo = torch.zeros((ntiles, lib.dz_spconv_tile_info_words()), dtype=torch.int32, device=dev)
     ltab = torch.empty((ntiles, lib.dz_spconv_tile_table_entries()), dtype=torch.int16, device=dev)
     rowmap = torch.empty((ntiles, tr), dtype=torch.int16, device=dev)
-    rc = lib.dz_build_tiles(L.ptr(nbr), kvol, cap, L.ptr(out_level.d_m), L.ptr(halo), L.ptr(tinfo), L.ptr(ltab), L.ptr(rowmap), L.stream())
+    rc = lib.dz_build_tiles(L.ptr(nbr.words), kvol, cap, L.ptr(out_level.d_m), L.ptr(halo), L.ptr(tinfo), L.ptr(ltab), L.ptr(rowmap), L.stream())
     L.check(rc, 'dz_build_tiles')
-    nbr.tiles = (halo, tinfo, ltab, rowmap)
+    nbr.tiles = Tiles(halo, tinfo, ltab, rowmap)
     return nbr
 
 
@@ -327,26 +372,32 @@ XRUN_SORT = os.environ.get('DZ_TUNE_XRUN_SORT', '1') != '0'       # development 
 XRUN_SORT_MIN_CHANNELS = int(os.environ.get('DZ_TUNE_XRUN_SORT_MIN', '64'))
 
 
-def build_windows(nbr, out_level, channels):
-    """Windows of the x-run convolution (dz_spconv_forward_split_x) for a PACKED submanifold table and the level's channel width:
-    per tile of dz_spconv_x_tile_rows(channels, channels) output rows and z offset the contiguous range of input rows its nine taps
-    read.  Attached as ``nbr.xwin`` = (windows, tile_rows); spconv_forward picks the x-run kernel whenever it is there and the
-    layer is channels -> channels.  Tables / widths the engine does not cover are returned unchanged."""
-    lib = L.load()
-    tr = lib.dz_spconv_x_tile_rows(int(channels), int(channels))
-    if not getattr(nbr, 'packed', False) or tr == 0:
-        return nbr
-    cap = nbr.shape[1]
+def _empty_xwin(lib, words, tr, channels):
+    """Unwritten XWindows of a packed (9, cap) table for units of `tr` rows."""
+    cap = words.shape[1]
     # (tiles x 3 x 2 window words + the tile-queue words of the convolution kernels)
-    win = torch.empty((lib.dz_spconv_x_windows_words(cap, tr),), dtype=torch.int32, device=nbr.device)
+    win = torch.empty((lib.dz_spconv_x_windows_words(cap, tr),), dtype=torch.int32, device=words.device)
     # the table and the row map in tap-set order (rows of a unit sorted by their neighbour pattern: fewer (fragment, tap) pairs to multiply)
     # (at 32 channels the order saves ~1 % of the kernel - less than sorting a level of 1.8 M rows and writing its table again costs)
     sort = XRUN_SORT and channels >= XRUN_SORT_MIN_CHANNELS
-    nbr_sorted = torch.empty_like(nbr) if sort else None
-    perm = torch.empty((cap,), dtype=torch.int32, device=nbr.device) if sort else None
-    rc = lib.dz_spconv_x_windows(L.ptr(nbr), cap, L.ptr(out_level.d_m), tr, L.ptr(win), L.ptr(nbr_sorted), L.ptr(perm), L.stream())
+    return XWindows(win, tr, torch.empty_like(words) if sort else None,
+                    torch.empty((cap,), dtype=torch.int32, device=words.device) if sort else None)
+
+
+def build_windows(nbr, out_level, channels):
+    """Windows of the x-run convolution (dz_spconv_forward_split_x) for a PACKED submanifold table and the level's channel width:
+    per tile of dz_spconv_x_tile_rows(channels, channels) output rows and z offset the contiguous range of input rows its nine taps
+    read.  Filled in as ``nbr.xwin`` (XWindows); spconv_route picks an x-run kernel whenever it is there and the layer is
+    channels -> channels.  Tables / widths the engine does not cover are returned unchanged."""
+    lib = L.load()
+    tr = lib.dz_spconv_x_tile_rows(int(channels), int(channels))
+    if not nbr.packed or tr == 0:
+        return nbr
+    xwin = _empty_xwin(lib, nbr.words, tr, channels)
+    rc = lib.dz_spconv_x_windows(L.ptr(nbr.words), nbr.shape[1], L.ptr(out_level.d_m), tr, L.ptr(xwin.windows), L.ptr(xwin.sorted_table),
+                                 L.ptr(xwin.perm), L.stream())
     L.check(rc, 'dz_spconv_x_windows')
-    nbr.xwin = (win, tr, nbr_sorted, perm)
+    nbr.xwin = xwin
     return nbr
 
 
@@ -381,117 +432,117 @@ SPARSE_F32_ENGINES = ('gather', 'xrun', 'xrun_bf16x3')
 SPARSE_F32_GATHER_ENGINES = ('mfma32', 'bf16x3')
 
 
-def _xrun_f32_usable(lib, nbr, w_taps):
-    """The packed table carries x-run windows the exact-fp32 x-run kernel can run this (kvol, cin, cout) fp32 layer from."""
-    xwin = getattr(nbr, 'xwin', None)
-    cin, cout = int(w_taps.shape[1]), int(w_taps.shape[2])
-    return (xwin is not None and cin == cout and lib.dz_spconv_x_f32_window_rows(cin, cout) > 0
-            and xwin[1] == lib.dz_spconv_x_tile_rows(cin, cout))
+# what spconv_route returns: a key of _SPCONV_ENGINES; the weight form the engine reads - 'taps' (fp32 (kvol, cin, cout)), 'split'
+# (pack_weight_split) or 'limb3' (pack_weight_limb3(w, cout_mult=32)); the library's (cin, cout) -> name of the kernel it launches
+SpconvRoute = NamedTuple('SpconvRoute', [('engine', str), ('weights', str), ('variant', Callable)])
 
 
-def _xrun_limb3_usable(lib, nbr, w_limb):
-    """The packed table carries x-run windows the bf16x3 x-run kernel can run this layer from; w_limb: its (27, cout, cin * 3 / 2)
-    limb weights (pack_weight_limb3(w, cout_mult=32))."""
-    xwin = getattr(nbr, 'xwin', None)
-    if w_limb.dim() != 3 or w_limb.shape[0] != 27 or w_limb.shape[2] % 12 != 0:
-        return False
-    cout, cin = int(w_limb.shape[1]), int(w_limb.shape[2]) * 2 // 3
-    return (xwin is not None and cin == cout and lib.dz_spconv_x_limb3_window_rows(cin, cout) > 0
-            and xwin[1] == lib.dz_spconv_x_tile_rows(cin, cout))
+def _x_args(t):
+    x = t.xwin
+    return L.ptr(x.sorted_table if x.perm is not None else t.words), L.ptr(x.perm), L.ptr(x.windows), x.tile_rows
+
+
+# engine: (weight form, C entry point, its variant-name function, the entry point's arguments between `cin` and `cap`) - in the order
+# spconv_route tries them
+_SPCONV_ENGINES = {
+    'xrun_bf16x3': ('limb3', 'dz_spconv_forward_x_limb3', 'dz_spconv_x_limb3_variant', _x_args),
+    'gather_bf16x3': ('limb3', 'dz_spconv_forward_limb3', 'dz_spconv_limb3_variant', lambda t: (L.ptr(t.words), L.ptr(t.tile_masks), t.kvol)),
+    'xrun_f32': ('taps', 'dz_spconv_forward_x_f32', 'dz_spconv_x_f32_variant', _x_args),
+    'xrun_split': ('split', 'dz_spconv_forward_split_x', 'dz_spconv_x_variant', _x_args),
+    'tiles': ('split', 'dz_spconv_tiles_forward', 'dz_spconv_tiles_variant', lambda t: (*(L.ptr(x) for x in t.tiles), t.kvol)),
+    'gather_split_packed': ('split', 'dz_spconv_forward_split_packed', 'dz_spconv_variant_split', lambda t: (L.ptr(t.words), L.ptr(t.tile_masks))),
+    'gather_split': ('split', 'dz_spconv_forward_split', 'dz_spconv_variant_split', lambda t: (L.ptr(t.words), L.ptr(t.tile_masks), t.kvol)),
+    'gather_f32': ('taps', 'dz_spconv_forward', 'dz_spconv_variant', lambda t: (L.ptr(t.words), t.kvol)),
+}
+
+
+def xrun_unit(cin, cout, math, bf16x3=False):
+    """Rows per window unit of the x-run kernel that runs a cin -> cout submanifold layer in this math mode (bf16x3: the three-limb
+    kernel of the exact-fp32 mode) from a packed table with windows; 0 = no such kernel.  The one coverage question of the index
+    builder (VoxelResBackBone8x.build_pyramid: is a table with windows worth building?) and of spconv_route."""
+    lib = L.load()
+    cin, cout = int(cin), int(cout)
+    rows = lib.dz_spconv_x_limb3_window_rows if bf16x3 else lib.dz_spconv_x_f32_window_rows
+    return lib.dz_spconv_x_tile_rows(cin, cout) if cin == cout and (math or rows(cin, cout) > 0) else 0
+
+
+def spconv_route(table, cin, cout, math, f32_engine=None, f32_gather=None, in_rows=0):
+    """The engine (SpconvRoute) of a cin -> cout convolution over NeighborTable `table`: host logic, the first match wins.
+      math 0: 'xrun_bf16x3' for f32_engine 'xrun_bf16x3' on a packed table with windows in the unit of a layer k_spconv_xt covers;
+              'gather_bf16x3' for f32_gather 'bf16x3' on a plain table with tile masks and a layer k_spconv_gt covers, the table, the
+              output and `in_rows` input rows all below 2 GiB; 'xrun_f32' on a packed table with windows in the unit of a layer
+              k_spconv_xf covers; 'gather_f32' on any other plain table - no fp32 kernel reads another packed one: an error
+      else:   'xrun_split' on a packed table with windows, cin == cout; 'tiles' on a table with tiles, kvol >= 3;
+              'gather_split_packed' / 'gather_split' on any other packed / plain table
+    A keyword whose engine does not cover the layer falls through (the backbone prefers); spconv_forward, which is explicit, refuses."""
+    lib = L.load()
+    cin, cout = int(cin), int(cout)
+    xwin = table.xwin if table.packed and cin == cout else None
+    windows_fit = lambda bf16x3: xwin is not None and 0 != xrun_unit(cin, cout, 0, bf16x3) == xwin.tile_rows
+    if math:
+        engine = ('xrun_split' if xwin is not None else 'tiles' if table.kvol >= 3 and table.tiles is not None
+                  else 'gather_split_packed' if table.packed else 'gather_split')
+    elif f32_engine == 'xrun_bf16x3' and windows_fit(True):
+        engine = 'xrun_bf16x3'
+    elif (f32_gather == 'bf16x3' and not table.packed and table.tile_masks is not None and lib.dz_spconv_limb3_tile_rows(cin, cout) > 0
+          and 4 * max(table.numel(), table.shape[1] * cout, int(in_rows) * cin) < (1 << 31)):
+        engine = 'gather_bf16x3'
+    elif windows_fit(False):
+        engine = 'xrun_f32'
+    elif table.packed:
+        raise L.DetZeroHipError('spconv_forward: a packed neighbour table feeds the split-math kernels only - in fp32 an x-run kernel, through windows in '
+                                'the unit of a layer it covers (%d -> %d, f32_engine=%r, f32_gather=%r)' % (cin, cout, f32_engine, f32_gather))
+    else:
+        engine = 'gather_f32'
+    form, _, variant, _ = _SPCONV_ENGINES[engine]
+    return SpconvRoute(engine, form, getattr(lib, variant))
 
 
 def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None,
                    f32_engine=None, f32_gather=None):
-    """feats (m_in,cin); nbr (kvol,cap); returns (cap,cout).
+    """feats (m_in,cin); nbr: NeighborTable of (kvol,cap); returns (cap,cout), computed by the engine of spconv_route.
     math == 0: fp32 rows, w_taps (kvol,cin,cout) fp32; a packed table with x-run windows (neighbors_xrun / build_windows) runs a
     cin == cout layer of 32 / 64 / 128 channels on the exact-fp32 x-run kernel (dz_spconv_forward_x_f32).
-    f32_engine (math 0 only; the split modes ignore it): None or 'xrun' = the above; 'xrun_bf16x3' = the same table and rows on the
-    three-limb kernel of csrc/sparse_conv_xt.hip (dz_spconv_forward_x_limb3), `w_taps` in the pack_weight_limb3(w, cout_mult=32)
-    layout; a layer or table that kernel does not cover is an error.
-    f32_gather (math 0 only; the split modes ignore it): None or 'mfma32' = dz_spconv_forward on a plain table; 'bf16x3' = the same
-    table and rows on the three-limb gather kernel of csrc/sparse_conv_gt.hip (dz_spconv_forward_limb3), `w_taps` in the
-    pack_weight_limb3(w, cout_mult=32) layout (kvol, cout_pad, cin * 3 / 2) and `cout=` the true width where it is below 32 (default:
-    the BatchNorm vector's, else the weights'); a packed table or a layer the library does not cover is an error.
+    f32_engine / f32_gather (math 0 only; the split modes ignore them) are explicit - a table or layer the named kernel does not
+    cover is an error: 'xrun_bf16x3' = that table and those rows on the three-limb kernel of csrc/sparse_conv_xt.hip; 'bf16x3' = a
+    plain table with tile masks on the three-limb gather kernel of csrc/sparse_conv_gt.hip.  Both read `w_taps` in the
+    pack_weight_limb3(w, cout_mult=32) layout (kvol, cout_pad, cin * 3 / 2), with `cout=` the true width where it is below 32
+    (default: the BatchNorm vector's, else the weights').  None, 'gather', 'xrun', 'mfma32' ask for nothing.
     math != 0: pair16 rows (in, residual, out), w_taps (kvol,cout_pad,cin) pair16 from pack_weight_split."""
     lib = L.load()
-    L.require_cuda(feats, nbr, w_taps, scale, shift, residual)
     if f32_engine not in (None,) + SPARSE_F32_ENGINES:
         raise L.DetZeroHipError('unknown fp32 sparse engine %r (%s)' % (f32_engine, ' | '.join(SPARSE_F32_ENGINES)))
     if f32_gather not in (None,) + SPARSE_F32_GATHER_ENGINES:
         raise L.DetZeroHipError('unknown fp32 gather arithmetic %r (%s)' % (f32_gather, ' | '.join(SPARSE_F32_GATHER_ENGINES)))
-    limb3 = f32_engine == 'xrun_bf16x3' and not math
-    glimb3 = f32_gather == 'bf16x3' and not math and not limb3
-    kvol, cap = nbr.shape
-    packed = getattr(nbr, 'packed', False)
-    if glimb3:
-        if packed:
-            raise L.DetZeroHipError("spconv_forward: fp32 gather arithmetic 'bf16x3' reads a plain (kvol, cap) table, not a packed one")
-        if getattr(nbr, 'tile_masks', None) is None or w_taps.dim() != 3 or w_taps.shape[0] != kvol or w_taps.shape[2] % 12 != 0:
-            raise L.DetZeroHipError("spconv_forward: fp32 gather arithmetic 'bf16x3' needs a plain table with tile masks and the "
-                                    '(kvol, cout_pad, cin * 3 / 2) limb weights of the layer')
-    if limb3 and not (packed and _xrun_limb3_usable(lib, nbr, w_taps)):
-        raise L.DetZeroHipError("spconv_forward: fp32 engine 'xrun_bf16x3' needs a packed table with x-run windows and the limb weights "
-                                'of a 32 / 64 / 128-channel cin == cout layer the kernel covers')
-    if packed:
-        kvol = nbr.kvol
-        # (fp32: only the x-run kernels of sparse_conv_xf.hip / sparse_conv_xt.hip read a packed table - they need the table's windows,
-        # for a layer they cover)
-        if not math and not limb3 and not _xrun_f32_usable(lib, nbr, w_taps):
-            raise L.DetZeroHipError('spconv_forward: a packed neighbour table feeds the split-math kernels only')
-    if math:
-        # (split weights are padded to 32 output channels: the true count comes from the BatchNorm vector, or `cout=`)
-        cin, cout = w_taps.shape[2], (int(cout) if cout is not None else scale.shape[0] if scale is not None else w_taps.shape[1])
-    elif limb3:
-        cin, cout = w_taps.shape[2] * 2 // 3, w_taps.shape[1]
-    elif glimb3:
-        # (limb weights are padded to 32 output channels: the true count comes from `cout=` or the BatchNorm vector)
-        cin, cout = w_taps.shape[2] * 2 // 3, (int(cout) if cout is not None else scale.shape[0] if scale is not None else w_taps.shape[1])
-        if lib.dz_spconv_limb3_tile_rows(cin, cout) == 0 or w_taps.shape[1] != max(cout, 32):
-            raise L.DetZeroHipError("spconv_forward: fp32 gather arithmetic 'bf16x3' does not cover a %d -> %d layer with %d weight rows"
+    limb = not math and (f32_engine == 'xrun_bf16x3' or f32_gather == 'bf16x3')
+    if math or limb:
+        # (split and limb weights are padded to 32 output channels: the true count comes from `cout=`, the BatchNorm vector, else the weights)
+        if limb and (w_taps.dim() != 3 or w_taps.shape[0] != nbr.kvol or w_taps.shape[2] % 12 != 0):
+            raise L.DetZeroHipError("spconv_forward: the fp32 engines 'xrun_bf16x3' / 'bf16x3' need the (kvol, cout_pad, cin * 3 / 2) limb "
+                                    'weights of the layer, not %s' % (tuple(w_taps.shape),))
+        cin = w_taps.shape[2] if math else w_taps.shape[2] * 2 // 3
+        cout = int(cout) if cout is not None else scale.shape[0] if scale is not None else w_taps.shape[1]
+        if limb and w_taps.shape[1] != max(cout, 32):
+            raise L.DetZeroHipError("spconv_forward: fp32 arithmetic 'bf16x3' does not cover a %d -> %d layer with %d weight rows"
                                     % (cin, cout, w_taps.shape[1]))
     else:
         cin, cout = w_taps.shape[1], w_taps.shape[2]
+    route = spconv_route(nbr, cin, cout, math, f32_engine, f32_gather, feats.shape[0])
+    if limb and route.engine != ('xrun_bf16x3' if f32_engine == 'xrun_bf16x3' else 'gather_bf16x3'):
+        raise L.DetZeroHipError("spconv_forward: this %s table and %d -> %d layer run on %r - f32_engine 'xrun_bf16x3' needs a packed table with x-run "
+                                "windows in the unit of a cin == cout layer it covers, f32_gather 'bf16x3' a plain table with tile masks, a layer it "
+                                'covers and tensors below 2 GiB' % ('packed' if nbr.packed else 'plain', cin, cout, route.engine))
+    L.require_cuda(feats, nbr.words, w_taps, scale, shift, residual)
     assert feats.shape[1] == cin, (feats.shape, w_taps.shape)
+    cap = nbr.shape[1]
     if out is None:
         out = torch.empty((cap, cout), dtype=torch.float32, device=feats.device)
+    form, entry, _, table_args = _SPCONV_ENGINES[route.engine]
 
-    tiles = getattr(nbr, 'tiles', None) if (math and kvol >= 3) else None
-    xwin = getattr(nbr, 'xwin', None) if (packed and cin == cout) else None
     def launch():
-        if limb3:
-            rc = lib.dz_spconv_forward_x_limb3(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
-                                               L.ptr(xwin[0]), xwin[1], cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift),
-                                               L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, L.stream())
-        elif glimb3:
-            rc = lib.dz_spconv_forward_limb3(L.ptr(feats), feats.shape[0], cin, L.ptr(nbr), L.ptr(nbr.tile_masks), kvol, cap, L.ptr(out_level.d_m),
-                                             L.ptr(w_taps), L.ptr(scale), L.ptr(shift), L.ptr(residual), 1 if relu else 0, L.ptr(out), cout,
-                                             L.stream())
-        elif xwin is not None and not math:
-            rc = lib.dz_spconv_forward_x_f32(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
-                                             L.ptr(xwin[0]), xwin[1], cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift),
-                                             L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, L.stream())
-        elif xwin is not None:
-            rc = lib.dz_spconv_forward_split_x(L.ptr(feats), feats.shape[0], cin, L.ptr(xwin[2] if xwin[3] is not None else nbr), L.ptr(xwin[3]),
-                                               L.ptr(xwin[0]), xwin[1], cap,
-                                               L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift), L.ptr(residual),
-                                               1 if relu else 0, L.ptr(out), cout, int(math), L.stream())
-        elif tiles is not None:
-            rc = lib.dz_spconv_tiles_forward(L.ptr(feats), feats.shape[0], cin, L.ptr(tiles[0]), L.ptr(tiles[1]), L.ptr(tiles[2]),
-                                             L.ptr(tiles[3]), kvol, cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale),
-                                             L.ptr(shift), L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, int(math), L.stream())
-        elif packed:
-            rc = lib.dz_spconv_forward_split_packed(L.ptr(feats), feats.shape[0], cin, L.ptr(nbr), L.ptr(nbr.tile_masks), cap,
-                                                    L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale), L.ptr(shift), L.ptr(residual),
-                                                    1 if relu else 0, L.ptr(out), cout, int(math), L.stream())
-        elif math:
-            rc = lib.dz_spconv_forward_split(L.ptr(feats), feats.shape[0], cin, L.ptr(nbr), L.ptr(getattr(nbr, 'tile_masks', None)),
-                                             kvol, cap, L.ptr(out_level.d_m),
-                                             L.ptr(w_taps), L.ptr(scale), L.ptr(shift), L.ptr(residual), 1 if relu else 0,
-                                             L.ptr(out), cout, int(math), L.stream())
-        else:
-            rc = lib.dz_spconv_forward(L.ptr(feats), feats.shape[0], cin, L.ptr(nbr), kvol, cap, L.ptr(out_level.d_m),
-                                       L.ptr(w_taps), L.ptr(scale), L.ptr(shift), L.ptr(residual), 1 if relu else 0,
-                                       L.ptr(out), cout, L.stream())
+        rc = getattr(lib, entry)(L.ptr(feats), feats.shape[0], cin, *table_args(nbr), cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale),
+                                 L.ptr(shift), L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, *((int(math),) if form == 'split' else ()),
+                                 L.stream())
         L.check(rc, 'dz_spconv_forward')
     if PROFILER is None:
         launch()
@@ -501,10 +552,8 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         pairs = table_pairs(nbr, m)
         flops = 2.0 * pairs * cin * cout
         n_in = in_level.num_active() if in_level is not None else m
-        nbytes = 4.0 * (n_in * cin + m * cout + kvol * cin * cout + (m * cout if residual is not None else 0)) + 8.0 * pairs
-        name = (lib.dz_spconv_x_limb3_variant(cin, cout) if limb3 else lib.dz_spconv_limb3_variant(cin, cout) if glimb3 else lib.dz_spconv_x_f32_variant(cin, cout) if xwin is not None and not math else lib.dz_spconv_x_variant(cin, cout) if xwin is not None else lib.dz_spconv_tiles_variant(cin, cout) if tiles is not None else
-                lib.dz_spconv_variant_split(cin, cout) if math else lib.dz_spconv_variant(cin, cout))
-        PROFILER.wrap(name.decode(), flops, nbytes, launch)
+        nbytes = 4.0 * (n_in * cin + m * cout + nbr.kvol * cin * cout + (m * cout if residual is not None else 0)) + 8.0 * pairs
+        PROFILER.wrap(route.variant(cin, cout).decode(), flops, nbytes, launch)
     return out
 
 
@@ -1654,6 +1703,7 @@ def _guarded(fn):
     def wrapper(*args, **kwargs):
         dev = None
         for a in list(args) + list(kwargs.values()):
+            a = a.words if isinstance(a, NeighborTable) else a
             if torch.is_tensor(a) and a.is_cuda:
                 dev = a.device
                 break

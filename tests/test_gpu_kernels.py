@@ -195,7 +195,7 @@ def test_index_and_rulebooks_bit_exact(device, seed, n, vs, batch, layout):
         # submanifold rulebook of the current level
         nbr = cur_lvl.neighbors_to(cur_lvl, K3, S1, P1)
         ref = osp.neighbor_table(cur, cur_shape, cur, K3, S1, P1)
-        assert np.array_equal(canon_table(nbr[:, :cur.shape[0]].cpu().numpy(), cur_order, cur_order), ref)
+        assert np.array_equal(canon_table(nbr.words[:, :cur.shape[0]].cpu().numpy(), cur_order, cur_order), ref)
         # strided conv: output set + rulebook
         nxt = cur_lvl.downsample(k, s, p)
         oc, oshape = osp.conv_out_coords(cur, cur_shape, k, s, p)
@@ -207,7 +207,7 @@ def test_index_and_rulebooks_bit_exact(device, seed, n, vs, batch, layout):
             assert np.array_equal(nxt_order, np.arange(oc.shape[0]))
         nbr = cur_lvl.neighbors_to(nxt, k, s, p)
         ref = osp.neighbor_table(cur, cur_shape, oc, k, s, p)
-        assert np.array_equal(canon_table(nbr[:, :oc.shape[0]].cpu().numpy(), nxt_order, cur_order), ref)
+        assert np.array_equal(canon_table(nbr.words[:, :oc.shape[0]].cpu().numpy(), nxt_order, cur_order), ref)
         cur, cur_shape, cur_lvl, cur_order = oc, oshape, nxt, nxt_order
 
 
@@ -231,7 +231,7 @@ def test_rulebooks_on_dense_small_grids(device, shape, fill):
     # (np.nonzero order = ascending linear key = the canonical order of the rows)
 
     def check(nbr, ref, m):
-        got = nbr[:, :m].cpu().numpy()
+        got = nbr.words[:, :m].cpu().numpy()
         assert np.array_equal(got, ref)
         masks = nbr.tile_masks.cpu().numpy().astype(np.uint32)
         for gi in range(masks.shape[0]):
@@ -289,7 +289,7 @@ def test_build_tiles_is_the_table(device, layout, kvol):
     halo, tinfo, ltab, rowmap = (t.cpu().numpy() for t in nbr.tiles)
     tr = L.load().dz_spconv_tile_rows()
     m = out.num_active()
-    tab = nbr.cpu().numpy()
+    tab = nbr.words.cpu().numpy()
     ltab = ltab.view(np.uint16)
     rowmap = rowmap.view(np.uint16).astype(np.int64)
     assert tr == 512 and m > tr and ltab.shape == ((out.cap + tr - 1) // tr, 32 * tr)

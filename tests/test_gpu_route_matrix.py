@@ -514,7 +514,7 @@ def test_fp32_xrun_gather_mode_skips_ranks_past_the_input(device, engine, channe
     win = xt.xwin[0][:-16].view(-1, 3, 2)[:max(cap // xt.xwin[1], 1)].cpu()              # (first row, rows) per unit and slab offset
     reach = (win[..., 1] > rcap) & (win[..., 0] + win[..., 1] > cap)
     assert bool(reach.any()), (rcap, cap, win[:2].tolist())                               # a gather-mode window that ends past the input's rows
-    assert int((plain >= cap).sum()) > 0                                                  # ... and the table does name such ranks
+    assert int((plain.words >= cap).sum()) > 0                                                  # ... and the table does name such ranks
     x = _t(rng.standard_normal((cap, channels)).astype(np.float32), device)
     r = _t(rng.standard_normal((cap, channels)).astype(np.float32), device)
     w = _t((rng.standard_normal((27, channels, channels)) / np.sqrt(channels * 8)).astype(np.float32), device)
@@ -526,7 +526,7 @@ def test_fp32_xrun_gather_mode_skips_ranks_past_the_input(device, engine, channe
     else:
         ops.spconv_forward(x, xt, lvl, ops.pack_weight_limb3(w, cout_mult=32), sc, sh, r, relu=False, out=out, f32_engine='xrun_bf16x3')
     torch.cuda.synchronize(device)
-    tab = torch.where(plain < cap, plain, torch.full_like(plain, -1))
+    tab = torch.where(plain.words < cap, plain.words, torch.full_like(plain.words, -1))
     acc, _ = _ref64(x, tab, w, cap)
     ref = (acc * sc.double() + sh.double() + r.double()).float()
     err = float((out - ref).abs().max())

@@ -157,7 +157,7 @@ def test_brick_index_chain_on_ragged_grids(device, shape, fill):
 
     def check(nbr, ref, out_order, in_order):
         mo = out_order.size
-        tab = nbr[:, :mo].cpu().numpy()
+        tab = nbr.words[:, :mo].cpu().numpy()
         assert np.array_equal(canon_table(tab, out_order, in_order), ref)
         masks = nbr.tile_masks.cpu().numpy().astype(np.uint32)
         for gi in range(masks.shape[0]):

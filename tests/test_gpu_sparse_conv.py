@@ -455,7 +455,7 @@ def gpu_tables(case, lvl_in, lvl_out, d_m, sort):
     if case.engine in ('f32', 'split', 'gt'):
         return lvl_in.neighbors_to(lvl_out, k, s, p), None
     nbr = lvl_in.neighbors_to(lvl_out, k, s, p, packed=True)
-    assert getattr(nbr, 'packed', False), 'the library did not build a packed table for this layer'
+    assert nbr.packed, 'the library did not build a packed table for this layer'
     if case.engine == 'packed':
         return nbr, None
     saved = ops.XRUN_SORT, ops.XRUN_SORT_MIN_CHANNELS
@@ -465,7 +465,7 @@ def gpu_tables(case, lvl_in, lvl_out, d_m, sort):
         nbr = ops.build_windows(nbr, types.SimpleNamespace(d_m=d_m), case.cout)
     finally:
         ops.XRUN_SORT, ops.XRUN_SORT_MIN_CHANNELS = saved
-    assert getattr(nbr, 'xwin', None) is not None and (nbr.xwin[3] is not None) == sort
+    assert nbr.xwin is not None and (nbr.xwin[3] is not None) == sort
     return nbr, nbr.xwin
 
 
@@ -473,15 +473,14 @@ def check_tables(case, nbr, xwin, tab, m):
     """The GPU table(s) of the launch against the oracle's `tab` (kvol, m) on the rows < m."""
     if m == 0:
         return
-    got = ops.unpack_table(nbr)[:, :m] if getattr(nbr, 'packed', False) else nbr[:, :m]
+    got = ops.unpack_table(nbr)[:, :m]
     assert torch.equal(got.int(), tab.int()), (case.label, 'the neighbour table differs from the oracle')
     if xwin is not None and xwin[3] is not None:
         perm = xwin[3][:m].long()
         tr = xwin[1]
         pos = torch.arange(m, device=perm.device)
         assert torch.equal(torch.sort(perm).values, pos) and torch.equal(perm // tr, pos // tr), (case.label, 'perm is not a permutation within units')
-        srt = xwin[2][:, :m].clone()
-        srt.packed = True
+        srt = ops.NeighborTable(xwin[2][:, :m].clone(), packed=True)
         assert torch.equal(ops.unpack_table(srt).int(), tab[:, perm].int()), (case.label, 'the tap-set-ordered table differs from the oracle')
 
 
@@ -490,19 +489,19 @@ def launch(case, x, in_rows, nbr, xwin, masks, cap, d_m, w, sc, sh, res, relu, o
     math = ops.math_id(case.mode)
     p = L.ptr
     if case.engine == 'f32':
-        rc = lib.dz_spconv_forward(p(x), in_rows, case.cin, p(nbr), case.kvol, cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out), case.cout, L.stream())
+        rc = lib.dz_spconv_forward(p(x), in_rows, case.cin, p(nbr.words), case.kvol, cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out), case.cout, L.stream())
     elif case.engine == 'split':
-        rc = lib.dz_spconv_forward_split(p(x), in_rows, case.cin, p(nbr), p(masks), case.kvol, cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
+        rc = lib.dz_spconv_forward_split(p(x), in_rows, case.cin, p(nbr.words), p(masks), case.kvol, cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
                                          case.cout, math, L.stream())
     elif case.engine == 'packed':
-        rc = lib.dz_spconv_forward_split_packed(p(x), in_rows, case.cin, p(nbr), p(masks), cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
+        rc = lib.dz_spconv_forward_split_packed(p(x), in_rows, case.cin, p(nbr.words), p(masks), cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
                                                 case.cout, math, L.stream())
     elif case.engine == 'gt':
-        assert masks is not None and not getattr(nbr, 'packed', False), (case.label, 'k_spconv_gt reads a plain table with tile masks')
-        rc = lib.dz_spconv_forward_limb3(p(x), in_rows, case.cin, p(nbr), p(masks), case.kvol, cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
+        assert masks is not None and not nbr.packed, (case.label, 'k_spconv_gt reads a plain table with tile masks')
+        rc = lib.dz_spconv_forward_limb3(p(x), in_rows, case.cin, p(nbr.words), p(masks), case.kvol, cap, p(d_m), p(w), p(sc), p(sh), p(res), relu, p(out),
                                          case.cout, L.stream())
     else:
-        tabx = xwin[2] if xwin[3] is not None else nbr
+        tabx = xwin[2] if xwin[3] is not None else nbr.words
         if case.engine == 'xt':
             rc = lib.dz_spconv_forward_x_limb3(p(x), in_rows, case.cin, p(tabx), p(xwin[3]), p(xwin[0]), xwin[1], cap, p(d_m), p(w), p(sc), p(sh), p(res),
                                                relu, p(out), case.cout, L.stream())
@@ -522,7 +521,7 @@ def convolve_and_check(case, lvl_in, lvl_out, nbr, xwin, tab, m_in, counter, dev
     mode, math = case.mode, ops.math_id(case.mode)
     cin, cout, kvol = case.cin, case.cout, case.kvol
     cap, in_rows = lvl_out.cap, lvl_in.cap
-    masks = getattr(nbr, 'tile_masks', None) if case.masks else None
+    masks = nbr.tile_masks if case.masks else None
     name = reported_name(case.engine, cin, cout, kvol, masks is not None, cap)
     if case.expect is not None:
         assert name == case.expect, (case.label, mode, name, case.expect)

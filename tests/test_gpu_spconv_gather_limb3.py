@@ -61,7 +61,7 @@ EDGE_CASES = _edge_cases()
 def launch(case, x, in_rows, nbr, cap, d_m, wl, sc, sh, res, relu, out, expect_rc=0):
     lib = L.load()
     p = L.ptr
-    rc = lib.dz_spconv_forward_limb3(p(x), in_rows, case.cin, p(nbr), p(nbr.tile_masks), case.kvol, cap, p(d_m), p(wl), p(sc), p(sh), p(res), relu,
+    rc = lib.dz_spconv_forward_limb3(p(x), in_rows, case.cin, p(nbr.words), p(nbr.tile_masks), case.kvol, cap, p(d_m), p(wl), p(sc), p(sh), p(res), relu,
                                      p(out), case.cout, L.stream())
     msg = lib.dz_last_error()
     assert rc == expect_rc, (case.label, rc, msg.decode() if msg else '')
@@ -87,7 +87,7 @@ def convolve(case, lvl_in, lvl_out, nbr, tab, m_in, counter, dev, gather=False):
     Returns (rows < m of the two settings, worst e, worst e of k_spconv on the same operands or None)."""
     cin, cout = case.cin, case.cout
     cap, in_rows = lvl_out.cap, lvl_in.cap
-    assert getattr(nbr, 'tile_masks', None) is not None and not getattr(nbr, 'packed', False)
+    assert nbr.tile_masks is not None and not nbr.packed
     d_m = lvl_out.d_m if counter is None else torch.tensor([counter], dtype=torch.int32, device=dev)
     m_level = lvl_out.num_active()
     m = min(m_level if counter is None else counter, cap)
@@ -360,7 +360,7 @@ def test_refusals(device):
     w = torch.zeros((27 * 256 * 256 * 3 // 2,), device=device)
     out = torch.full((lvl.cap, 256), SENTINEL, dtype=torch.int32, device=device)
 
-    def call(cin, cout, kvol=27, in_rows=None, cap=None, table=nbr, masks=nbr.tile_masks):
+    def call(cin, cout, kvol=27, in_rows=None, cap=None, table=nbr.words, masks=nbr.tile_masks):
         rc = lib.dz_spconv_forward_limb3(L.ptr(x), lvl.cap if in_rows is None else in_rows, cin, L.ptr(table), L.ptr(masks), kvol,
                                          lvl.cap if cap is None else cap, L.ptr(lvl.d_m), L.ptr(w), None, None, None, 0, L.ptr(out), cout, L.stream())
         msg = lib.dz_last_error().decode()

@@ -116,11 +116,11 @@ def test_packed_neighbour_tables(device, name, mid):
     for src, dst, k, s, p in cases:
         plain = src.neighbors_to(dst, k, s, p)
         packed = src.neighbors_to(dst, k, s, p, packed=True)
-        assert getattr(packed, 'packed', False) and tuple(packed.shape) == (9, plain.shape[1]) and packed.kvol == 27
+        assert packed.packed and tuple(packed.shape) == (9, plain.shape[1]) and packed.kvol == 27
         m = dst.num_active()
-        assert torch.equal(ops.unpack_table(packed)[:, :m], plain[:, :m])
+        assert torch.equal(ops.unpack_table(packed)[:, :m], plain.words[:, :m])
         assert torch.equal(packed.tile_masks, plain.tile_masks)
-        assert ops.table_pairs(packed, m) == ops.table_pairs(plain, m) == int((plain[:, :m] >= 0).sum().item())
+        assert ops.table_pairs(packed, m) == ops.table_pairs(plain, m) == int((plain.words[:, :m] >= 0).sum().item())
         for cin, cout in ((16, 16), (16, 32), (32, 32)):
             w = ops.pack_weight_split(_t((rng.standard_normal((27, cin, cout)) / np.sqrt(cin * 8)).astype(np.float32), device), mid)
             scale, shift = _t(rng.uniform(0.5, 1.5, cout).astype(np.float32), device), _t(rng.standard_normal(cout).astype(np.float32) * 0.1, device)

@@ -67,7 +67,7 @@ def test_windows_cover_the_rulebook_exactly(device, channels):
     if perm is None:
         return
     perm = perm[:m].cpu().numpy().astype(np.int64)
-    packed = nbr[:, :m].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    packed = nbr.words[:, :m].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
     srt = nbr_sorted[:, :m].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
     assert np.array_equal(np.sort(perm), np.arange(m)) and np.array_equal(perm // tr, np.arange(m) // tr)
     assert np.array_equal(srt, packed[:, perm])
@@ -102,7 +102,7 @@ def test_fused_table_and_windows_equal_the_two_launches(device, channels):
         one = ops.neighbors_xrun(lvl, channels)
         m = lvl.num_active()
         assert one.packed and one.kvol == 27 and one.xwin[1] == two.xwin[1]
-        assert torch.equal(one[:, :m], two[:, :m]) and torch.equal(one.tile_masks, two.tile_masks)
+        assert torch.equal(one.words[:, :m], two.words[:, :m]) and torch.equal(one.tile_masks, two.tile_masks)
         assert torch.equal(one.xwin[0], two.xwin[0])
         assert (one.xwin[2] is None) == (two.xwin[2] is None)
         if one.xwin[2] is not None:
@@ -199,7 +199,7 @@ def test_xrun_refuses_what_it_does_not_cover(device):
     assert getattr(ops.build_windows(plain, lvl, 64), 'xwin', None) is None        # unpacked table: left alone
     win = torch.zeros((6 + 16,), dtype=torch.int32, device=device)
     x = torch.zeros((lvl.cap, 32), device=device)
-    rc = lib.dz_spconv_forward_split_x(L.ptr(x), lvl.cap, 32, L.ptr(packed), None, L.ptr(win), 128, lvl.cap, L.ptr(lvl.d_m), L.ptr(x), None, None,
+    rc = lib.dz_spconv_forward_split_x(L.ptr(x), lvl.cap, 32, L.ptr(packed.words), None, L.ptr(win), 128, lvl.cap, L.ptr(lvl.d_m), L.ptr(x), None, None,
                                        None, 0, L.ptr(x), 32, 1, L.stream())
     assert rc != 0 and b'tiles' in lib.dz_last_error()
 

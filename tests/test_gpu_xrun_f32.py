@@ -101,7 +101,7 @@ def test_xrun_f32_error_class(device, channels, monkeypatch):
     feats, w, scale, shift, res, x, r = _inputs(rng, lvl, m, channels, device)
     plain, xt = _tables(lvl, channels, channels >= 64, monkeypatch)
     wd, sc, sh = _t(w, device), _t(scale, device), _t(shift, device)
-    acc, aacc = _ref64(x, plain[:, :m], wd, m)
+    acc, aacc = _ref64(x, plain.words[:, :m], wd, m)
     ref = acc * sc.double() + sh.double() + r[:m].double()
     den = aacc * sc.double().abs() + sh.double().abs() + r[:m].double().abs()
     e = {}
@@ -155,7 +155,7 @@ def test_xrun_f32_refusals(device):
     out = torch.full((lvl.cap, 128), SENTINEL, device=device)
 
     def call(cin, cout, tile_rows, in_rows=None, cap=None):
-        rc = lib.dz_spconv_forward_x_f32(L.ptr(x), lvl.cap if in_rows is None else in_rows, cin, L.ptr(packed), None, L.ptr(win), tile_rows,
+        rc = lib.dz_spconv_forward_x_f32(L.ptr(x), lvl.cap if in_rows is None else in_rows, cin, L.ptr(packed.words), None, L.ptr(win), tile_rows,
                                          lvl.cap if cap is None else cap, L.ptr(lvl.d_m), L.ptr(w), None, None, None, 0, L.ptr(out), cout, L.stream())
         msg = lib.dz_last_error().decode()
         torch.cuda.synchronize(device)
@@ -169,7 +169,7 @@ def test_xrun_f32_refusals(device):
     assert rc == L.ERR_UNSUPPORTED and '2 GiB' in msg
     rc, msg = call(64, 64, tr, cap=2 ** 31 // (64 * 4))                      # an output of exactly 2^31 bytes
     assert rc == L.ERR_UNSUPPORTED and '2 GiB' in msg
-    rc = lib.dz_spconv_forward_x_f32(L.ptr(x), lvl.cap, 64, L.ptr(packed), None, None, tr, lvl.cap, L.ptr(lvl.d_m), L.ptr(w), None, None, None, 0,
+    rc = lib.dz_spconv_forward_x_f32(L.ptr(x), lvl.cap, 64, L.ptr(packed.words), None, None, tr, lvl.cap, L.ptr(lvl.d_m), L.ptr(w), None, None, None, 0,
                                      L.ptr(out), 64, L.stream())
     assert rc != 0 and b'null' in lib.dz_last_error() and bool((out == SENTINEL).all())
     # the Python mirror: a packed table without windows has no fp32 kernel

@@ -48,7 +48,7 @@ def test_xrun_limb3_vs_float64_gather_and_xf(device, channels, monkeypatch):
         for sort in (True, False):
             plain, xt = _tables(lvl, channels, sort, monkeypatch)
             if sort:
-                acc, aacc = _ref64(x, plain[:, :m], wd, m)
+                acc, aacc = _ref64(x, plain.words[:, :m], wd, m)
             wins = xt.xwin[0][:-16].view(-1, 3, 2)[..., 1]
             longest, shortest = int(wins.max().item()), int(wins[wins > 0].min().item())
             above, below = above or longest > rcap, below or shortest <= rcap
@@ -116,7 +116,7 @@ def test_input_limbs_bit_exact(device, channels, monkeypatch):
     x = torch.zeros((lvl.cap, channels), device=device)
     x[:m] = _patterned((m, channels), gen, device)
     plain, xt = _tables(lvl, channels, channels >= 64, monkeypatch)
-    tab = plain[:, :m]
+    tab = plain.words[:, :m]
     edge = [c for k in range(channels // 16) for c in (16 * k, 16 * k + 15)]
     combos = [(t, c) for t in range(27) for c in edge]
     order = torch.randperm(len(combos), generator=torch.Generator().manual_seed(channels)).tolist()
@@ -144,7 +144,7 @@ def test_subnormal_limbs_are_measured(device, monkeypatch):
     x = torch.zeros((lvl.cap, channels), device=device)
     x[:m] = _patterned_tiny((m, channels), gen, device)
     plain, xt = _tables(lvl, channels, True, monkeypatch)
-    tab = plain[:, :m]
+    tab = plain.words[:, :m]
     ar = torch.arange(channels, device=device)
     tap, ci = ar % 27, (ar * 7 + 3) % channels
     val = torch.tensor([1.0, -1.0, 0.5, 2.0, -2.0], device=device)[ar % 5]
@@ -178,7 +178,7 @@ def test_weight_limbs_bit_exact(device, channels, monkeypatch):
     row_val = torch.zeros(m, dtype=torch.float64, device=device)
     row_ch[rows], row_val[rows] = ch, val.double()
     plain, xt = _tables(lvl, channels, channels >= 64, monkeypatch)
-    tab = plain[:, :m].long()
+    tab = plain.words[:, :m].long()
     e64 = torch.zeros((m, channels), dtype=torch.float64, device=device)
     hits = torch.zeros(m, dtype=torch.long, device=device)
     for t in range(27):
@@ -211,7 +211,7 @@ def test_mm_term_bit_exact(device, channels, monkeypatch):
     w = torch.zeros((27, channels, channels), device=device)
     w[tap, ci, torch.arange(channels, device=device)] = val
     plain, xt = _tables(lvl, channels, channels >= 64, monkeypatch)
-    exp = _one_hot_expect(x, plain[:, :m], tap, ci, val)
+    exp = _one_hot_expect(x, plain.words[:, :m], tap, ci, val)
     assert bool((exp != 0).any())
     _same_bits(_xt(x, xt, lvl, w)[:m], exp, 'm.m term %d ch' % channels)
 
@@ -265,7 +265,7 @@ def test_xrun_limb3_refusals(device):
     out = torch.full((lvl.cap, 128), SENTINEL, device=device)
 
     def call(cin, cout, tile_rows, in_rows=None, cap=None, windows=win):
-        rc = lib.dz_spconv_forward_x_limb3(L.ptr(x), lvl.cap if in_rows is None else in_rows, cin, L.ptr(packed), None, L.ptr(windows), tile_rows,
+        rc = lib.dz_spconv_forward_x_limb3(L.ptr(x), lvl.cap if in_rows is None else in_rows, cin, L.ptr(packed.words), None, L.ptr(windows), tile_rows,
                                            lvl.cap if cap is None else cap, L.ptr(lvl.d_m), L.ptr(w), None, None, None, 0, L.ptr(out), cout, L.stream())
         msg = lib.dz_last_error().decode()
         torch.cuda.synchronize(device)

@@ -176,9 +176,8 @@ def test_packed_table_format_against_the_rulebook():
         assert np.array_equal(left[both] + 1, right[both])                               # centre empty: right follows left
         r = np.where(left >= 0, left + 1, np.where(cen >= 0, cen, np.where(right >= 0, right, 0)))
         word = r | ((left >= 0).astype(np.int64) << 29) | ((cen >= 0).astype(np.int64) << 30) | ((right >= 0).astype(np.int64) << 31)
-        packed = torch.from_numpy(word.astype(np.uint32).view(np.int32))
-        packed.packed, packed.kvol = True, 27
+        packed = ops.NeighborTable(torch.from_numpy(word.astype(np.uint32).view(np.int32)), packed=True)
         assert torch.equal(ops.unpack_table(packed), torch.from_numpy(tab.astype(np.int32)))
         assert ops.table_pairs(packed, oc.shape[0]) == int((tab >= 0).sum())
-        plain = torch.from_numpy(tab.astype(np.int32))
-        assert ops.unpack_table(plain) is plain and ops.table_pairs(plain, oc.shape[0]) == int((tab >= 0).sum())
+        plain = ops.NeighborTable(torch.from_numpy(tab.astype(np.int32)))
+        assert ops.unpack_table(plain) is plain.words and ops.table_pairs(plain, oc.shape[0]) == int((tab >= 0).sum())

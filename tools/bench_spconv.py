@@ -70,7 +70,7 @@ def main():
     total = 0.0
     for (f, nbr, lvl, w, scale, shift, residual, relu, in_level, f32e) in calls:
         kvol = w.shape[0]
-        variant = 'x' if getattr(nbr, 'xwin', None) is not None and (w.shape[1] == w.shape[2] or f32e == 'xrun_bf16x3') else 'g'
+        variant = 'x' if nbr.xwin is not None and (w.shape[1] == w.shape[2] or f32e == 'xrun_bf16x3') else 'g'
         cin, cout = (w.shape[2], scale.shape[0]) if mm else (w.shape[1], w.shape[1]) if f32e == 'xrun_bf16x3' else (w.shape[1], w.shape[2])
         kname = ''
         if variant == 'x':          # the x-run kernel instance that ran (pair16 or exact fp32)
@@ -106,7 +106,7 @@ def main():
             seen[key] = (us, stats)
         us, (pairs, t16, t32, t64, t128) = seen[key]
         halo = ''
-        if getattr(nbr, 'tiles', None) is not None:
+        if nbr.tiles is not None:
             nh = nbr.tiles[1][:(m + 511) // 512].float()
             halo = '  tiles: halo/rows %.2f max %d' % (float(nh.sum().item()) / max(m, 1), int(nh.max().item()))
         total += us
@@ -157,7 +157,7 @@ def compare_f32_engines(args):
     layers, seen = [], set()
     for (f, nbr, lvl, w, scale, shift, residual, relu) in calls:
         c = int(w.shape[1])
-        if getattr(nbr, 'xwin', None) is None or w.shape[1] != w.shape[2] or (c, residual is not None) in seen:
+        if nbr.xwin is None or w.shape[1] != w.shape[2] or (c, residual is not None) in seen:
             continue
         if args.only and '%d-%d' % (c, c) not in args.only.split(','):
             continue
