@@ -203,6 +203,13 @@ __device__ __forceinline__ srsrc_t make_srsrc(const void *base, unsigned int byt
     return r;
 }
 
+// 16 bytes per lane from a buffer straight into LDS (no staging registers): lane L of the wave writes LDS bytes
+// [lds_base + 16 L, + 16) with the 16 bytes at offset voff + soff of the buffer (zeros past its end).  lds_base and soff are wave-uniform.
+__device__ __forceinline__ void load16_lds(unsigned int lds_base, unsigned int voff, srsrc_t rsrc, unsigned int soff) {
+    const unsigned int b = __builtin_amdgcn_readfirstlane(lds_base), so = __builtin_amdgcn_readfirstlane(soff);
+    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(b), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
+}
+
 template <class T>
 __device__ __forceinline__ void load_hstage(HStage<T> &st, srsrc_t prsrc, const unsigned int (&pvoff)[T::P_PER_THREAD],
                                             unsigned int padd, srsrc_t crsrc, const unsigned int (&cvoff)[T::C_PER_THREAD],

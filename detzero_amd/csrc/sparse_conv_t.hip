@@ -222,12 +222,8 @@ struct SpConvTArgs {
     unsigned int in_bytes, w_bytes, ltab_bytes;
 };
 
-// 16 bytes (4 bytes) per lane from a buffer straight into LDS at lds_base + lane * 16 (lane * 4); lds_base wave-uniform
+// load16_lds (hgemm.h) for 4 bytes per lane: LDS bytes [lds_base + 4 lane, + 4); lds_base and soff wave-uniform
 // (readfirstlane: both are wave-uniform by construction, the compiler cannot always prove it)
-__device__ __forceinline__ void t_load16_lds(unsigned int lds_base, unsigned int voff, srsrc_t rsrc, unsigned int soff) {
-    const unsigned int b = __builtin_amdgcn_readfirstlane(lds_base), so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(b), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
-}
 __device__ __forceinline__ void t_load4_lds(unsigned int lds_base, unsigned int voff, srsrc_t rsrc, unsigned int soff) {
     const unsigned int b = __builtin_amdgcn_readfirstlane(lds_base), so = __builtin_amdgcn_readfirstlane(soff);
     asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dword %1, %2, %3 offen lds" ::"s"(b), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
@@ -340,16 +336,16 @@ __global__ __launch_bounds__(T_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
         for (int j = 0; j < WL; ++j) {
             const int s = it.st * G + (G == 1 ? 0 : wpiece_g(j));
             const int tap = (it.kc < nk && s < T_SLOTS) ? tap_at(s) : -1;
-            t_load16_lds((unsigned int)(C::OFF_W + ring * C::WSLOT + (j * T_THREADS + wid * 64) * 16), tap >= 0 ? wpiece_voff(j) : OOB_OFFSET, crsrc,
-                         tap >= 0 ? (unsigned int)tap * tap_bytes + (unsigned int)(it.kc * 64) : 0u);
+            load16_lds((unsigned int)(C::OFF_W + ring * C::WSLOT + (j * T_THREADS + wid * 64) * 16), tap >= 0 ? wpiece_voff(j) : OOB_OFFSET, crsrc,
+                       tap >= 0 ? (unsigned int)tap * tap_bytes + (unsigned int)(it.kc * 64) : 0u);
         }
     };
     auto issue_l = [&](const It &it, int ring) {
         if constexpr (G == 4) {
             // one dwordx4 per lane: the 4 slots x 2 rows of pair p; slot group = step
             const bool ok = it.kc < nk && l_real && it.st * 4 < T_SLOTS;
-            t_load16_lds((unsigned int)(l_real ? C::OFF_L + ring * C::LSLOT + wid * 1024 : C::OFF_ZERO), ok ? (unsigned int)((wid * 64 + lane) * 16) : OOB_OFFSET,
-                         lrsrc, ok ? ltile + (unsigned int)(it.st * 4096) : 0u);
+            load16_lds((unsigned int)(l_real ? C::OFF_L + ring * C::LSLOT + wid * 1024 : C::OFF_ZERO), ok ? (unsigned int)((wid * 64 + lane) * 16) : OOB_OFFSET,
+                       lrsrc, ok ? ltile + (unsigned int)(it.st * 4096) : 0u);
         } else {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -377,9 +373,9 @@ __global__ __launch_bounds__(T_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
             asm volatile("" : "+v"(pc));
             voff = x_voff(i, hal_s[pc >> 2]);
         }
-        t_load16_lds((unsigned int)(C::OFF_X + buf * T_XBUF + (i * T_WAVES + wid) * 1024), voff, prsrc, (unsigned int)(kc * 64));
+        load16_lds((unsigned int)(C::OFF_X + buf * T_XBUF + (i * T_WAVES + wid) * 1024), voff, prsrc, (unsigned int)(kc * 64));
     };
-    auto issue_dummy = [&]() { t_load16_lds((unsigned int)C::OFF_ZERO, OOB_OFFSET, prsrc, 0u); };
+    auto issue_dummy = [&]() { load16_lds((unsigned int)C::OFF_ZERO, OOB_OFFSET, prsrc, 0u); };
 
     // local-table entries of this lane for the G slots of a step (slot g: low half = row l31, high half = row l31 + 32)
     struct LT { unsigned int e[G]; };

@@ -89,11 +89,6 @@ struct XCfg {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-__device__ __forceinline__ void x_load16_lds(unsigned int lds_base, unsigned int voff, srsrc_t rsrc, unsigned int soff) {
-    const unsigned int b = __builtin_amdgcn_readfirstlane(lds_base), so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(b), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
-}
-
 // store_tile_pair16 (hgemm.h) for this kernel: the output rows of the lane's items come in `orow` (fetched through the row map a
 // whole stage earlier: -1 = no row), and ALL residual groups of the tile are requested before the first fragment is staged - one
 // round trip to memory per tile instead of one per 32 x 32 fragment (measured: the residual cost of the per-fragment form was as much
@@ -351,8 +346,8 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         const int left = s.wcnt - 1 - wid * 16 - I * NW * 16;     // rows of the window after the first row of my run
         // (rows past the window's end re-read its last row: always inside the buffer, never referenced)
         const unsigned int voff = left >= 0 ? (unsigned int)min(lrow, left) * row_bytes + lpiece : OOB_OFFSET;
-        x_load16_lds((unsigned int)(C::OFF_WIN + s.wb * C::WIN_BYTES) + wid_lds + (unsigned int)(I * NW * 1024), voff, prsrc,
-                     (unsigned int)s.wlo * row_bytes + (unsigned int)(s.kc * 64) + wid_rows + (unsigned int)I * nw_rows);
+        load16_lds((unsigned int)(C::OFF_WIN + s.wb * C::WIN_BYTES) + wid_lds + (unsigned int)(I * NW * 1024), voff, prsrc,
+                   (unsigned int)s.wlo * row_bytes + (unsigned int)(s.kc * 64) + wid_rows + (unsigned int)I * nw_rows);
     };
     // table word (fragment PTI, window row TY) of stage s's slab
     auto issue_pw = [&](const XStage &s, auto pt_t, auto ty_t) {
@@ -370,9 +365,9 @@ __global__ __launch_bounds__(C::THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         constexpr int I = decltype(i_t)::value;
         constexpr bool part = C::WJ % NW != 0 && I == C::WPW - 1;             // the last, partial round
         const bool ok = !part || w_last_ok;
-        x_load16_lds(ok ? (unsigned int)(C::OFF_W + slot * C::WSLOT_BYTES) + wid_lds + (unsigned int)(I * NW * 1024) : (unsigned int)C::OFF_TRASH,
-                     ok && s.live ? w_voff : OOB_OFFSET, crsrc,
-                     (unsigned int)(s.tz * 9 + q * TAPS + I * (NW / C::R)) * tap_bytes + (unsigned int)(s.kc * 64) + w_soff_w);
+        load16_lds(ok ? (unsigned int)(C::OFF_W + slot * C::WSLOT_BYTES) + wid_lds + (unsigned int)(I * NW * 1024) : (unsigned int)C::OFF_TRASH,
+                   ok && s.live ? w_voff : OOB_OFFSET, crsrc,
+                   (unsigned int)(s.tz * 9 + q * TAPS + I * (NW / C::R)) * tap_bytes + (unsigned int)(s.kc * 64) + w_soff_w);
     };
 
     f32x16 acc[CT][PT];

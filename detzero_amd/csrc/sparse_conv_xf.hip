@@ -45,22 +45,9 @@
 // dz_spconv_forward (tap, then channel) the result differs by fp32 summation-order noise only.
 #include <type_traits>
 
-#include "hgemm.h"
+#include "sparse_conv_xw.h"
 
 namespace dz {
-
-struct SpConvXFArgs {
-    const float *in;            // fp32 rows (in_rows, cin)
-    const int *nbr;             // packed table (9, cap), in tap-set order when perm is given
-    const int *win;             // (units, 3, 2): first input row, row count of the window of (unit, tz)
-    const int *d_m_out;
-    const float *w;             // (27, cin, cout) fp32
-    const float *scale, *shift, *residual;
-    float *out;
-    const int *perm;            // output row of each position when the table is in tap-set order, or null
-    int cin, cout, cap, relu;
-    unsigned int in_bytes, w_bytes;
-};
 
 template <int COUT_, int WP_, int WC_, int RCAP_>
 struct XFCfg {
@@ -68,6 +55,7 @@ struct XFCfg {
     static constexpr int NW = WP * WC, THREADS = 64 * NW;
     static constexpr int CT = COUT / (32 * WC);              // 32-channel fragments per wave
     static constexpr int UR = WP * 32;                       // output rows per unit
+    static constexpr int SPS = 3;                            // steps per stage (tz, kc): one per window row ty
     static constexpr int WIN_BYTES = (RCAP + 1) * 64;        // + the zero row missing neighbours read
     static constexpr int TAP_BYTES = 16 * COUT * 4;          // weight slice of one tap: 16 input channels x COUT
     static constexpr int WSTEP_BYTES = 3 * TAP_BYTES;
@@ -79,83 +67,37 @@ struct XFCfg {
     static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 };
 
-__device__ __forceinline__ void xf_load16_lds(unsigned int lds_base, unsigned int voff, srsrc_t rsrc, unsigned int soff) {
-    const unsigned int b = __builtin_amdgcn_readfirstlane(lds_base), so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(b), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
-}
-
 template <class C>
-__global__ __launch_bounds__(C::THREADS) void k_spconv_xf(SpConvXFArgs a) {
+__global__ __launch_bounds__(C::THREADS) void k_spconv_xf(SpConvXWArgs a) {
     constexpr int CT = C::CT, COUT = C::COUT, RCAP = C::RCAP, NW = C::NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wp = wid / C::WC, wc = wid % C::WC, l31 = lane & 31, kh = lane >> 5;
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wc = wid % C::WC, l31 = lane & 31, kh = lane >> 5;
     const int m = min(*a.d_m_out, a.cap);
-    const int unit = blockIdx.x;
-    if (unit * C::UR >= m) return;
-    const int nk = a.cin / 16;
-    const srsrc_t prsrc = make_srsrc(a.in, a.in_bytes), crsrc = make_srsrc(a.w, a.w_bytes);
-    const unsigned int row_bytes = (unsigned int)a.cin * 4u;
-    const unsigned int in_rows = a.in_bytes / row_bytes;
+    if ((int)blockIdx.x * C::UR >= m) return;
+    const srsrc_t crsrc = make_srsrc(a.w, a.w_bytes);
+    const unsigned int in_rows = a.in_bytes / ((unsigned int)a.cin * 4u);
+    XWUnit<C> u(a, smem, m, wid, lane);
+    const int nsteps = u.nz * u.nk * C::SPS;
 
-    // the zero rows of the two window buffers
-    if (tid < 32) reinterpret_cast<unsigned int *>(smem + C::OFF_WIN + (tid >> 4) * C::WIN_BYTES + RCAP * 64)[tid & 15] = 0u;
-
-    // windows of the unit: (first row, rows) per z slab; the slabs that have any neighbour, in order (the centre slab always has)
-    int wlo[3], wn[3];
-#pragma unroll
-    for (int z = 0; z < 3; ++z) {
-        wlo[z] = __builtin_amdgcn_readfirstlane(a.win[(size_t)unit * 6 + 2 * z]);
-        wn[z] = __builtin_amdgcn_readfirstlane(a.win[(size_t)unit * 6 + 2 * z + 1]);
-    }
-    int zlist = 0, nz = 0;          // two bits per live slab
-#pragma unroll
-    for (int z = 0; z < 3; ++z)
-        if (wn[z] > 0) { zlist |= z << (2 * nz); ++nz; }
-    const int nsteps = nz * nk * 3;
-
-    // packed table words of my row (position), all nine (tz, ty) lines: zero = no neighbour for positions past the level's end
-    const int pos = unit * C::UR + wp * 32 + l31;
-    unsigned int pw[9];
-#pragma unroll
-    for (int g = 0; g < 9; ++g) pw[g] = pos < m ? (unsigned int)a.nbr[(size_t)g * a.cap + pos] : 0u;
-
-    // ---- direct loads: lane L of a 1 KB load writes LDS bytes [16 L, 16 L + 16) of its run.
-    // Window runs = 16 rows x 64 bytes: row L >> 2, slot L & 3, which holds source piece slot ^ ((row >> 2) & 3), and (row >> 2) & 3 ==
-    // (L >> 4) & 3 because runs start at multiples of 16 rows.  Weight runs are 1 KB of contiguous memory, copied as they are.
-    const int lrow = lane >> 2;
-    const unsigned int lpiece = (unsigned int)((lane & 3) ^ ((lane >> 4) & 3)) << 4;
-    auto stage_of = [&](int i, int &tz, int &kc, int &ty) {
-        const int st = i / 3;
-        ty = i - st * 3;
-        const int zi = st / nk;
-        kc = st - zi * nk;
-        tz = (zlist >> (2 * zi)) & 3;
-    };
-    auto pick = [](const int (&v)[3], int z) { return z == 0 ? v[0] : (z == 1 ? v[1] : v[2]); };
     auto issue = [&](int i) {
         if (i >= nsteps) return;
         int tz, kc, ty;
-        stage_of(i, tz, kc, ty);
-        // weights of the step's three taps: tap (tz*9 + ty*3 + tx), input channels [kc*16, kc*16 + 16), all COUT
+        u.stage_of(i, tz, kc, ty);
+        // weights of the step's three taps: tap (tz*9 + ty*3 + tx), input channels [kc*16, kc*16 + 16), all COUT; 1 KB runs of
+        // contiguous memory, copied as they are
         const unsigned int wbuf = (unsigned int)(C::OFF_W + (i & 1) * C::WSTEP_BYTES);
         for (int j = wid; j < C::WRUNS; j += NW) {
             const int tx = j / (C::TAP_BYTES / 1024), part = j % (C::TAP_BYTES / 1024);
             const unsigned int src = (unsigned int)(((tz * 9 + ty * 3 + tx) * a.cin + kc * 16) * COUT * 4 + part * 1024);
-            xf_load16_lds(wbuf + (unsigned int)j * 1024u, (unsigned int)lane * 16u, crsrc, src);
+            load16_lds(wbuf + (unsigned int)j * 1024u, (unsigned int)lane * 16u, crsrc, src);
         }
         // the window of the stage, at its first step (a window beyond RCAP rows is not staged: gather mode)
-        const int n = pick(wn, tz);
+        const int n = xw_pick(u.wn, tz);
         if (ty == 0 && n <= RCAP) {
-            const int lo = pick(wlo, tz);
-            const unsigned int wbase = (unsigned int)(C::OFF_WIN + ((i / 3) & 1) * C::WIN_BYTES);
-            const int nruns = (n + 15) >> 4;            // <= RCAP / 16: the zero row is never overwritten
-            for (int j = wid; j < nruns; j += NW) {
-                // (rows past the window's end re-read its last row: inside the input, never referenced)
-                const int left = n - 1 - j * 16;
-                const unsigned int voff = (unsigned int)min(lrow, left) * row_bytes + lpiece;
-                xf_load16_lds(wbase + (unsigned int)j * 1024u, voff, prsrc, (unsigned int)(lo + j * 16) * row_bytes + (unsigned int)(kc * 64));
-            }
+            const int lo = xw_pick(u.wlo, tz);
+            const int nruns = (n + 15) >> 4;
+            for (int j = wid; j < nruns; j += NW) u.load_window_run(i / C::SPS, j, lo, n, kc);
         }
     };
 
@@ -169,7 +111,7 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xf(SpConvXFArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // (the table words are in their registers from here on: no wait for them - and with them for the direct loads in flight - in the loop)
 #pragma unroll
-    for (int g = 0; g < 9; ++g) asm volatile("" : "+v"(pw[g]));
+    for (int g = 0; g < 9; ++g) asm volatile("" : "+v"(u.pw[g]));
     __syncthreads();
 
     const unsigned int wcol = (unsigned int)((wc * CT * 32 + l31) * 4 + kh * 8 * COUT * 4);     // my weight column, input channel 8 kh of the chunk
@@ -179,13 +121,14 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xf(SpConvXFArgs a) {
     auto step = [&](int i, auto gm_t) {
         constexpr bool GM = decltype(gm_t)::value;
         int tz, kc, ty;
-        stage_of(i, tz, kc, ty);
-        const int lo = pick(wlo, tz), n = pick(wn, tz);
+        u.stage_of(i, tz, kc, ty);
+        const int lo = xw_pick(u.wlo, tz), n = xw_pick(u.wn, tz);
+        const unsigned int(&pw)[9] = u.pw;
         const unsigned int e = tz == 0 ? (ty == 0 ? pw[0] : ty == 1 ? pw[1] : pw[2])
                              : tz == 1 ? (ty == 0 ? pw[3] : ty == 1 ? pw[4] : pw[5]) : (ty == 0 ? pw[6] : ty == 1 ? pw[7] : pw[8]);
         const int rank = (int)(e & 0x1FFFFFFFu);
         const unsigned char *const wbuf = smem + C::OFF_W + (i & 1) * C::WSTEP_BYTES + wcol;
-        const unsigned char *const winb = smem + C::OFF_WIN + ((i / 3) & 1) * C::WIN_BYTES;
+        const unsigned char *const winb = smem + C::OFF_WIN + ((i / C::SPS) & 1) * C::WIN_BYTES;
         auto tap = [&](auto tx_t) {
             constexpr int tx = decltype(tx_t)::value;
             const int idx = rank + (tx == 0 ? -1 : tx == 1 ? 0 : (int)((e >> 30) & 1u));       // input row of the tap
@@ -229,40 +172,15 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xf(SpConvXFArgs a) {
     };
     for (int i = 0; i < nsteps; ++i) {
         int tz, kc, ty;
-        stage_of(i, tz, kc, ty);
-        if (pick(wn, tz) > RCAP) step(i, std::true_type{});
+        u.stage_of(i, tz, kc, ty);
+        if (xw_pick(u.wn, tz) > RCAP) step(i, std::true_type{});
         else step(i, std::false_type{});
         // the next step's loads have landed, and everyone is done with the buffers the loads issued next will overwrite
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
 
-    // ---- epilogue: register quad j of fragment ct = channels ct*32 + 8 j + 4 kh .. + 3 of my row
-    if (pos >= m) return;
-    const int orow = a.perm ? a.perm[pos] : pos;
-    const size_t rbase = (size_t)orow * COUT;
-    // (per 32-channel fragment all of scale / shift / residual are requested before the first is used: one memory round trip, not twelve)
-    const bool has_sc = a.scale != nullptr, has_sh = a.shift != nullptr, has_res = a.residual != nullptr;
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        float4 sc[4], sh[4], rs[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ch = wc * CT * 32 + ct * 32 + j * 8 + kh * 4;
-            sc[j] = has_sc ? *reinterpret_cast<const float4 *>(a.scale + ch) : make_float4(1.f, 1.f, 1.f, 1.f);
-            sh[j] = has_sh ? *reinterpret_cast<const float4 *>(a.shift + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
-            rs[j] = has_res ? *reinterpret_cast<const float4 *>(a.residual + rbase + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ch = wc * CT * 32 + ct * 32 + j * 8 + kh * 4;
-            float4 v = make_float4(fmaf(acc[ct][4 * j], sc[j].x, sh[j].x), fmaf(acc[ct][4 * j + 1], sc[j].y, sh[j].y),
-                                   fmaf(acc[ct][4 * j + 2], sc[j].z, sh[j].z), fmaf(acc[ct][4 * j + 3], sc[j].w, sh[j].w));
-            if (has_res) { v.x += rs[j].x; v.y += rs[j].y; v.z += rs[j].z; v.w += rs[j].w; }
-            if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            *reinterpret_cast<float4 *>(a.out + rbase + ch) = v;
-        }
-    }
+    xw_epilogue<C>(a, acc, u.pos, m, wc, kh);
 }
 
 // unit rows = dz_spconv_x_tile_rows of the pair16 engine's shipped configurations (one index serves both arithmetics)
@@ -272,19 +190,9 @@ using XF32 = XFCfg<32, 8, 1, 512>;
 using XF64 = XFCfg<64, 8, 1, 432>;
 using XF128 = XFCfg<128, 4, 2, 240>;
 
-template <class C>
-static int launch_xf(const SpConvXFArgs &a, hipStream_t stream) {
-    static PerDeviceFlags done;
-    if (int rc = reserve_lds(reinterpret_cast<const void *>(&k_spconv_xf<C>), C::LDS_BYTES, done, "dz_spconv_forward_x_f32")) return rc;
-    hipLaunchKernelGGL((k_spconv_xf<C>), dim3(ceil_div(a.cap, C::UR)), dim3(C::THREADS), C::LDS_BYTES, stream, a);
-    DZ_LAUNCH_CHECK();
-    return DZ_OK;
-}
-
-static int xf_tile_rows(int cin, int cout) {
-    if (cin != cout) return 0;
-    return cout == 32 ? XF32::UR : cout == 64 ? XF64::UR : cout == 128 ? XF128::UR : 0;
-}
+static const XWVariant kXF[] = {{32, XF32::UR, XF32::RCAP, "k_spconv_xf<32>", launch_xw<k_spconv_xf<XF32>, XF32>},
+                                 {64, XF64::UR, XF64::RCAP, "k_spconv_xf<64>", launch_xw<k_spconv_xf<XF64>, XF64>},
+                                 {128, XF128::UR, XF128::RCAP, "k_spconv_xf<128>", launch_xw<k_spconv_xf<XF128>, XF128>}};
 
 }  // namespace dz
 
@@ -293,40 +201,20 @@ using namespace dz;
 extern "C" {
 
 int dz_spconv_x_f32_window_rows(int cin, int cout) {
-    if (cin != cout) return 0;
-    return cout == 32 ? XF32::RCAP : cout == 64 ? XF64::RCAP : cout == 128 ? XF128::RCAP : 0;
+    const XWVariant *v = xw_select(kXF, cin, cout);
+    return v ? v->window_rows : 0;
 }
 
 const char *dz_spconv_x_f32_variant(int cin, int cout) {
-    if (cin == 32 && cout == 32) return "k_spconv_xf<32>";
-    if (cin == 64 && cout == 64) return "k_spconv_xf<64>";
-    if (cin == 128 && cout == 128) return "k_spconv_xf<128>";
-    return "none";
+    const XWVariant *v = xw_select(kXF, cin, cout);
+    return v ? v->name : "none";
 }
 
 int dz_spconv_forward_x_f32(const float *in, int in_rows, int cin, const int *nbr_packed, const int *perm, int *windows, int tile_rows,
                             int cap_out, const int *d_m_out, const float *w, const float *scale, const float *shift, const float *residual,
-                            int relu, float *out, int cout, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    DZ_CHECK_ARG(in && nbr_packed && windows && d_m_out && w && out, "dz_spconv_forward_x_f32: null pointer");
-    const int tr = xf_tile_rows(cin, cout);
-    if (tr == 0) {
-        set_error("dz_spconv_forward_x_f32: %d -> %d channels (submanifold 32 -> 32, 64 -> 64, 128 -> 128 only)", cin, cout);
-        return DZ_ERR_UNSUPPORTED;
-    }
-    DZ_CHECK_ARG(tile_rows == tr, "dz_spconv_forward_x_f32: windows built for %d-row tiles, the %d-channel kernel uses %d", tile_rows, cout, tr);
-    DZ_CHECK_ARG(cap_out >= 0 && cap_out < (1 << 29), "dz_spconv_forward_x_f32: capacity %d outside the packed table's 29-bit ranks", cap_out);
-    const size_t in_bytes = (size_t)(in_rows < 0 ? 0 : in_rows) * cin * sizeof(float), out_bytes = (size_t)cap_out * cout * sizeof(float);
-    if (in_rows < 0 || in_bytes >= 0x80000000ull || out_bytes >= 0x80000000ull) {
-        set_error("dz_spconv_forward_x_f32: input of %zu / output of %zu bytes exceeds the 2 GiB buffer-addressing limit", in_bytes, out_bytes);
-        return DZ_ERR_UNSUPPORTED;
-    }
-    if (cap_out == 0) return DZ_OK;
-    SpConvXFArgs a{in, nbr_packed, windows, d_m_out, w, scale, shift, residual, out, perm, cin, cout, cap_out, relu,
-                   (unsigned int)in_bytes, (unsigned int)((size_t)27 * cin * cout * sizeof(float))};
-    if (cout == 32) return launch_xf<XF32>(a, stream);
-    if (cout == 64) return launch_xf<XF64>(a, stream);
-    return launch_xf<XF128>(a, stream);
+                            int relu, float *out, int cout, void *stream) {
+    return xw_forward("dz_spconv_forward_x_f32", xw_select(kXF, cin, cout), (size_t)27 * cin * cout * sizeof(float), in, in_rows, cin, nbr_packed,
+                      perm, windows, tile_rows, cap_out, d_m_out, w, scale, shift, residual, relu, out, cout, stream);
 }
 
 }  // extern "C"

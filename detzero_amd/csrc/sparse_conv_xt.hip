@@ -11,10 +11,11 @@
 // bit, none the value with those limbs flushed (test_subnormal_limbs_are_measured).  Below 2^-110 the split itself
 // stops being exact (bf16's quantum there is 2^-133): the result is then within 2^-133 |w| of x . w.
 //
-// Everything the index decides is k_spconv_xf's, unchanged: the unit (WP x 32 rows = dz_spconv_x_tile_rows), the windows and the
-// zero row behind them, the gather-mode arm for a window longer than RCAP (same taps, same order), the packed-table decode, the
+// Everything the index decides is k_spconv_xf's, from the frame both kernels share (sparse_conv_xw.h): the unit (WP x 32 rows =
+// dz_spconv_x_tile_rows), the windows and the zero row behind them, the packed table words, the epilogue and the write contract, the
+// checks of the entry point.  Written out here as there: the gather-mode arm for a window longer than RCAP (same taps, same order), the
 // ballot skip of (fragment, tap) pairs, the operand mapping (lane (row l & 31, half l >> 5) holds channels 8 half .. 8 half + 7 of
-// the chunk = the B operand of ONE 32x32x16 k-step; D[cout x row]) and with it the epilogue and the write contract.
+// the chunk = the B operand of ONE 32x32x16 k-step; D[cout x row]).
 //
 // Where the split happens - form (B) of the two workable ones, at every width: the fp32 window stays in LDS exactly as k_spconv_xf
 // stages it (direct loads, 64 bytes per row and chunk) and the 8 values of a fragment read are split in registers: 4 x split3x2 =
@@ -48,23 +49,10 @@
 //   ballot would have added exact zeros).  No atomics; two launches agree bit for bit.
 #include <type_traits>
 
-#include "hgemm.h"
 #include "limb3.h"
+#include "sparse_conv_xw.h"
 
 namespace dz {
-
-struct SpConvXTArgs {
-    const float *in;            // fp32 rows (in_rows, cin)
-    const int *nbr;             // packed table (9, cap), in tap-set order when perm is given
-    const int *win;             // (units, 3, 2): first input row, row count of the window of (unit, tz)
-    const int *d_m_out;
-    const float *w;             // (27, cout, cin / 8, 3 x 16 B) limb words
-    const float *scale, *shift, *residual;
-    float *out;
-    const int *perm;            // output row of each position when the table is in tap-set order, or null
-    int cin, cout, cap, relu;
-    unsigned int in_bytes, w_bytes;
-};
 
 template <int COUT_, int WP_, int WC_, int RCAP_, int TPS_>
 struct XTCfg {
@@ -85,68 +73,29 @@ struct XTCfg {
     static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 };
 
-__device__ __forceinline__ void xt_load16_lds(unsigned int lds_base, unsigned int voff, srsrc_t rsrc, unsigned int soff) {
-    const unsigned int b = __builtin_amdgcn_readfirstlane(lds_base), so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(b), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
-}
-
 template <class C>
-__global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXTArgs a) {
+__global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXWArgs a) {
     constexpr int CT = C::CT, COUT = C::COUT, RCAP = C::RCAP, NW = C::NW, TPS = C::TPS, SPS = C::SPS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wp = wid / C::WC, wc = wid % C::WC, l31 = lane & 31, kh = lane >> 5;
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wc = wid % C::WC, l31 = lane & 31, kh = lane >> 5;
     const int m = min(*a.d_m_out, a.cap);
-    const int unit = blockIdx.x;
-    if (unit * C::UR >= m) return;
-    const int nk = a.cin / 16;
-    const srsrc_t prsrc = make_srsrc(a.in, a.in_bytes), crsrc = make_srsrc(a.w, a.w_bytes);
-    const unsigned int row_bytes = (unsigned int)a.cin * 4u;
-    const unsigned int in_rows = a.in_bytes / row_bytes;
+    if ((int)blockIdx.x * C::UR >= m) return;
+    const srsrc_t crsrc = make_srsrc(a.w, a.w_bytes);
+    const unsigned int in_rows = a.in_bytes / ((unsigned int)a.cin * 4u);
     const unsigned int wrow_bytes = (unsigned int)a.cin * 6u;           // a weight row: cin / 8 groups of 48 bytes
+    XWUnit<C> u(a, smem, m, wid, lane);
+    const int nsteps = u.nz * u.nk * SPS;
 
-    // the zero rows of the two window buffers
-    if (tid < 32) reinterpret_cast<unsigned int *>(smem + C::OFF_WIN + (tid >> 4) * C::WIN_BYTES + RCAP * 64)[tid & 15] = 0u;
-
-    // windows of the unit: (first row, rows) per z slab; the slabs that have any neighbour, in order (the centre slab always has)
-    int wlo[3], wn[3];
-#pragma unroll
-    for (int z = 0; z < 3; ++z) {
-        wlo[z] = __builtin_amdgcn_readfirstlane(a.win[(size_t)unit * 6 + 2 * z]);
-        wn[z] = __builtin_amdgcn_readfirstlane(a.win[(size_t)unit * 6 + 2 * z + 1]);
-    }
-    int zlist = 0, nz = 0;          // two bits per live slab
-#pragma unroll
-    for (int z = 0; z < 3; ++z)
-        if (wn[z] > 0) { zlist |= z << (2 * nz); ++nz; }
-    const int nsteps = nz * nk * SPS;
-
-    // packed table words of my row (position), all nine (tz, ty) lines: zero = no neighbour for positions past the level's end
-    const int pos = unit * C::UR + wp * 32 + l31;
-    unsigned int pw[9];
-#pragma unroll
-    for (int g = 0; g < 9; ++g) pw[g] = pos < m ? (unsigned int)a.nbr[(size_t)g * a.cap + pos] : 0u;
-
-    // ---- direct loads: lane L of a 1 KB load writes LDS bytes [16 L, 16 L + 16) of its run.
-    // Window runs = 16 rows x 64 bytes: row L >> 2, slot L & 3, which holds source piece slot ^ ((row >> 2) & 3), and (row >> 2) & 3 ==
-    // (L >> 4) & 3 because runs start at multiples of 16 rows.  Weight runs: slot d = part * 64 + L of a tap slice = (row d / 6, slot
-    // d % 6), which holds source piece (slot + ((row >> 3) & 1)) mod 6.
-    const int lrow = lane >> 2;
-    const unsigned int lpiece = (unsigned int)((lane & 3) ^ ((lane >> 4) & 3)) << 4;
-    // step i: stage st = i / SPS = (slab, chunk kc), r = i % SPS = window row ty (TPS == 3) or tap ty * 3 + tx (TPS == 1)
-    auto stage_of = [&](int i, int &tz, int &kc, int &r) {
-        const int st = i / SPS;
-        r = i - st * SPS;
-        const int zi = st / nk;
-        kc = st - zi * nk;
-        tz = (zlist >> (2 * zi)) & 3;
-    };
-    auto pick = [](const int (&v)[3], int z) { return z == 0 ? v[0] : (z == 1 ? v[1] : v[2]); };
+    // step i of a stage: r = window row ty (TPS == 3) or tap ty * 3 + tx (TPS == 1)
+    // (through a lambda: with u.stage_of called in place the 128-channel kernel computes i / 9 once more per step body)
+    auto stage_of = [&](int i, int &tz, int &kc, int &r) { u.stage_of(i, tz, kc, r); };
     auto issue = [&](int i) {
         if (i >= nsteps) return;
         int tz, kc, r;
         stage_of(i, tz, kc, r);
-        // limb weights of the step's taps: tap tz*9 + ty*3 + tx, all COUT rows, the two 48-byte groups of input channels [kc*16, kc*16 + 16)
+        // limb weights of the step's taps: tap tz*9 + ty*3 + tx, all COUT rows, the two 48-byte groups of input channels [kc*16, kc*16 + 16).
+        // Slot d = part * 64 + lane of a tap slice = (row d / 6, slot d % 6), which holds source piece (slot + ((row >> 3) & 1)) mod 6
         const unsigned int wbuf = (unsigned int)(C::OFF_W + (i & 1) * C::WSTEP_BYTES);
         const int tap0 = tz * 9 + (TPS == 3 ? r * 3 : r);
         for (int j = wid; j < C::WRUNS; j += NW) {
@@ -156,20 +105,14 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXTArgs a) {
             p = p >= 6 ? p - 6 : p;
             const unsigned int voff = (unsigned int)co * wrow_bytes + (unsigned int)p * 16u;
             const unsigned int src = (unsigned int)((tap0 + t) * COUT) * wrow_bytes + (unsigned int)(kc * 96);
-            xt_load16_lds(wbuf + (unsigned int)j * 1024u, voff, crsrc, src);
+            load16_lds(wbuf + (unsigned int)j * 1024u, voff, crsrc, src);
         }
         // the window of the stage, at its first step (a window beyond RCAP rows is not staged: gather mode)
-        const int n = pick(wn, tz);
+        const int n = xw_pick(u.wn, tz);
         if (r == 0 && n <= RCAP) {
-            const int lo = pick(wlo, tz);
-            const unsigned int wbase = (unsigned int)(C::OFF_WIN + ((i / SPS) & 1) * C::WIN_BYTES);
-            const int nruns = (n + 15) >> 4;            // <= RCAP / 16: the zero row is never overwritten
-            for (int j = wid; j < nruns; j += NW) {
-                // (rows past the window's end re-read its last row: inside the input, never referenced)
-                const int left = n - 1 - j * 16;
-                const unsigned int voff = (unsigned int)min(lrow, left) * row_bytes + lpiece;
-                xt_load16_lds(wbase + (unsigned int)j * 1024u, voff, prsrc, (unsigned int)(lo + j * 16) * row_bytes + (unsigned int)(kc * 64));
-            }
+            const int lo = xw_pick(u.wlo, tz);
+            const int nruns = (n + 15) >> 4;
+            for (int j = wid; j < nruns; j += NW) u.load_window_run(i / SPS, j, lo, n, kc);
         }
     };
 
@@ -183,7 +126,7 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXTArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // (the table words are in their registers from here on: no wait for them - and with them for the direct loads in flight - in the loop)
 #pragma unroll
-    for (int g = 0; g < 9; ++g) asm volatile("" : "+v"(pw[g]));
+    for (int g = 0; g < 9; ++g) asm volatile("" : "+v"(u.pw[g]));
     __syncthreads();
 
     // my weight row of a tap slice and the slots of its three limbs (h, m, l of input channels 8 kh .. 8 kh + 7 of the chunk)
@@ -199,12 +142,12 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXTArgs a) {
         int tz, kc, r;
         stage_of(i, tz, kc, r);
         const int ty = TPS == 3 ? r : r / 3;
-        const int lo = pick(wlo, tz), n = pick(wn, tz);
+        const int lo = xw_pick(u.wlo, tz), n = xw_pick(u.wn, tz);
         const int line = tz * 3 + ty;
-        unsigned int e = pw[0];
+        unsigned int e = u.pw[0];
 #pragma unroll
         for (int g = 1; g < 9; ++g) {
-            e = line == g ? pw[g] : e;
+            e = line == g ? u.pw[g] : e;
             asm volatile("" : "+v"(e));          // (a chain of selects, not an indexed read of the table words: that would move them to scratch)
         }
         const int rank = (int)(e & 0x1FFFFFFFu);
@@ -278,39 +221,14 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXTArgs a) {
     for (int i = 0; i < nsteps; ++i) {
         int tz, kc, r;
         stage_of(i, tz, kc, r);
-        if (pick(wn, tz) > RCAP) step(i, std::true_type{});
+        if (xw_pick(u.wn, tz) > RCAP) step(i, std::true_type{});
         else step(i, std::false_type{});
         // the next step's loads have landed, and everyone is done with the buffers the loads issued next will overwrite
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
 
-    // ---- epilogue: register quad j of fragment ct = channels ct*32 + 8 j + 4 kh .. + 3 of my row
-    if (pos >= m) return;
-    const int orow = a.perm ? a.perm[pos] : pos;
-    const size_t rbase = (size_t)orow * COUT;
-    // (per 32-channel fragment all of scale / shift / residual are requested before the first is used: one memory round trip, not twelve)
-    const bool has_sc = a.scale != nullptr, has_sh = a.shift != nullptr, has_res = a.residual != nullptr;
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        float4 sc[4], sh[4], rs[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ch = wc * CT * 32 + ct * 32 + j * 8 + kh * 4;
-            sc[j] = has_sc ? *reinterpret_cast<const float4 *>(a.scale + ch) : make_float4(1.f, 1.f, 1.f, 1.f);
-            sh[j] = has_sh ? *reinterpret_cast<const float4 *>(a.shift + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
-            rs[j] = has_res ? *reinterpret_cast<const float4 *>(a.residual + rbase + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ch = wc * CT * 32 + ct * 32 + j * 8 + kh * 4;
-            float4 v = make_float4(fmaf(acc[ct][4 * j], sc[j].x, sh[j].x), fmaf(acc[ct][4 * j + 1], sc[j].y, sh[j].y),
-                                   fmaf(acc[ct][4 * j + 2], sc[j].z, sh[j].z), fmaf(acc[ct][4 * j + 3], sc[j].w, sh[j].w));
-            if (has_res) { v.x += rs[j].x; v.y += rs[j].y; v.z += rs[j].z; v.w += rs[j].w; }
-            if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            *reinterpret_cast<float4 *>(a.out + rbase + ch) = v;
-        }
-    }
+    xw_epilogue<C>(a, acc, u.pos, m, wc, kh);
 }
 
 // unit rows = dz_spconv_x_tile_rows of the pair16 engine's shipped configurations (one index serves every arithmetic)
@@ -320,28 +238,23 @@ using XT64 = XTCfg<64, 8, 1, 336, 3>;
 using XT128 = XTCfg<128, 4, 2, 432, 1>;
 
 // Which widths the selector offers: a width ships only where it measured faster than BOTH existing fp32 kernels of its layer (the gather
-// kernel and k_spconv_xf; DESIGN.md 2h-bis has the numbers).  A width that is off reports 0 window rows and "none": the backbone keeps
-// such a layer on k_spconv_xf.
-constexpr bool XT_SHIP_32 = true, XT_SHIP_64 = true, XT_SHIP_128 = true;
+// kernel and k_spconv_xf; DESIGN.md 2h-bis has the numbers).  A width that is off has no row below and no kernel instance; it reports
+// 0 window rows and "none": the backbone keeps such a layer on k_spconv_xf.
+#define XT_SHIP_32 1
+#define XT_SHIP_64 1
+#define XT_SHIP_128 1
 
-template <class C>
-static int launch_xt(const SpConvXTArgs &a, hipStream_t stream) {
-    static PerDeviceFlags done;
-    if (int rc = reserve_lds(reinterpret_cast<const void *>(&k_spconv_xt<C>), C::LDS_BYTES, done, "dz_spconv_forward_x_limb3")) return rc;
-    hipLaunchKernelGGL((k_spconv_xt<C>), dim3(ceil_div(a.cap, C::UR)), dim3(C::THREADS), C::LDS_BYTES, stream, a);
-    DZ_LAUNCH_CHECK();
-    return DZ_OK;
-}
-
-static bool xt_ships(int cin, int cout) {
-    if (cin != cout) return false;
-    return (cout == 32 && XT_SHIP_32) || (cout == 64 && XT_SHIP_64) || (cout == 128 && XT_SHIP_128);
-}
-
-static int xt_tile_rows(int cin, int cout) {
-    if (!xt_ships(cin, cout)) return 0;
-    return cout == 32 ? XT32::UR : cout == 64 ? XT64::UR : XT128::UR;
-}
+static const XWVariant kXT[] = {
+#if XT_SHIP_32
+    {32, XT32::UR, XT32::RCAP, "k_spconv_xt<32>", launch_xw<k_spconv_xt<XT32>, XT32>},
+#endif
+#if XT_SHIP_64
+    {64, XT64::UR, XT64::RCAP, "k_spconv_xt<64>", launch_xw<k_spconv_xt<XT64>, XT64>},
+#endif
+#if XT_SHIP_128
+    {128, XT128::UR, XT128::RCAP, "k_spconv_xt<128>", launch_xw<k_spconv_xt<XT128>, XT128>},
+#endif
+};
 
 }  // namespace dz
 
@@ -350,39 +263,20 @@ using namespace dz;
 extern "C" {
 
 int dz_spconv_x_limb3_window_rows(int cin, int cout) {
-    if (!xt_ships(cin, cout)) return 0;
-    return cout == 32 ? XT32::RCAP : cout == 64 ? XT64::RCAP : XT128::RCAP;
+    const XWVariant *v = xw_select(kXT, cin, cout);
+    return v ? v->window_rows : 0;
 }
 
 const char *dz_spconv_x_limb3_variant(int cin, int cout) {
-    if (!xt_ships(cin, cout)) return "none";
-    return cout == 32 ? "k_spconv_xt<32>" : cout == 64 ? "k_spconv_xt<64>" : "k_spconv_xt<128>";
+    const XWVariant *v = xw_select(kXT, cin, cout);
+    return v ? v->name : "none";
 }
 
 int dz_spconv_forward_x_limb3(const float *in, int in_rows, int cin, const int *nbr_packed, const int *perm, int *windows, int tile_rows,
                               int cap_out, const int *d_m_out, const float *w, const float *scale, const float *shift, const float *residual,
-                              int relu, float *out, int cout, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    DZ_CHECK_ARG(in && nbr_packed && windows && d_m_out && w && out, "dz_spconv_forward_x_limb3: null pointer");
-    const int tr = xt_tile_rows(cin, cout);
-    if (tr == 0) {
-        set_error("dz_spconv_forward_x_limb3: %d -> %d channels (submanifold 32 -> 32, 64 -> 64, 128 -> 128 only)", cin, cout);
-        return DZ_ERR_UNSUPPORTED;
-    }
-    DZ_CHECK_ARG(tile_rows == tr, "dz_spconv_forward_x_limb3: windows built for %d-row tiles, the %d-channel kernel uses %d", tile_rows, cout, tr);
-    DZ_CHECK_ARG(cap_out >= 0 && cap_out < (1 << 29), "dz_spconv_forward_x_limb3: capacity %d outside the packed table's 29-bit ranks", cap_out);
-    const size_t in_bytes = (size_t)(in_rows < 0 ? 0 : in_rows) * cin * sizeof(float), out_bytes = (size_t)cap_out * cout * sizeof(float);
-    if (in_rows < 0 || in_bytes >= 0x80000000ull || out_bytes >= 0x80000000ull) {
-        set_error("dz_spconv_forward_x_limb3: input of %zu / output of %zu bytes exceeds the 2 GiB buffer-addressing limit", in_bytes, out_bytes);
-        return DZ_ERR_UNSUPPORTED;
-    }
-    if (cap_out == 0) return DZ_OK;
-    SpConvXTArgs a{in, nbr_packed, windows, d_m_out, w, scale, shift, residual, out, perm, cin, cout, cap_out, relu,
-                   (unsigned int)in_bytes, (unsigned int)((size_t)27 * cout * cin * 6)};
-    if constexpr (XT_SHIP_32) { if (cout == 32) return launch_xt<XT32>(a, stream); }
-    if constexpr (XT_SHIP_64) { if (cout == 64) return launch_xt<XT64>(a, stream); }
-    if constexpr (XT_SHIP_128) { if (cout == 128) return launch_xt<XT128>(a, stream); }
-    return DZ_ERR_UNSUPPORTED;          // (not reached: xt_tile_rows refused the width above)
+                              int relu, float *out, int cout, void *stream) {
+    return xw_forward("dz_spconv_forward_x_limb3", xw_select(kXT, cin, cout), (size_t)27 * cout * cin * 6, in, in_rows, cin, nbr_packed, perm,
+                      windows, tile_rows, cap_out, d_m_out, w, scale, shift, residual, relu, out, cout, stream);
 }
 
 }  // extern "C"

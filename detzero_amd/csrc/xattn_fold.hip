@@ -33,11 +33,6 @@ constexpr int XF_TILE = XF_KB * XF_ROWB;                // one 16-key block
 constexpr int XF_OFF_Q = 0, XF_OFF_T = XF_ROWS * XF_ROWB, XF_LDS = XF_OFF_T + XF_WAVES * 2 * XF_TILE;
 static_assert(XF_LDS <= 160 * 1024, "LDS");
 
-__device__ __forceinline__ void xf_load16_lds(unsigned int lds_base, unsigned int voff, srsrc_t rsrc, unsigned int soff) {
-    const unsigned int b = __builtin_amdgcn_readfirstlane(lds_base), so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(b), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
-}
-
 // Qf[b][h * lq + qi][c] = scale * sum_d q[b][qi][h * hd + d] * Wk[h * hd + d][c]; rows >= heads * lq are zero.  Grid (heads + 1, B):
 // one workgroup per (object, head) - the head's hd rows of Wk are read once per workgroup, coalesced - and one for the padding rows
 __global__ __launch_bounds__(XF_THREADS) void k_fold_queries(const float *__restrict__ q, const float *__restrict__ wk_oi, int lq, int heads,
@@ -92,7 +87,7 @@ __global__ __launch_bounds__(XF_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
 #pragma unroll
         for (int i = 0; i < XF_KB; ++i) {
             const int key = min(blk * XF_KB + i, lk - 1);
-            xf_load16_lds(tbase + buf * XF_TILE + i * XF_ROWB, (unsigned int)((lane ^ i) << 4), rsrc, (unsigned int)key * XF_ROWB);
+            load16_lds(tbase + buf * XF_TILE + i * XF_ROWB, (unsigned int)((lane ^ i) << 4), rsrc, (unsigned int)key * XF_ROWB);
         }
     };
 
