@@ -42,6 +42,13 @@ static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int tile_masks_words(int cap) { return (cap / 32 + 1 + 3) & ~3; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Explicit-origin entry of a pixel-tile list (dz_bev_tile_cover; read by k_conv3x3_h and k_bev_fill_spans): bit 31 set, frame b in bits
+// 21..30, 8-row band ty in bits 12..20, pixel column x in bits 0..11.  A grid tile id is never negative, so an entry says itself which
+// form it has.
+constexpr int TILE_XY_MAX_B = 1 << 10, TILE_XY_MAX_TY = 1 << 9, TILE_XY_MAX_X = 1 << 12;
+__host__ __device__ static inline int tile_xy_pack(int b, int ty, int x) { return (int)(0x80000000u | ((unsigned)b << 21) | ((unsigned)ty << 12) | (unsigned)x); }
+__host__ __device__ static inline void tile_xy_unpack(int e, int &b, int &ty, int &x) { x = e & 0xFFF; ty = (e >> 12) & 0x1FF; b = (e >> 21) & 0x3FF; }
+
 // persistent-grid size for memory-bound grid-stride kernels: enough blocks to fill 256 CUs x 8
 static inline int stream_grid(long work_items, int block) {
     long g = (work_items + block - 1) / block;

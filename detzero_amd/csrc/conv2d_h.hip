@@ -275,7 +275,7 @@ static ConvHChoice conv_h_select(const dz_conv2d_desc &p, int out_f32) {
     if (p.in_rowidx && (!bc3 || out_f32))
         return {CH_NONE, "dz_conv2d_forward_split: in_rowidx (sparse input) is implemented for 3 x 3 stride-1 layers with 128-channel output tiles, "
                          "two z slabs (cin == 2 * in_row_channels) and pair16 output"};
-    // in_tiles lists 8 x 32-pixel tiles (dz_bev_tile_list): only the 64 / 128-channel variants of k_conv3x3_h walk that grid.  The
+    // in_tiles lists 8 x 32-pixel tiles (dz_bev_tile_cover): only the 64 / 128-channel variants of k_conv3x3_h walk that grid.  The
     // 32-channel variant has 16 x 32 tiles - a list there would be decoded on the wrong grid (wrong pixels): refused.  A layer
     // that no tile variant takes (small images, strided layers) runs on the generic kernel, which computes EVERY pixel: the list is
     // ignored there (results stay correct; the caller's fill of the skipped tiles rewrites what was computed).

@@ -78,8 +78,8 @@ __global__ __launch_bounds__(C3_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     // this launch covers the (group, channel tile) pairs pair0 .. pair0 + ny - 1 of the layer's ntn * groups (all of them unless their
     // number does not divide the 32 workgroups of an XCD: launch_c3)
     const int ntn = p.cout_pad / BC, nty = ny;                  // channel tiles per group; pairs of this launch
-    // pixel tiles: all of them, or - with a tile list (dz_bev_tile_list) - the tiles to run; the others' result (the layer's zero-input
-    // response) is written by dz_bev_fill_empty_tiles
+    // pixel tiles: all of them, or - with a tile list (dz_bev_tile_cover) - the tiles to run; the other pixels' result (the layer's zero-input
+    // response) is written by dz_bev_fill_spans
     const int *const tlist = p.in_tiles;
     const int npx = tlist ? tlist[0] : p.batch * tiles_x * tiles_y;
     const int xcd = blockIdx.x & 7, jloc = blockIdx.x >> 3, nj = gridDim.x >> 3;      // gridDim.x is a multiple of 8
@@ -104,7 +104,15 @@ __global__ __launch_bounds__(C3_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(id) : "s"(ptr) : "memory");
         return id;
     };
-    auto tile_origin = [&](int t, int &ox, int &oy, int &ob) {          // t = a tile ID
+    auto tile_origin = [&](int t, int &ox, int &oy, int &ob) {          // t = a tile ID, or a list entry with its own origin
+        if (tlist && t < 0) {
+            // explicit origin (dz_bev_tile_cover): the tile starts at ANY pixel column of its 8-row band.  Nothing else changes - the
+            // `cols` mask of the input pieces and the x < wo test of the stores cut a tile that reaches past the right edge
+            int ty;
+            tile_xy_unpack(t, ob, ty, ox);
+            oy = ty * C3_TH;
+            return;
+        }
         ox = (t % tiles_x) * C3_TW;
         oy = ((t / tiles_x) % tiles_y) * C3_TH;
         ob = t / (tiles_x * tiles_y);

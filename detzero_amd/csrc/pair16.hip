@@ -145,114 +145,189 @@ __global__ __launch_bounds__(256) void k_bev_row_index(const uint32_t *__restric
     }
 }
 
-// ---- pixel tiles of the sparse-input convolution (8 x 32 output pixels, conv3x3_h.hip) whose 10 x 34 input halo holds no row at all:
-// the convolution of such a tile is ReLU(shift) in every pixel.  k_bev_tile_flags marks them (one wavefront per tile), k_bev_tile_compact
-// writes list[0] = n occupied, list[1] = n empty, then the occupied tile ids in ascending order, then the empty ones; the convolution
-// walks only the occupied ones, k_bev_fill_tiles writes the constant into the empty ones - the same bits the kernel would have produced
-// (acc = 0 -> fmaf(0, scale, shift) = shift -> ReLU -> the (hi, lo) split).
-// Chebyshev distance (capped at DCAP) of every pixel to the nearest pixel that holds a row; outside the image there are none.
-// D >= l + 1 on all pixels of a tile <=> the tile's input halo at dense layer l (1 = the sparse-input layer) lies in the region where the
-// network's activations are its ZERO-INPUT RESPONSE: the tile's result is a copy of that response (dz_bev_fill_empty_tiles).
-constexpr int BEV_DCAP = 8;
-__global__ __launch_bounds__(256) void k_bev_tile_mind(const int2 *__restrict__ idx, int batch, int hp, int wp, int ho, int wo, int tiles_y, int tiles_x,
-                                                       unsigned char *__restrict__ mind) {
-    // one workgroup per tile: occupancy of the tile's pixels + BEV_DCAP pixels around them into LDS, then each of the 256 threads
-    // grows a square around its pixel
-    constexpr int R = BEV_DCAP - 1, SH = 8 + 2 * R, SW = 32 + 2 * R;
-    __shared__ unsigned char occ[SH][SW + 2];
-    __shared__ int tile_min;
-    const int t = blockIdx.x;
-    const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-    const int y0 = ty * 8 - R, x0 = tx * 32 - R;             // image coordinates (unpadded) of the LDS window's origin
-    if (threadIdx.x == 0) tile_min = BEV_DCAP;
-    for (int k = threadIdx.x; k < SH * SW; k += 256) {
-        const int ry = k / SW, rx = k - ry * SW;
-        const int y = y0 + ry, x = x0 + rx;
-        unsigned char o = 0;
-        if ((unsigned)y < (unsigned)ho && (unsigned)x < (unsigned)wo) {
-            const int2 v = idx[((size_t)b * hp + y + 1) * wp + x + 1];
-            o = (v.x >= 0 || v.y >= 0) ? 1 : 0;
+// ---- pixel tiles (8 x 32 output pixels, conv3x3_h.hip) of the first BEV block whose result is the network's ZERO-INPUT RESPONSE.
+// With D = the Chebyshev distance of a pixel to the nearest pixel that holds a row (outside the image there are none), the block's 3 x 3
+// stride-1 layer number l (1 = the sparse-input layer) sees around a pixel with D >= l + 1 exactly what it sees on an all-zero input, and
+// produces what it produces there: ReLU(shift) at layer 1 (acc = 0 -> fmaf(0, scale, shift) -> ReLU -> the (hi, lo) split), the layer's
+// zero-response image behind it.  Per 8-row band [y0, y0 + 8) and layer l, column x is BUSY if some occupied pixel lies in rows
+// [y0 - l, y0 + 7 + l] and columns [x - l, x + l] - one of the column's pixels has D <= l.  The launch of layer l has to cover the busy
+// columns; every other pixel is a copy (k_bev_fill_spans).
+//   cover list: sweep x from 0, put a tile [x, x + 32) at the first busy column not yet covered, go on at x + 32 - for one band the fewest
+//               tiles that cover its busy columns; entries carry their own origin (tile_xy_pack), spans = the complement per band;
+//   grid list:  the tiles of the fixed 32-column grid that hold a busy column (tile id = (b * tiles_y + ty) * tiles_x + tx).
+constexpr int BEV_DCAP = 8;             // layers 1 .. BEV_DCAP - 2 (a column's distance to the band is capped at BEV_DCAP - 1)
+constexpr int BEV_MAX_W = 1024;         // columns of a band the planner takes (its grid mask is one 32-bit word)
+// words of one (band, layer) slot of the planner's workspace: n tiles, n spans, grid mask, tile columns, spans (xs | xe << 16)
+static inline __host__ __device__ int bev_slot_words(int tiles_x) { return 3 + tiles_x + tiles_x + 1; }
+
+// one workgroup per (frame, band): vertical distance of every column to the band in ONE pass over the band's window, then per layer the
+// busy mask (ballots) and a sweep of at most tiles_x steps by one thread
+__global__ __launch_bounds__(256) void k_bev_cover_plan(const int2 *__restrict__ idx, int hp, int wp, int ho, int wo, int tiles_y, int tiles_x, int nl,
+                                                        int *__restrict__ slots) {
+    __shared__ unsigned char vd[BEV_MAX_W];
+    __shared__ unsigned long long busy[BEV_DCAP - 2][BEV_MAX_W / 64];
+    const int tid = threadIdx.x, ty = blockIdx.x % tiles_y, b = blockIdx.x / tiles_y, y0 = ty * 8;
+    for (int k = tid; k < (BEV_DCAP - 2) * (BEV_MAX_W / 64); k += 256) (&busy[0][0])[k] = 0ull;
+    for (int x = tid; x < wo; x += 256) {
+        int v = BEV_DCAP - 1;
+        for (int r = -nl; r < 8 + nl; ++r) {
+            const int y = y0 + r;
+            if ((unsigned)y >= (unsigned)ho) continue;
+            const int2 e = idx[((size_t)b * hp + y + 1) * wp + x + 1];
+            if (e.x >= 0 || e.y >= 0) v = min(v, r < 0 ? -r : r > 7 ? r - 7 : 0);
         }
-        occ[ry][rx] = o;
+        vd[x] = (unsigned char)v;
     }
     __syncthreads();
-    const int py = threadIdx.x >> 5, px = threadIdx.x & 31;
-    int d = BEV_DCAP;
-    if (ty * 8 + py < ho && tx * 32 + px < wo) {
-        const int cy = py + R, cx = px + R;
-        if (occ[cy][cx]) d = 0;
-        else {
-            for (int r = 1; r <= R && d == BEV_DCAP; ++r) {
-                bool hit = false;
-                for (int k = -r; k <= r; ++k)
-                    hit |= occ[cy - r][cx + k] | occ[cy + r][cx + k] | occ[cy + k][cx - r] | occ[cy + k][cx + r];
-                if (hit) d = r;
+    const int wo64 = (wo + 63) & ~63;
+    for (int l = 1; l <= nl; ++l)
+        for (int x = tid; x < wo64; x += 256) {             // (whole wavefronts: wo64 is a multiple of 64)
+            bool bz = false;
+            if (x < wo)
+                for (int k = max(0, x - l); k <= min(wo - 1, x + l); ++k) bz |= vd[k] <= l;
+            const unsigned long long m = __ballot(bz);
+            if ((tid & 63) == 0) busy[l - 1][x >> 6] = m;
+        }
+    __syncthreads();
+    if (tid >= nl) return;
+    const unsigned long long *const bm = busy[tid];
+    int *const s = slots + ((size_t)blockIdx.x * nl + tid) * bev_slot_words(tiles_x);
+    const int nw = wo64 >> 6;
+    int n = 0, ns = 0, pos = 0;
+    for (;;) {                                              // pos < wo
+        int w = pos >> 6, x = wo;
+        unsigned long long m = bm[w] & (~0ull << (pos & 63));
+        while (!m && ++w < nw) m = bm[w];
+        if (m) x = w * 64 + __ffsll(m) - 1;                 // first busy column at or behind pos
+        if (x > pos) s[3 + tiles_x + ns++] = pos | (x << 16);
+        if (x >= wo) break;
+        s[3 + n++] = x;
+        pos = x + 32;
+        if (pos >= wo) break;
+    }
+    unsigned int gm = 0u;
+    for (int tx = 0; tx < tiles_x; ++tx) gm |= (unsigned int)(bm[tx >> 1] >> (32 * (tx & 1))) ? 1u << tx : 0u;
+    s[0] = n;
+    s[1] = ns;
+    s[2] = (int)gm;
+}
+
+// slots -> lists: one wavefront per (64 bands, layer).  It sums the counts of the bands before its own (a few hundred words), scans its own
+// 64 and writes their entries: order ascending in (b, ty, x), as the slots are.  List l at lists + (l - 1) * stride:
+// [grid: n run, n skippable, ids to run, skippable ids][cover at + 2 + n_bands * tiles_x: n run, n spans, tile entries, spans (2 words each)]
+__global__ __launch_bounds__(64) void k_bev_cover_compact(const int *__restrict__ slots, int n_bands, int tiles_y, int tiles_x, int nl, int *__restrict__ lists,
+                                                          int stride) {
+    const int lane = threadIdx.x, l = blockIdx.y, first = blockIdx.x * 64, sw = bev_slot_words(tiles_x);
+    auto slot = [&](int i) { return slots + ((size_t)i * nl + l) * sw; };
+    int before[3] = {0, 0, 0}, total[3] = {0, 0, 0};        // tiles, spans, grid tiles to run
+    for (int i = lane; i < n_bands; i += 64) {
+        const int *s = slot(i);
+        const int c[3] = {s[0], s[1], (int)__popc((unsigned int)s[2])};
+        for (int k = 0; k < 3; ++k) { total[k] += c[k]; if (i < first) before[k] += c[k]; }
+    }
+    for (int k = 0; k < 3; ++k)
+        for (int d = 32; d >= 1; d >>= 1) { total[k] += __shfl_xor(total[k], d); before[k] += __shfl_xor(before[k], d); }
+    const int me = first + lane;
+    const bool live = me < n_bands;
+    const int *const s = slot(live ? me : 0);
+    const int n = live ? s[0] : 0, ns = live ? s[1] : 0;
+    const unsigned int gm = live ? (unsigned int)s[2] : 0u;
+    int pre[3] = {n, ns, (int)__popc(gm)};
+    for (int k = 0; k < 3; ++k) {
+        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(pre[k], d); if (lane >= d) pre[k] += t; }
+        pre[k] += before[k];                                 // inclusive over all bands up to mine
+    }
+    int *const grid = lists + (size_t)l * stride, *const cover = grid + 2 + n_bands * tiles_x;
+    if (blockIdx.x == 0 && lane == 0) {
+        grid[0] = total[2];
+        grid[1] = n_bands * tiles_x - total[2];
+        cover[0] = total[0];
+        cover[1] = total[1];
+    }
+    if (!live) return;
+    const int b = me / tiles_y, ty = me % tiles_y;
+    int *o = cover + 2 + pre[0] - n;
+    for (int k = 0; k < n; ++k) o[k] = tile_xy_pack(b, ty, s[3 + k]);
+    o = cover + 2 + total[0] + 2 * (pre[1] - ns);
+    for (int k = 0; k < ns; ++k) {
+        const int sp = s[3 + tiles_x + k];
+        o[2 * k] = tile_xy_pack(b, ty, sp & 0xFFFF);
+        o[2 * k + 1] = sp >> 16;
+    }
+    int run = pre[2] - (int)__popc(gm);                          // grid tiles to run before tile (me, tx)
+    for (int tx = 0; tx < tiles_x; ++tx) {
+        const int id = me * tiles_x + tx;
+        if ((gm >> tx) & 1u) grid[2 + run++] = id;
+        else grid[2 + total[2] + id - run] = id;
+    }
+}
+
+// The pixels a list's launch leaves out get the layer's zero-input response.  The entries behind the list's tiles to run: spans of a
+// cover list ([xs, xe) of a band, two words) or skippable tiles of a grid list (ids).  A fixed grid of wavefronts (a multiple of 8
+// workgroups) walks (entry, row): one row of a span is one contiguous run of 16-byte pieces in the image and in the response; every lane
+// has FILL_DEPTH loads in flight before its first store.
+constexpr int FILL_DEPTH = 8;
+template <class M>
+__global__ __launch_bounds__(256) void k_bev_fill_spans(const int *__restrict__ list, int batch, int tiles_y, int tiles_x, int ho, int wo,
+                                                        const float *__restrict__ shift, int relu, int cout, float *__restrict__ out, int out_hp, int out_wp,
+                                                        int out_cstride, int out_coff, const float *__restrict__ zero_resp) {
+    const int n_run = list[0], n_fill = min(list[1], batch * tiles_y * (tiles_x + 1));
+    if (n_fill <= 0) return;
+    const int *const ent = list + 2 + n_run;
+    const bool xy = ent[0] < 0;
+    const int lane = threadIdx.x & 63;
+    // workgroup j runs on XCD j % 8 (own L2 each): XCD k copies row k of every band, so it reads one eighth of the response image
+    // (2.3 MB at 188 x 188 x 128) - after the first frame from its L2 - instead of all of it once per frame
+    const int y8 = blockIdx.x & 7;
+    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x >> 3) * 4 + (threadIdx.x >> 6))), nwaves = (gridDim.x >> 3) * 4;
+    const int ppp = cout / 4;                                // 16-byte pieces of a pixel: (hi, lo) of each group of 8 channels
+    // a unit = 64 columns of a span's row (16 wavefront rounds at 128 channels): full-width spans of the empty bands would otherwise
+    // keep single wavefronts busy long after the others have finished
+    const int nseg = (wo + 63) / 64;
+    for (int u = wave; u < n_fill * nseg; u += nwaves) {
+        const int i = u / nseg, seg = u - i * nseg;
+        int b, ty, xs, xe;
+        if (xy) {
+            tile_xy_unpack(ent[2 * i], b, ty, xs);
+            xe = ent[2 * i + 1];
+        } else {
+            const int t = ent[i];
+            xs = (t % tiles_x) * 32, xe = min(xs + 32, wo), ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
+        }
+        const int y = ty * 8 + y8;
+        if ((unsigned)b >= (unsigned)batch || y >= ho || xs < 0 || xe > wo) continue;
+        xs += seg * 64;
+        if (xs >= xe) continue;
+        xe = min(xe, xs + 64);
+        const int np = (xe - xs) * ppp;
+        float *const drow = out + (((size_t)b * out_hp + y + 1) * out_wp + xs + 1) * out_cstride + out_coff;
+        const uint4 *const srow = zero_resp ? reinterpret_cast<const uint4 *>(zero_resp + ((size_t)(y + 1) * out_wp + xs + 1) * cout) : nullptr;
+        for (int p0 = lane; p0 < np; p0 += 64 * FILL_DEPTH) {
+            uint4 v[FILL_DEPTH];
+#pragma unroll
+            for (int k = 0; k < FILL_DEPTH; ++k) {
+                const int p = p0 + 64 * k;
+                if (p >= np) continue;
+                if (srow) { v[k] = srow[p]; continue; }
+                const int g = (p % ppp) >> 1;                // the constant ReLU(shift): hi or lo words of channel group g
+                float v0[4], v1[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float a = shift ? shift[g * 8 + e] : 0.f, bb = shift ? shift[g * 8 + 4 + e] : 0.f;
+                    v0[e] = relu ? fmaxf(a, 0.f) : a;
+                    v1[e] = relu ? fmaxf(bb, 0.f) : bb;
+                }
+                uint2 h0, l0, h1, l1;
+                split4<M>(v0, h0, l0);
+                split4<M>(v1, h1, l1);
+                v[k] = (p & 1) ? make_uint4(l0.x, l0.y, l1.x, l1.y) : make_uint4(h0.x, h0.y, h1.x, h1.y);
+            }
+#pragma unroll
+            for (int k = 0; k < FILL_DEPTH; ++k) {
+                const int p = p0 + 64 * k;
+                if (p < np) *reinterpret_cast<uint4 *>(drow + (size_t)(p / ppp) * out_cstride + (p % ppp) * 4) = v[k];
             }
         }
-    }
-    atomicMin(&tile_min, d);
-    __syncthreads();
-    if (threadIdx.x == 0) mind[t] = (unsigned char)tile_min;
-}
-
-// list l (blockIdx.x = l - 1, l = 1 .. nlists): [n occupied, n skippable, ids of the tiles with min D < l + 1 ascending, the others], stride `stride` ints
-__global__ __launch_bounds__(1024) void k_bev_tile_compact(const unsigned char *__restrict__ mind, int n, int *__restrict__ lists, int stride) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x, need = (int)blockIdx.x + 2;
-    int *const list = lists + (size_t)blockIdx.x * stride;
-    const int per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
-    int c = 0;
-    for (int i = lo; i < hi; ++i) c += mind[i] < need;
-    part[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                      // inclusive scan of the per-thread counts
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    const int total = part[1023];
-    int occ = part[tid] - c, emp = lo - occ;                 // occupied / skippable tiles before my range
-    for (int i = lo; i < hi; ++i) {
-        if (mind[i] < need) list[2 + occ++] = i;
-        else list[2 + total + emp++] = i;
-    }
-    if (tid == 0) { list[0] = total; list[1] = n - total; }
-}
-
-template <class M>
-__global__ __launch_bounds__(256) void k_bev_fill_tiles(const int *__restrict__ list, int tiles_y, int tiles_x, int ho, int wo, const float *__restrict__ shift,
-                                                        int relu, int cout, float *__restrict__ out, int out_hp, int out_wp, int out_cstride, int out_coff,
-                                                        const float *__restrict__ zero_resp) {
-    const int n_occ = list[0], n_emp = list[1];
-    if ((int)blockIdx.x >= n_emp) return;
-    const int t = list[2 + n_occ + blockIdx.x];
-    const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
-    const int groups = cout / 8;
-    for (int k = threadIdx.x; k < 8 * 32 * groups; k += 256) {
-        const int g = k % groups, px = k / groups, r = px / 32, c = px % 32;
-        const int y = ty * 8 + r, x = tx * 32 + c;
-        if (y >= ho || x >= wo) continue;
-        uint4 *dst = reinterpret_cast<uint4 *>(out + (((size_t)b * out_hp + y + 1) * out_wp + x + 1) * out_cstride + out_coff + g * 8);
-        if (zero_resp) {
-            // the layer's response to an all-zero input at this pixel: a (1, out_hp, out_wp, cout) pair16 image computed once per model
-            const uint4 *src = reinterpret_cast<const uint4 *>(zero_resp + (((size_t)(y + 1)) * out_wp + x + 1) * cout + g * 8);
-            dst[0] = src[0];
-            dst[1] = src[1];
-            continue;
-        }
-        float v0[4], v1[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float a = shift ? shift[g * 8 + e] : 0.f, bb = shift ? shift[g * 8 + 4 + e] : 0.f;
-            v0[e] = relu ? fmaxf(a, 0.f) : a;
-            v1[e] = relu ? fmaxf(bb, 0.f) : bb;
-        }
-        uint2 h0, l0, h1, l1;
-        split4<M>(v0, h0, l0);
-        split4<M>(v1, h1, l1);
-        dst[0] = make_uint4(h0.x, h0.y, h1.x, h1.y);
-        dst[1] = make_uint4(l0.x, l0.y, l1.x, l1.y);
     }
 }
 
@@ -262,32 +337,43 @@ using namespace dz;
 
 extern "C" {
 
-size_t dz_bev_tile_list_words(int batch, int ho, int wo) { return (size_t)batch * ceil_div(ho, 8) * ceil_div(wo, 32) + 2; }
+static inline int bev_bands(int batch, int ho) { return batch * ceil_div(ho, 8); }
+size_t dz_bev_tile_cover_offset(int batch, int ho, int wo) { return (size_t)bev_bands(batch, ho) * ceil_div(wo, 32) + 2; }
+size_t dz_bev_tile_cover_words(int batch, int ho, int wo) {
+    const size_t n = bev_bands(batch, ho), tx = ceil_div(wo, 32);
+    return dz_bev_tile_cover_offset(batch, ho, wo) + 2 + n * tx + 2 * n * (tx + 1);
+}
+size_t dz_bev_tile_cover_ws_words(int batch, int ho, int wo, int nlists) { return (size_t)bev_bands(batch, ho) * nlists * bev_slot_words(ceil_div(wo, 32)); }
 
-int dz_bev_tile_list(const int *idx, int batch, int hp, int wp, int ho, int wo, int nlists, int *lists, unsigned char *mind_ws, void *stream_) {
+int dz_bev_tile_cover(const int *idx, int batch, int hp, int wp, int ho, int wo, int nlists, int *lists, int *ws, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    DZ_CHECK_ARG(idx && lists && mind_ws && batch > 0 && ho > 0 && wo > 0 && hp >= ho + 2 && wp >= wo + 2 && nlists >= 1 && nlists < BEV_DCAP,
-                 "dz_bev_tile_list: bad argument (1 <= nlists <= %d)", BEV_DCAP - 1);
-    const int ty = ceil_div(ho, 8), tx = ceil_div(wo, 32), n = batch * ty * tx;
-    hipLaunchKernelGGL(k_bev_tile_mind, dim3(n), dim3(256), 0, stream, reinterpret_cast<const int2 *>(idx), batch, hp, wp, ho, wo, ty, tx, mind_ws);
-    hipLaunchKernelGGL(k_bev_tile_compact, dim3(nlists), dim3(1024), 0, stream, mind_ws, n, lists, (int)dz_bev_tile_list_words(batch, ho, wo));
+    DZ_CHECK_ARG(idx && lists && ws && batch > 0 && ho > 0 && wo > 0 && hp >= ho + 2 && wp >= wo + 2 && nlists >= 1 && nlists <= BEV_DCAP - 2,
+                 "dz_bev_tile_cover: bad argument (1 <= nlists <= %d)", BEV_DCAP - 2);
+    const int ty = ceil_div(ho, 8), tx = ceil_div(wo, 32), n = batch * ty;
+    DZ_CHECK_ARG(wo <= BEV_MAX_W && wo <= TILE_XY_MAX_X && ty <= TILE_XY_MAX_TY && batch <= TILE_XY_MAX_B,
+                 "dz_bev_tile_cover: %d frames of %d x %d pixels exceed the list entry (%d frames, %d rows, %d columns)", batch, ho, wo, TILE_XY_MAX_B,
+                 TILE_XY_MAX_TY * 8, BEV_MAX_W);
+    hipLaunchKernelGGL(k_bev_cover_plan, dim3(n), dim3(256), 0, stream, reinterpret_cast<const int2 *>(idx), hp, wp, ho, wo, ty, tx, nlists, ws);
+    hipLaunchKernelGGL(k_bev_cover_compact, dim3(ceil_div(n, 64), nlists), dim3(64), 0, stream, ws, n, ty, tx, nlists, lists,
+                       (int)dz_bev_tile_cover_words(batch, ho, wo));
     DZ_LAUNCH_CHECK();
     return DZ_OK;
 }
 
-int dz_bev_fill_empty_tiles(const int *list, int batch, int ho, int wo, const float *shift, int relu, int cout, float *out, int out_hp, int out_wp,
-                            int out_cstride, int out_coff, const float *zero_resp, int math, void *stream_) {
+int dz_bev_fill_spans(const int *list, int batch, int ho, int wo, const float *shift, int relu, int cout, float *out, int out_hp, int out_wp,
+                      int out_cstride, int out_coff, const float *zero_resp, int math, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DZ_CHECK_ARG(list && out && batch > 0 && ho > 0 && wo > 0 && cout > 0 && cout % 8 == 0 && out_cstride % 8 == 0 && out_coff % 8 == 0 &&
-                 out_hp >= ho + 2 && out_wp >= wo + 2, "dz_bev_fill_empty_tiles: bad argument");
-    DZ_CHECK_ARG(math == DZ_MATH_F16X2 || math == DZ_MATH_BF16X2 || math == DZ_MATH_F16, "dz_bev_fill_empty_tiles: math %d is not a split mode", math);
-    const int ty = ceil_div(ho, 8), tx = ceil_div(wo, 32), n = batch * ty * tx;
+                 out_hp >= ho + 2 && out_wp >= wo + 2, "dz_bev_fill_spans: bad argument");
+    DZ_CHECK_ARG(math == DZ_MATH_F16X2 || math == DZ_MATH_BF16X2 || math == DZ_MATH_F16, "dz_bev_fill_spans: math %d is not a split mode", math);
+    const int ty = ceil_div(ho, 8), tx = ceil_div(wo, 32);
+    const dim3 grid((4 * device_cus() + 7) / 8 * 8);        // the fill is a copy: four workgroups per CU, whatever the list holds
     if (math == DZ_MATH_BF16X2)
-        hipLaunchKernelGGL(k_bev_fill_tiles<MathBF16>, dim3(n), dim3(256), 0, stream, list, ty, tx, ho, wo, shift, relu, cout, out, out_hp, out_wp, out_cstride,
-                           out_coff, zero_resp);
+        hipLaunchKernelGGL(k_bev_fill_spans<MathBF16>, grid, dim3(256), 0, stream, list, batch, ty, tx, ho, wo, shift, relu, cout, out, out_hp, out_wp,
+                           out_cstride, out_coff, zero_resp);
     else
-        hipLaunchKernelGGL(k_bev_fill_tiles<MathF16>, dim3(n), dim3(256), 0, stream, list, ty, tx, ho, wo, shift, relu, cout, out, out_hp, out_wp, out_cstride,
-                           out_coff, zero_resp);
+        hipLaunchKernelGGL(k_bev_fill_spans<MathF16>, grid, dim3(256), 0, stream, list, batch, ty, tx, ho, wo, shift, relu, cout, out, out_hp, out_wp,
+                           out_cstride, out_coff, zero_resp);
     DZ_LAUNCH_CHECK();
     return DZ_OK;
 }

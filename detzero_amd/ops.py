@@ -569,23 +569,32 @@ def bev_row_index(level, feat_rows, pad=1):
 
 
 def bev_tile_list(ridx, ho, wo, nlists=1):
-    """(nlists, words) int32: list l - 1 = [n to run, n skippable, tiles to run ascending, skippable ones] for the l-th 3 x 3 layer of the
-    first BEV block over a row-index image (dz_bev_tile_list: 8 x 32 pixel tiles whose pixels are all at least l + 1 pixels away from any row)."""
+    """(nlists, words) int32 over a row-index image: row l - 1 holds the two pixel-tile lists of the l-th 3 x 3 layer of the first BEV block
+    (dz_bev_tile_cover), each [n to run, n to fill, entries to run, entries to fill].  From word 0 the fixed-grid list: ids of the 8 x 32
+    tiles with a pixel less than l + 1 pixels away from any row, ascending, then the skippable ones; from word bev_tile_cover_offset the
+    free-offset cover of the same pixels (`bev_tile_cover`) - what the detector launches."""
     lib = L.load()
     b, hp, wp, _ = ridx.shape
-    n = lib.dz_bev_tile_list_words(b, int(ho), int(wo))
+    n = lib.dz_bev_tile_cover_words(b, int(ho), int(wo))
     lst = torch.empty((int(nlists), n), dtype=torch.int32, device=ridx.device)
-    ws = torch.empty((n,), dtype=torch.uint8, device=ridx.device)
-    L.check(lib.dz_bev_tile_list(L.ptr(ridx), b, hp, wp, int(ho), int(wo), int(nlists), L.ptr(lst), L.ptr(ws), L.stream()), 'dz_bev_tile_list')
+    ws = torch.empty((lib.dz_bev_tile_cover_ws_words(b, int(ho), int(wo), int(nlists)),), dtype=torch.int32, device=ridx.device)
+    L.check(lib.dz_bev_tile_cover(L.ptr(ridx), b, hp, wp, int(ho), int(wo), int(nlists), L.ptr(lst), L.ptr(ws), L.stream()), 'dz_bev_tile_cover')
     return lst
 
 
+def bev_tile_cover(lists, batch, ho, wo):
+    """The cover lists of `bev_tile_list`'s rows (a view): [n tiles, n spans, tile entries (bit 31 | b << 21 | ty << 12 | x0), spans (entry of
+    (b, ty, xs), xe)].  Tiles start at any pixel column of their 8-row band; spans are the columns of a band outside its tiles."""
+    return lists[:, L.load().dz_bev_tile_cover_offset(int(batch), int(ho), int(wo)):]
+
+
 def bev_fill_empty_tiles(tiles, batch, ho, wo, shift, relu, cout, out, math, zero_resp=None):
-    """The skippable pixel tiles of list `tiles` in the zero-bordered pair16 image `out` (B, ho + 2, wo + 2, C) get the layer's zero-input
-    response: the (1, ho + 2, wo + 2, C) image `zero_resp`, or - None: the first layer - the constant ReLU(shift)."""
+    """The pixels that list `tiles` (either list of a `bev_tile_list` row) leaves out of its launch get the layer's zero-input response in the
+    zero-bordered pair16 image `out` (B, ho + 2, wo + 2, C): the (1, ho + 2, wo + 2, C) image `zero_resp`, or - None: the first layer - the
+    constant ReLU(shift)."""
     lib = L.load()
-    L.check(lib.dz_bev_fill_empty_tiles(L.ptr(tiles), int(batch), int(ho), int(wo), L.ptr(shift), 1 if relu else 0, int(cout), L.ptr(out), out.shape[1],
-                                        out.shape[2], out.shape[3], 0, L.ptr(zero_resp), int(math), L.stream()), 'dz_bev_fill_empty_tiles')
+    L.check(lib.dz_bev_fill_spans(L.ptr(tiles), int(batch), int(ho), int(wo), L.ptr(shift), 1 if relu else 0, int(cout), L.ptr(out), out.shape[1],
+                                  out.shape[2], out.shape[3], 0, L.ptr(zero_resp), int(math), L.stream()), 'dz_bev_fill_spans')
 
 
 BEV_DENSE = not os.environ.get('DZ_BEV_SCATTER')   # development switch: False = zero-fill + scatter (dz_sparse_to_bev_split) for two-slab levels too
@@ -858,8 +867,8 @@ def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None, f32_engine=None):
     if tiles is not None:
         # zero-response tiles are not run: count the EXECUTED share of the layer (one host sync; profiling passes only), so that the
         # roofline figures of the kernel describe the kernel, not the work it was spared
-        n_run, n_skip = (int(v) for v in tiles[:2].tolist())
-        share = n_run / float(max(n_run + n_skip, 1))
+        # (a cover list counts spans behind its tiles, not tiles: the share is of the layer's 8 x 32 grid)
+        share = int(tiles[0]) / float(max(d.batch * (-(-d.ho // 8)) * (-(-d.wo // 32)), 1))
         flops *= share
         nbytes = 4.0 * (share * (m * d.cin + m * cout) + taps * d.cin * d.cout_pad * d.groups)
     if limb3:

@@ -209,7 +209,8 @@ typedef struct dz_conv2d_desc {
                                  in_cstride is ignored.  HeightCompression (height_compression.py:20-24) + the first block's ZeroPad2d
                                  (backbone2d.py:41-46) fused into that block's convolution */
     int in_row_channels, in_rows;
-    const int *in_tiles;      /* 3 x 3 stride-1 resident-tile layers, optional: a list of dz_bev_tile_list (8 x 32 pixel tiles) - the launch covers its tiles to run only.
+    const int *in_tiles;      /* 3 x 3 stride-1 resident-tile layers, optional: a list of dz_bev_tile_cover (8 x 32 pixel tiles; grid ids, or entries with their own origin -
+                                 an entry says which by its bit 31) - the launch covers its tiles to run only.
                                  Walked by the 64- / 128-channel tile kernels (pair16 output); IGNORED by the generic kernel (every pixel computed); refused
                                  (DZ_ERR_UNSUPPORTED) on the 32-channel tile kernel, whose tiles are 16 x 32 */
 } dz_conv2d_desc;
@@ -390,19 +391,31 @@ const char *dz_spconv_limb3_variant(int cin, int cout);
  * backbone2d.py:41-46 never touch HBM.  DZ_ERR_UNSUPPORTED for d != 2. */
 int dz_bev_row_index(const uint32_t *bitmap, const uint32_t *prefix, int batch, int d, int h, int w, int layout, int pad, int feat_rows,
                      int *idx, void *stream);
-/* Pixel tiles (8 x 32 output pixels) of the first BEV block whose result is the network's ZERO-INPUT RESPONSE (round 5).  With D = the
- * Chebyshev distance of a pixel to the nearest pixel holding a row (nothing outside the image), the 3 x 3 stride-1 layer number l of the
- * block (l = 1: the sparse-input layer) sees, in a tile whose pixels all have D >= l + 1, exactly what it sees on an all-zero input - and
- * produces what it produces there.  dz_bev_tile_list writes, for l = 1 .. nlists (< 8), list l at lists + (l - 1) * dz_bev_tile_list_words:
- * [n to run, n skippable, ids of the tiles to run ascending ..., the skippable ones ...] (tile id = (b * tiles_y + ty) * tiles_x + tx);
- * mind_ws = one byte per tile.  Pass list l as dz_conv2d_desc.in_tiles of layer l: the launch walks the tiles to run only;
- * dz_bev_fill_empty_tiles gives the others their result: zero_resp = the layer's output on an all-zero input (1, out_hp, out_wp, cout)
- * pair16, computed once per model by the same kernels - or NULL for layer 1, whose response is the constant ReLU(shift).  Bit-identical
- * to running every tile (a pixel's result depends on its 3 x 3 input neighbourhood only). */
-size_t dz_bev_tile_list_words(int batch, int ho, int wo);
-int dz_bev_tile_list(const int *idx, int batch, int hp, int wp, int ho, int wo, int nlists, int *lists, unsigned char *mind_ws, void *stream);
-int dz_bev_fill_empty_tiles(const int *list, int batch, int ho, int wo, const float *shift, int relu, int cout, float *out, int out_hp, int out_wp,
-                            int out_cstride, int out_coff, const float *zero_resp, int math, void *stream);
+/* Pixel tiles (8 x 32 output pixels) of the first BEV block whose result is the network's ZERO-INPUT RESPONSE.  With D = the Chebyshev
+ * distance of a pixel to the nearest pixel holding a row (nothing outside the image), the 3 x 3 stride-1 layer number l of the block
+ * (l = 1: the sparse-input layer) sees around a pixel with D >= l + 1 exactly what it sees on an all-zero input - and produces what it
+ * produces there.  Per 8-row band [y0, y0 + 8) column x is BUSY at layer l if an occupied pixel lies in rows [y0 - l, y0 + 7 + l] and
+ * columns [x - l, x + l]; the launch of layer l has to cover the busy columns only.
+ * dz_bev_tile_cover (idx = the row-index image of dz_bev_row_index, pad 1) writes, for l = 1 .. nlists (<= 6), at
+ * lists + (l - 1) * dz_bev_tile_cover_words two lists of the same [n to run, n to fill, entries to run ..., entries to fill ...] shape:
+ *   + 0                         the GRID list: tiles of the fixed 32-column grid holding a busy column, ids ascending
+ *                               (id = (b * tiles_y + ty) * tiles_x + tx), then the ids of the skippable ones;
+ *   + dz_bev_tile_cover_offset  the COVER list: per band, sweeping x from 0, a tile [x, x + 32) at the first busy column not yet covered -
+ *                               the fewest tiles that cover the band's busy columns, never more than the grid's.  A tile entry carries
+ *                               its origin: bit 31 | b << 21 | ty << 12 | x (ascending in (b, ty, x)); a tile may reach past wo.  To fill:
+ *                               the maximal column intervals [xs, xe) of every band outside its tiles, two words each: the entry of
+ *                               (b, ty, xs), then xe.
+ * ws = dz_bev_tile_cover_ws_words ints.  Two launches, counts stay on the device.  wo <= 1024, ho <= 4096, batch <= 1024.
+ * Pass either list as dz_conv2d_desc.in_tiles of layer l: the launch walks the tiles to run only.  dz_bev_fill_spans gives the other
+ * pixels of that list their result: zero_resp = the layer's output on an all-zero input (1, out_hp, out_wp, cout) pair16, computed once
+ * per model by the same kernels - or NULL for layer 1, whose response is the constant ReLU(shift).  Bit-identical to running every tile (a
+ * pixel's result depends on its 3 x 3 input neighbourhood only, and its accumulation order does not depend on the tile's origin). */
+size_t dz_bev_tile_cover_words(int batch, int ho, int wo);
+size_t dz_bev_tile_cover_offset(int batch, int ho, int wo);
+size_t dz_bev_tile_cover_ws_words(int batch, int ho, int wo, int nlists);
+int dz_bev_tile_cover(const int *idx, int batch, int hp, int wp, int ho, int wo, int nlists, int *lists, int *ws, void *stream);
+int dz_bev_fill_spans(const int *list, int batch, int ho, int wo, const float *shift, int relu, int cout, float *out, int out_hp, int out_wp,
+                      int out_cstride, int out_coff, const float *zero_resp, int math, void *stream);
 /* dz_sparse_to_bev on pair16 rows / images (the 16-bit halves are moved, no arithmetic) */
 int dz_sparse_to_bev_split(const float *feats, const int *coords, const int *d_m, int cap, int c, int d, int h,
                            int w, int pad, float *bev, void *stream);
