@@ -246,17 +246,22 @@ def set_sparse_engine(model, engine, f32_engine=None, f32_gather=None):
     return model
 
 
-def set_dense_engine(model, f32_engine):
+def set_dense_engine(model, f32_engine, f32_generic=None):
     """Engine of the 3 x 3 stride-1 dense layers (BEV backbone, the head's shared and hidden convolutions) in the exact-fp32 mode:
     'mfma32' (default: k_conv2d on the fp32 matrix cores) or 'bf16x3' (csrc/conv3x3_t.hip: every operand as three exact bf16 limbs,
-    six bf16 MFMAs per product - fp32-class results in another accumulation order).  Strided layers, deblocks, the grouped output layer
-    and the head-at-candidates kernel stay where they are; the split math modes ignore the switch."""
+    six bf16 MFMAs per product - fp32-class results in another accumulation order).
+    f32_generic (None = unchanged): the engine of the dense layers that kernel does not run - the strided 3 x 3 layer, the deblocks, the
+    head's grouped output layer, and with f32_engine 'mfma32' every other dense layer too: 'mfma32' (default) or 'bf16x3'
+    (csrc/conv2d_t.hip, the generic implicit GEMM in the same three-limb arithmetic).  The head-at-candidates kernel stays where it is;
+    the split math modes ignore both switches.  A refused value changes nothing."""
     if f32_engine not in ops.DENSE_F32_ENGINES:
         raise DetZeroHipError('unknown fp32 dense engine %r (%s)' % (f32_engine, ' | '.join(ops.DENSE_F32_ENGINES)))
+    if f32_generic is not None and f32_generic not in ops.DENSE_F32_GENERIC_ENGINES:
+        raise DetZeroHipError('unknown generic fp32 dense engine %r (%s)' % (f32_generic, ' | '.join(ops.DENSE_F32_GENERIC_ENGINES)))
     for name in ('backbone2d', 'dense_head'):
         mod = getattr(model, name, None)
         if mod is not None and hasattr(mod, 'set_dense_engine'):
-            mod.set_dense_engine(f32_engine)
+            mod.set_dense_engine(f32_engine, f32_generic)
     return model
 
 

@@ -131,6 +131,7 @@ class _Cached(nn.Module):
         self._prescale_stale = False        # True: weights were loaded after the exponents of act_exp were calibrated (`_e` then refuses)
         self.math = 0       # ops.MATH_MODES: 0 = fp32 MFMA, 1 = fp16-pair split, 2 = bf16-pair split, 3 = fp16 pairs with one product (csrc/hgemm.h)
         self.f32_dense_engine = 'mfma32'    # BaseBEVBackbone / CenterHead: set_dense_engine
+        self.f32_dense_generic = 'mfma32'   # ... and its f32_generic (csrc/conv2d_t.hip; no environment knob yet: DESIGN.md 2a-quater)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._weights_loaded())
 
     def invalidate(self):
@@ -219,12 +220,17 @@ class _Cached(nn.Module):
             entry[ck] = ops.pack_weight_split(entry[key], ops.storage_math(self.math))
         return entry[ck]
 
-    def set_dense_engine(self, f32_engine):
+    def set_dense_engine(self, f32_engine, f32_generic=None):
         """Engine of the 3 x 3 stride-1 dense layers in the exact-fp32 mode: 'mfma32' (k_conv2d, the default) or 'bf16x3' (three bf16
-        limbs per operand, csrc/conv3x3_t.hip).  The split modes ignore it."""
+        limbs per operand, csrc/conv3x3_t.hip).  f32_generic (None = unchanged): the engine of the dense layers that kernel does not
+        run - 'mfma32' (k_conv2d, the default) or 'bf16x3' (csrc/conv2d_t.hip).  The split modes ignore both."""
         if f32_engine not in ops.DENSE_F32_ENGINES:
             raise DetZeroHipError('unknown fp32 dense engine %r (%s)' % (f32_engine, ' | '.join(ops.DENSE_F32_ENGINES)))
+        if f32_generic is not None and f32_generic not in ops.DENSE_F32_GENERIC_ENGINES:
+            raise DetZeroHipError('unknown generic fp32 dense engine %r (%s)' % (f32_generic, ' | '.join(ops.DENSE_F32_GENERIC_ENGINES)))
         self.f32_dense_engine = f32_engine
+        if f32_generic is not None:
+            self.f32_dense_generic = f32_generic
         CACHE_GEN[0] += 1
         return self
 
@@ -238,6 +244,20 @@ class _Cached(nn.Module):
             ck = '%s_limb3' % key
             if ck not in entry:
                 entry[ck] = ops.pack_weight_limb3(entry[key])
+            return entry[ck]
+        return packed
+
+    def _l3g(self, entry, key='w'):
+        """`_l3` for the generic bf16x3 engine (set_dense_engine's f32_generic): the entry's (groups, taps, cin, cout_pad) or (taps, cin,
+        cout_pad) weights in dz_conv2d_limb3_forward's layout, packed once and cached in the plan entry; None in the split modes and with
+        the switch off."""
+        if self.math or getattr(self, 'f32_dense_generic', 'mfma32') != 'bf16x3':
+            return None
+
+        def packed():
+            ck = '%s_limb3g' % key
+            if ck not in entry:
+                entry[ck] = ops.pack_weight_limb3_generic(entry[key])
             return entry[ck]
         return packed
 
@@ -848,11 +868,12 @@ FUSED_DEBLOCK_PHASES = os.environ.get('DZ_TUNE_DEBLOCK_PHASES', '1') != '0'     
 def conv_layer(inp, in_shape, w, scale, shift, relu, out, out_shape, *, cin, in_cstride, in_coff=0, ksize=3,
                stride=1, in_off=0, out_cstride, out_coff=0, out_s=1, out_d=(0, 0), groups=1, cout_pad=None,
                g_cout=None, g_ooff=None, ho=None, wo=None, batch=1, math=0, out_f32=False, phase_groups=False, in_rowidx=None,
-               in_row_channels=0, in_rows=0, in_tiles=None, w_limb3=None):
+               in_row_channels=0, in_rows=0, in_tiles=None, w_limb3=None, w_limb3g=None):
     """One dz_conv2d_forward[_split] call.  in_shape/out_shape = (Hp, Wp) of the (padded) images.
     math != 0: w is the pack_weight_split layout (..., cout_pad, cin).
     w_limb3 (f32 mode, `_Cached._l3`): the layer runs on the bf16x3 engine with the weights that function returns wherever
-    dz_conv3x3_limb3_supported takes it, on dz_conv2d_forward otherwise."""
+    dz_conv3x3_limb3_supported takes it; else, with w_limb3g (`_Cached._l3g`), on the generic bf16x3 engine wherever
+    dz_conv2d_limb3_supported takes it; on dz_conv2d_forward otherwise."""
     if cout_pad is None:
         cout_pad = w.shape[-2] if math else w.shape[-1]
     desc = dict(
@@ -871,6 +892,10 @@ def conv_layer(inp, in_shape, w, scale, shift, relu, out, out_shape, *, cin, in_
     if w_limb3 is not None and not math and ops.conv3x3_limb3_supported(desc):
         desc['w'] = w_limb3().data_ptr()
         ops.conv2d(desc, math=math, out_f32=out_f32, tiles=in_tiles, f32_engine='bf16x3')
+        return
+    if w_limb3g is not None and not math and ops.conv2d_limb3_supported(desc):
+        desc['w'] = w_limb3g().data_ptr()
+        ops.conv2d(desc, math=math, out_f32=out_f32, tiles=in_tiles, f32_generic='bf16x3')
         return
     ops.conv2d(desc, math=math, out_f32=out_f32, tiles=in_tiles)      # engine off: the call made before the engine existed, word for word
 
@@ -1044,7 +1069,8 @@ class BaseBEVBackbone(_Cached):
                 wc, scc, shc = self._p(cv, e_in if (li == 0 and ci == 0) else e_mid, e_mid)
                 conv_layer(x, (xh + 2, xw + 2), wc, scc, shc, True, y, (oh + 2, ow + 2),
                            cin=cv['cin'], in_cstride=xc, ksize=3, stride=s, in_off=0, out_cstride=cv['cout'],
-                           out_d=(1, 1), ho=oh, wo=ow, batch=batch, math=self.math, in_tiles=tl, w_limb3=self._l3(cv))
+                           out_d=(1, 1), ho=oh, wo=ow, batch=batch, math=self.math, in_tiles=tl, w_limb3=self._l3(cv),
+                           w_limb3g=self._l3g(cv))
                 if tl is not None:
                     ops.bev_fill_empty_tiles(tl, batch, oh, ow, shc, True, cv['cout'], y, self.math, zero_resp=zero[ci])
             if audit is not None:
@@ -1083,7 +1109,7 @@ class BaseBEVBackbone(_Cached):
                 conv_layer(x, (xh + 2, xw + 2), *self._p(de['phases'][dy][dx], e_mid, e_mid, scale=de['scale'], shift=de['shift']), True, concat,
                            (h + 2, w + 2), cin=de['cin'], in_cstride=xc, ksize=1, stride=1, in_off=1,
                            out_cstride=ctot, out_coff=coff, out_s=s, out_d=(dy + 1, dx + 1), ho=xh, wo=xw,
-                           batch=batch, math=self.math)
+                           batch=batch, math=self.math, w_limb3g=self._l3g(de['phases'][dy][dx]))
 
     def run(self, bev, batch, sparse_in=None):
         """bev (B, H+2, W+2, Cin) zero-bordered channel-last -> concat (B, H+2, W+2, sum(upsample)) zero-bordered.
@@ -1319,7 +1345,7 @@ class CenterHead(_Cached):
         e = self._e('spatial_features_2d')                    # (the head's hidden maps share the exponent of its input)
         conv_layer(concat, (hp, wp), *self._p(p['shared'], e, e), True, shared, (hp, wp),
                    cin=p['shared']['cin'], in_cstride=concat.shape[3], out_cstride=c, out_d=(1, 1), ho=hp - 2, wo=wp - 2, batch=batch,
-                   math=self.math, w_limb3=self._l3(p['shared']))
+                   math=self.math, w_limb3=self._l3(p['shared']), w_limb3g=self._l3g(p['shared']))
         audit = range_audit.active()
         if audit is not None:
             audit.probe('dense_head.shared_conv', shared, math=self.math, stage='spatial_features_2d', exp=e)
@@ -1338,12 +1364,14 @@ class CenterHead(_Cached):
         hidden = bordered_zeros('head.hidden', (batch, hp, wp, 6 * c), dev)
         e = self._e('spatial_features_2d')
         conv_layer(shared, (hp, wp), *self._p(hp_['hidden'], e, e), True, hidden, (hp, wp),
-                   cin=c, in_cstride=c, out_cstride=6 * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm, w_limb3=self._l3(hp_['hidden']))
+                   cin=c, in_cstride=c, out_cstride=6 * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm, w_limb3=self._l3(hp_['hidden']),
+                   w_limb3g=self._l3g(hp_['hidden']))
         head = torch.empty((batch, h * w, 12), dtype=torch.float32, device=dev)
         # (output layer: no BatchNorm - the plan holds no scale; fp32 output at exponent 0)
         conv_layer(hidden, (hp, wp), *self._p(hp_['final'], e, 0, scale=None, shift=hp_['final']['shift32' if mm else 'shift']), False, head, (h, w),
                    cin=c, in_cstride=6 * c, out_cstride=12, out_d=(0, 0), groups=6, cout_pad=32 if mm else 16,
-                   g_cout=hp_['final']['g_cout'], g_ooff=hp_['final']['g_ooff'], ho=h, wo=w, batch=batch, math=mm, out_f32=True)
+                   g_cout=hp_['final']['g_cout'], g_ooff=hp_['final']['g_ooff'], ho=h, wo=w, batch=batch, math=mm, out_f32=True,
+                   w_limb3g=self._l3g(hp_['final']))
         self._audit_head('heads_list.%d' % index, 'hidden', 'final', hidden, head, hp_['final'], e)
         return head, h, w
 
@@ -1388,12 +1416,12 @@ class CenterHead(_Cached):
         e = self._e('spatial_features_2d')
         conv_layer(shared, (hp, wp), *self._p(hp_['score_hidden'], e, e), True, hidden, (hp, wp),
                    cin=c, in_cstride=c, out_cstride=ng * c, out_d=(1, 1), ho=h, wo=w, batch=batch, math=mm,
-                   w_limb3=self._l3(hp_['score_hidden']))
+                   w_limb3=self._l3(hp_['score_hidden']), w_limb3g=self._l3g(hp_['score_hidden']))
         head = torch.empty((batch, h * w, 12), dtype=torch.float32, device=dev)
         fin = hp_['score_final']
         conv_layer(hidden, (hp, wp), *self._p(fin, e, 0, scale=None, shift=fin['shift32' if mm else 'shift']), False, head, (h, w),
                    cin=c, in_cstride=ng * c, out_cstride=12, out_d=(0, 0), groups=ng, cout_pad=32 if mm else 16,
-                   g_cout=fin['g_cout'], g_ooff=fin['g_ooff'], ho=h, wo=w, batch=batch, math=mm, out_f32=True)
+                   g_cout=fin['g_cout'], g_ooff=fin['g_ooff'], ho=h, wo=w, batch=batch, math=mm, out_f32=True, w_limb3g=self._l3g(fin))
         self._audit_head('heads_list.%d' % index, 'score_hidden', 'score_final', hidden, head, fin, e)
         return head, h, w
 

@@ -162,6 +162,9 @@ _SIGS = {
     'dz_conv3x3_limb3_forward': (c_int, [ctypes.POINTER(Conv2dDesc), c_void_p]),
     'dz_conv3x3_limb3_supported': (c_int, [ctypes.POINTER(Conv2dDesc)]),
     'dz_conv3x3_limb3_variant': (ctypes.c_char_p, [ctypes.POINTER(Conv2dDesc)]),
+    'dz_conv2d_limb3_forward': (c_int, [ctypes.POINTER(Conv2dDesc), c_void_p]),
+    'dz_conv2d_limb3_supported': (c_int, [ctypes.POINTER(Conv2dDesc)]),
+    'dz_conv2d_limb3_variant': (ctypes.c_char_p, [ctypes.POINTER(Conv2dDesc)]),
     'dz_spconv_variant_split': (ctypes.c_char_p, [c_int, c_int]),
     'dz_spconv_variant_split_arm': (ctypes.c_char_p, [c_int, c_int, c_int, c_int, c_size_t]),
     'dz_spconv_variant_split_packed': (ctypes.c_char_p, [c_int, c_int]),

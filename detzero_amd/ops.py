@@ -819,6 +819,8 @@ def range_read(table):
 # dense conv
 # ------------------------------------------------------------------------------------------------
 DENSE_F32_ENGINES = ('mfma32', 'bf16x3')
+# engine of the layers the 3 x 3 stride-1 kernel does not take (strided 3 x 3, 1 x 1 deblock phases, grouped output layers): csrc/conv2d_t.hip
+DENSE_F32_GENERIC_ENGINES = ('mfma32', 'bf16x3')
 
 
 def _conv2d_desc(desc_kwargs):
@@ -838,20 +840,39 @@ def conv3x3_limb3_supported(desc_kwargs):
     return bool(L.load().dz_conv3x3_limb3_supported(ctypes.byref(_conv2d_desc(desc_kwargs))))
 
 
-def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None, f32_engine=None):
+def conv2d_limb3_supported(desc_kwargs):
+    """Whether the generic bf16x3 engine of the f32 mode (dz_conv2d_limb3_forward, csrc/conv2d_t.hip) takes the layer of these
+    dz_conv2d_desc fields.  Host only."""
+    return bool(L.load().dz_conv2d_limb3_supported(ctypes.byref(_conv2d_desc(desc_kwargs))))
+
+
+def pack_weight_limb3_generic(w):
+    """(groups, taps, cin, cout_pad) or (taps, cin, cout_pad) fp32 weights of dz_conv2d_forward -> the operand of dz_conv2d_limb3_forward:
+    (groups * taps, round_up(cout_pad, 32), cin * 3 / 2) limb words (pack_weight_limb3 with the zero rows k_conv2d_t's tiles read)."""
+    return pack_weight_limb3(w.reshape(-1, w.shape[-2], w.shape[-1]), cout_mult=32)
+
+
+def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None, f32_engine=None, f32_generic=None):
     """One dense-conv launch from a dict of dz_conv2d_desc fields.  math != 0: pair16 input / weights
     (pack_weight_split layout) and pair16 output unless out_f32.  tiles: the tensor behind `in_tiles` (profiling only: the work of
     the launch is that of the tiles it runs).  f32_engine='bf16x3' (math 0 only; the split modes ignore it): the three-limb kernel
-    of csrc/conv3x3_t.hip, `w` in the pack_weight_limb3 layout; a layer it does not cover is an error."""
+    of csrc/conv3x3_t.hip, `w` in the pack_weight_limb3 layout; a layer it does not cover is an error.  f32_generic='bf16x3' (likewise
+    math 0 only, and only where f32_engine does not name 'bf16x3'): the generic three-limb kernel of csrc/conv2d_t.hip, `w` in the
+    pack_weight_limb3_generic layout; a layer it does not cover is an error."""
     lib = L.load()
     if f32_engine not in (None,) + DENSE_F32_ENGINES:
         raise L.DetZeroHipError('unknown fp32 dense engine %r (%s)' % (f32_engine, ' | '.join(DENSE_F32_ENGINES)))
+    if f32_generic not in (None,) + DENSE_F32_GENERIC_ENGINES:
+        raise L.DetZeroHipError('unknown generic fp32 dense engine %r (%s)' % (f32_generic, ' | '.join(DENSE_F32_GENERIC_ENGINES)))
     limb3 = f32_engine == 'bf16x3' and not math
+    limb3g = f32_generic == 'bf16x3' and not math and not limb3
     d = _conv2d_desc(desc_kwargs)
 
     def launch():
         if limb3:
             L.check(lib.dz_conv3x3_limb3_forward(ctypes.byref(d), L.stream()), 'dz_conv3x3_limb3_forward')
+        elif limb3g:
+            L.check(lib.dz_conv2d_limb3_forward(ctypes.byref(d), L.stream()), 'dz_conv2d_limb3_forward')
         elif math:
             L.check(lib.dz_conv2d_forward_split(ctypes.byref(d), int(math), 1 if out_f32 else 0, L.stream()), 'dz_conv2d_forward_split')
         else:
@@ -873,6 +894,8 @@ def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None, f32_engine=None):
         nbytes = 4.0 * (share * (m * d.cin + m * cout) + taps * d.cin * d.cout_pad * d.groups)
     if limb3:
         name = lib.dz_conv3x3_limb3_variant(ctypes.byref(d)).decode()
+    elif limb3g:
+        name = lib.dz_conv2d_limb3_variant(ctypes.byref(d)).decode()
     else:
         name = (lib.dz_conv2d_variant_split(ctypes.byref(d), 1 if out_f32 else 0) if math else lib.dz_conv2d_variant(ctypes.byref(d))).decode()
     PROFILER.wrap(name, flops, nbytes, launch)
@@ -1730,7 +1753,7 @@ def _install_guards():
     import types
     g = globals()
     for name, obj in list(g.items()):
-        if isinstance(obj, types.FunctionType) and obj.__module__ == __name__ and not name.startswith('_') and name not in ('grid_size_of', 'math_id', 'pair16_pack', 'pair16_unpack', 'limb3_pack', 'limb3_unpack', 'conv3x3_limb3_supported'):
+        if isinstance(obj, types.FunctionType) and obj.__module__ == __name__ and not name.startswith('_') and name not in ('grid_size_of', 'math_id', 'pair16_pack', 'pair16_unpack', 'limb3_pack', 'limb3_unpack', 'conv3x3_limb3_supported', 'conv2d_limb3_supported'):
             g[name] = _guarded(obj)
     for name in ('build_from_coords', 'downsample', 'neighbors_to'):
         setattr(SparseLevel, name, _guarded(getattr(SparseLevel, name)))

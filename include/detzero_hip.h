@@ -447,6 +447,20 @@ const char *dz_conv2d_variant_split(const dz_conv2d_desc *h_desc, int out_f32);
 int dz_conv3x3_limb3_forward(const dz_conv2d_desc *h_desc, void *stream);
 int dz_conv3x3_limb3_supported(const dz_conv2d_desc *h_desc);
 const char *dz_conv3x3_limb3_variant(const dz_conv2d_desc *h_desc);
+/* Opt-in engine of the exact-fp32 mode for the dense layers dz_conv3x3_limb3_forward does not take (csrc/conv2d_t.hip): the generic
+ * implicit GEMM of dz_conv2d_forward in the three-limb arithmetic above - same fp32 images in and out, same pixel mapping, epilogue
+ * and write contract (never the border, other channels, the pad channels g_cout .. cout_pad - 1, or other phases' pixels).
+ *   desc->w = (groups * kh * kw, round_up(cout_pad, 32), cin / 8, 3, 8) bf16: ops.pack_weight_limb3 of the (groups * taps, cin,
+ *   cout_pad) weights with cout_mult = 32 (zero rows behind cout_pad).  scale / shift as dz_conv2d_forward (NULL = 1 / 0).
+ * dz_conv2d_limb3_supported (host only, no GPU needed) is 1 exactly for kh == kw in {1, 3}, stride in {1, 2}, groups 1..8,
+ * cin % 32 == 0, cout_pad % 16 == 0, no group_shift / group_max / phase_groups / in_rowidx / in_tiles, and image and weight bytes
+ * below 2 GiB; any in_coff / in_cstride / out_coff / out_cstride / out_s* / out_d* / relu that dz_conv2d_forward takes.
+ * dz_conv2d_limb3_forward returns DZ_ERR_UNSUPPORTED, naming the field, for anything else without launching.
+ * dz_conv2d_limb3_variant: "k_conv2d_t<128x128x16>" (cout_pad % 128 == 0), "k_conv2d_t<128x64x32>" (other cout_pad above 32),
+ * "k_conv2d_t<128x32x32>" (cout_pad 16 or 32) or "none".  Accumulation order: taps, then channels, six limb terms smallest first. */
+int dz_conv2d_limb3_forward(const dz_conv2d_desc *h_desc, void *stream);
+int dz_conv2d_limb3_supported(const dz_conv2d_desc *h_desc);
+const char *dz_conv2d_limb3_variant(const dz_conv2d_desc *h_desc);
 /* dz_linear_forward on pair16 rows: x (rows, x_stride words) pair16, w (cout_pad, cin) pair16 (cin, cout_pad % 32 == 0), y pair16
  * rows or, with out_f32 != 0, fp32 rows; group_shift (row groups, cout_pad) fp32 as in dz_linear_forward.
  * group_max != 0 (with out_f32): the torch.max over the points of an object that follows the PointNet encoders

@@ -1,6 +1,7 @@
 """Register / occupancy table of the kernels of one .hip file (cross-compiles for gfx950, no GPU needed).
 
     python tools/kernel_regs.py detzero_amd/csrc/sparse_conv_h.hip [filter]
+    python tools/kernel_regs.py detzero_amd/csrc/conv2d_t.hip k_conv2d_t        (the three instances of the generic bf16x3 dense engine)
 """
 import os
 import re
