@@ -231,7 +231,7 @@ def set_math(model, mode):
     return model
 
 
-def set_sparse_engine(model, engine, f32_engine=None, f32_gather=None):
+def set_sparse_engine(model, engine, f32_engine=None, f32_gather=None, f32_small=None):
     """Convolution engine of the sparse backbone in the split math modes: 'xrun' (default: the gather kernels plus sparse_conv_x.hip
     for the submanifold convolutions of the 32 / 64 / 128-channel levels), 'gather' (sparse_conv_h.hip / sparse_conv_w.h only; both
     on rows in the canonical linear-key order) or 'tiles' (sparse_conv_t.hip: tile-resident inputs on rows in the brick order).
@@ -241,8 +241,11 @@ def set_sparse_engine(model, engine, f32_engine=None, f32_gather=None):
     as it is.
     f32_gather: the arithmetic of the exact-fp32 convolutions that stay on the gather path whatever f32_engine says (conv_input, conv1,
     the strided layers, submanifold layers without x-run windows): 'mfma32' (default: sparse_conv.hip) or 'bf16x3' (three exact bf16
-    limbs per operand, sparse_conv_gt.hip, for the layers it covers); None leaves it as it is.  A refused call changes nothing."""
-    model.backbone3d.set_engine(engine, f32_engine, f32_gather)
+    limbs per operand, sparse_conv_gt.hip, for the layers it covers); None leaves it as it is.
+    f32_small: the kernel of the exact-fp32 mode's 16-input-channel layers (conv_input, conv1, conv2's stride-2 layer): 'gather' (default:
+    what f32_gather gives them) or 'wave_bf16x3' (wave-private tiles with resident limb weights, sparse_conv_wt.hip, for the layers it
+    covers, whatever f32_gather says); None leaves it as it is.  A refused call changes nothing."""
+    model.backbone3d.set_engine(engine, f32_engine, f32_gather, f32_small)
     return model
 
 

@@ -486,25 +486,32 @@ class VoxelResBackBone8x(_Cached):
         # strided layers, and every submanifold layer whose table has no x-run windows): 'mfma32' (default: k_spconv) or 'bf16x3' (three
         # exact bf16 limbs per operand on the bf16 matrix pipe: sparse_conv_gt.hip, for the layers dz_spconv_limb3_tile_rows covers)
         self.f32_gather = os.environ.get('DZ_TUNE_SPCONV_F32_GATHER', 'mfma32')
+        # ... and, on top of either arithmetic, the kernel of the exact-fp32 mode's 16-input-channel layers (conv_input, conv1, conv2's
+        # stride-2 layer): 'gather' (default: what f32_gather gives them) or 'wave_bf16x3' (wave-private tiles, resident limb weights:
+        # sparse_conv_wt.hip, for the layers dz_spconv_limb3_w_tile_rows covers)
+        self.f32_small = 'gather'
         # output widths whose convolutions run on the tile engine when it is selected (the others keep the gather kernels)
         self.tile_couts = tuple(int(c) for c in os.environ.get('DZ_TUNE_SPCONV_TILE_COUTS', '16,32,64,128').split(',') if c)
         self.backbone_channels = {'x_conv1': channels[0], 'x_conv2': channels[1], 'x_conv3': channels[2],
                                   'x_conv4': channels[3]}
         self.channels = channels
 
-    def set_engine(self, engine, f32_engine=None, f32_gather=None):
+    def set_engine(self, engine, f32_engine=None, f32_gather=None, f32_small=None):
         """'gather' (rows in the canonical linear-key order), 'xrun' (gather + the z-slab window kernel for the submanifold
         convolutions of the 32 / 64 / 128-channel levels; same row order) or 'tiles' (tile-resident convolution; rows in brick order).
         f32_engine (None = unchanged): the engine of the exact-fp32 mode, 'gather', 'xrun' or 'xrun_bf16x3' (the tables of 'xrun'; the
         submanifold layers on the three-limb kernel of sparse_conv_xt.hip where it covers the width, on sparse_conv_xf.hip otherwise).
         f32_gather (None = unchanged): the arithmetic of the exact-fp32 mode's gather-path convolutions, 'mfma32' or 'bf16x3'
-        (sparse_conv_gt.hip).  A refused call changes nothing."""
+        (sparse_conv_gt.hip).  f32_small (None = unchanged): the kernel of its 16-input-channel layers, 'gather' (what f32_gather gives
+        them) or 'wave_bf16x3' (sparse_conv_wt.hip).  A refused call changes nothing."""
         if engine not in ('gather', 'tiles', 'xrun'):
             raise DetZeroHipError('unknown sparse engine %r (gather | xrun | tiles)' % (engine,))
         if f32_engine is not None and f32_engine not in ops.SPARSE_F32_ENGINES:
             raise DetZeroHipError('unknown fp32 sparse engine %r (%s)' % (f32_engine, ' | '.join(ops.SPARSE_F32_ENGINES)))
         if f32_gather is not None and f32_gather not in ops.SPARSE_F32_GATHER_ENGINES:
             raise DetZeroHipError('unknown fp32 gather arithmetic %r (%s)' % (f32_gather, ' | '.join(ops.SPARSE_F32_GATHER_ENGINES)))
+        if f32_small is not None and f32_small not in ops.SPARSE_F32_SMALL_ENGINES:
+            raise DetZeroHipError('unknown fp32 small-layer engine %r (%s)' % (f32_small, ' | '.join(ops.SPARSE_F32_SMALL_ENGINES)))
         if engine == 'tiles' and ops.L.load().dz_spconv_tile_rows() == 0:
             raise DetZeroHipError("sparse engine 'tiles' is an experimental build option (measured slower, DESIGN.md 2d): rebuild the library "
                                   'with DZ_BUILD_EXPERIMENTAL=1 (python -m detzero_amd.build --force)')
@@ -513,6 +520,8 @@ class VoxelResBackBone8x(_Cached):
             self.f32_engine = f32_engine
         if f32_gather is not None:
             self.f32_gather = f32_gather
+        if f32_small is not None:
+            self.f32_small = f32_small
         self.layout = ops.LAYOUT_BRICK if engine == 'tiles' else ops.LAYOUT_LINEAR
 
     # ---- kernel-layout parameters -------------------------------------------------------------
@@ -559,19 +568,21 @@ class VoxelResBackBone8x(_Cached):
     def _route_p(self, entry, nbr, e_in, e_out, in_rows):
         """((weights, scale, shift), further keywords of ops.spconv_forward) of a convolution over table `nbr`.  The backbone's engine
         switches are preferences, so ops.spconv_route is asked first: `_p`'s parameters and no keyword, unless the route reads limb
-        weights - then the entry's limb form (packed once, cached in the plan entry; both bf16x3 kernels read it) and the keyword
+        weights - then the entry's limb form (packed once, cached in the plan entry; every sparse bf16x3 kernel reads it) and the keyword
         that names the engine.  (The split modes have one weight form and no keyword: nothing to ask.  In f32 spconv_forward resolves
         once more to check the keyword: a few host-side library queries per layer, nothing on the device.)"""
         w, scale, shift = self._p(entry, e_in, e_out)
         if self.math:
             return (w, scale, shift), {}
         cin, cout = int(w.shape[1]), int(w.shape[2])
-        route = ops.spconv_route(nbr, cin, cout, 0, self.f32_engine, getattr(self, 'f32_gather', 'mfma32'), in_rows)
+        route = ops.spconv_route(nbr, cin, cout, 0, self.f32_engine, getattr(self, 'f32_gather', 'mfma32'), in_rows,
+                                 getattr(self, 'f32_small', 'gather'))
         if route.weights != 'limb3':
             return (w, scale, shift), {}
         if 'w_xlimb3' not in entry:
             entry['w_xlimb3'] = ops.pack_weight_limb3(entry['w'], cout_mult=32)
-        more = {'f32_engine': 'xrun_bf16x3'} if route.engine == 'xrun_bf16x3' else {'f32_gather': 'bf16x3', 'cout': cout}
+        more = ({'f32_engine': 'xrun_bf16x3'} if route.engine == 'xrun_bf16x3'
+                else {'f32_small': 'wave_bf16x3', 'cout': cout} if route.engine == 'wave_bf16x3' else {'f32_gather': 'bf16x3', 'cout': cout})
         return (entry['w_xlimb3'], scale, shift), more
 
     def build_pyramid(self, voxel_features, voxel_coords, batch_size, d_n=None, overlap=True, side_key=0, caps=None, level1=None,

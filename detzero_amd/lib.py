@@ -147,6 +147,10 @@ _SIGS = {
                                         c_void_p, c_int, c_void_p, c_int, c_void_p]),
     'dz_spconv_limb3_tile_rows': (c_int, [c_int, c_int]),
     'dz_spconv_limb3_variant': (ctypes.c_char_p, [c_int, c_int]),
+    'dz_spconv_forward_limb3_w': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'dz_spconv_limb3_w_tile_rows': (c_int, [c_int, c_int]),
+    'dz_spconv_limb3_w_variant': (ctypes.c_char_p, [c_int, c_int]),
     'dz_bev_tile_cover_words': (c_size_t, [c_int, c_int, c_int]),
     'dz_bev_tile_cover_offset': (c_size_t, [c_int, c_int, c_int]),
     'dz_bev_tile_cover_ws_words': (c_size_t, [c_int, c_int, c_int, c_int]),

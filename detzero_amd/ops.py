@@ -430,6 +430,9 @@ SPARSE_F32_ENGINES = ('gather', 'xrun', 'xrun_bf16x3')
 # ... and, orthogonal to it, the arithmetic of the convolutions that STAY on the gather path (Backbone3d.set_engine(f32_gather=)):
 # 'mfma32' = k_spconv (sparse_conv.hip, fp32 MFMA); 'bf16x3' = k_spconv_gt (sparse_conv_gt.hip, three exact bf16 limbs per operand)
 SPARSE_F32_GATHER_ENGINES = ('mfma32', 'bf16x3')
+# ... and, on top of either, the kernel of the 16-input-channel layers (conv_input, conv1, conv2's stride-2 layer; set_engine(f32_small=)):
+# 'gather' = whatever f32_gather gives them; 'wave_bf16x3' = k_spconv_wt (sparse_conv_wt.hip: wave-private tiles, resident limb weights)
+SPARSE_F32_SMALL_ENGINES = ('gather', 'wave_bf16x3')
 
 
 # what spconv_route returns: a key of _SPCONV_ENGINES; the weight form the engine reads - 'taps' (fp32 (kvol, cin, cout)), 'split'
@@ -446,6 +449,7 @@ def _x_args(t):
 # spconv_route tries them
 _SPCONV_ENGINES = {
     'xrun_bf16x3': ('limb3', 'dz_spconv_forward_x_limb3', 'dz_spconv_x_limb3_variant', _x_args),
+    'wave_bf16x3': ('limb3', 'dz_spconv_forward_limb3_w', 'dz_spconv_limb3_w_variant', lambda t: (L.ptr(t.words), L.ptr(t.tile_masks), t.kvol)),
     'gather_bf16x3': ('limb3', 'dz_spconv_forward_limb3', 'dz_spconv_limb3_variant', lambda t: (L.ptr(t.words), L.ptr(t.tile_masks), t.kvol)),
     'xrun_f32': ('taps', 'dz_spconv_forward_x_f32', 'dz_spconv_x_f32_variant', _x_args),
     'xrun_split': ('split', 'dz_spconv_forward_split_x', 'dz_spconv_x_variant', _x_args),
@@ -466,11 +470,12 @@ def xrun_unit(cin, cout, math, bf16x3=False):
     return lib.dz_spconv_x_tile_rows(cin, cout) if cin == cout and (math or rows(cin, cout) > 0) else 0
 
 
-def spconv_route(table, cin, cout, math, f32_engine=None, f32_gather=None, in_rows=0):
+def spconv_route(table, cin, cout, math, f32_engine=None, f32_gather=None, in_rows=0, f32_small=None):
     """The engine (SpconvRoute) of a cin -> cout convolution over NeighborTable `table`: host logic, the first match wins.
       math 0: 'xrun_bf16x3' for f32_engine 'xrun_bf16x3' on a packed table with windows in the unit of a layer k_spconv_xt covers;
-              'gather_bf16x3' for f32_gather 'bf16x3' on a plain table with tile masks and a layer k_spconv_gt covers, the table, the
-              output and `in_rows` input rows all below 2 GiB; 'xrun_f32' on a packed table with windows in the unit of a layer
+              'wave_bf16x3' for f32_small 'wave_bf16x3' on a plain table with tile masks and a layer k_spconv_wt covers, the table, the
+              output and `in_rows` input rows all below 2 GiB (whatever f32_gather says); 'gather_bf16x3' for f32_gather 'bf16x3' on
+              such a table and sizes and a layer k_spconv_gt covers; 'xrun_f32' on a packed table with windows in the unit of a layer
               k_spconv_xf covers; 'gather_f32' on any other plain table - no fp32 kernel reads another packed one: an error
       else:   'xrun_split' on a packed table with windows, cin == cout; 'tiles' on a table with tiles, kvol >= 3;
               'gather_split_packed' / 'gather_split' on any other packed / plain table
@@ -479,13 +484,17 @@ def spconv_route(table, cin, cout, math, f32_engine=None, f32_gather=None, in_ro
     cin, cout = int(cin), int(cout)
     xwin = table.xwin if table.packed and cin == cout else None
     windows_fit = lambda bf16x3: xwin is not None and 0 != xrun_unit(cin, cout, 0, bf16x3) == xwin.tile_rows
+    # what both bf16x3 gather kernels read: a plain table with tile masks; table, output and input rows below 2 GiB
+    plain_fits = lambda: (not table.packed and table.tile_masks is not None
+                          and 4 * max(table.numel(), table.shape[1] * cout, int(in_rows) * cin) < (1 << 31))
     if math:
         engine = ('xrun_split' if xwin is not None else 'tiles' if table.kvol >= 3 and table.tiles is not None
                   else 'gather_split_packed' if table.packed else 'gather_split')
     elif f32_engine == 'xrun_bf16x3' and windows_fit(True):
         engine = 'xrun_bf16x3'
-    elif (f32_gather == 'bf16x3' and not table.packed and table.tile_masks is not None and lib.dz_spconv_limb3_tile_rows(cin, cout) > 0
-          and 4 * max(table.numel(), table.shape[1] * cout, int(in_rows) * cin) < (1 << 31)):
+    elif f32_small == 'wave_bf16x3' and plain_fits() and lib.dz_spconv_limb3_w_tile_rows(cin, cout) > 0:
+        engine = 'wave_bf16x3'
+    elif f32_gather == 'bf16x3' and plain_fits() and lib.dz_spconv_limb3_tile_rows(cin, cout) > 0:
         engine = 'gather_bf16x3'
     elif windows_fit(False):
         engine = 'xrun_f32'
@@ -499,13 +508,15 @@ def spconv_route(table, cin, cout, math, f32_engine=None, f32_gather=None, in_ro
 
 
 def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, relu=True, out=None, in_level=None, math=0, cout=None,
-                   f32_engine=None, f32_gather=None):
+                   f32_engine=None, f32_gather=None, f32_small=None, *, max_workgroups=0):
     """feats (m_in,cin); nbr: NeighborTable of (kvol,cap); returns (cap,cout), computed by the engine of spconv_route.
     math == 0: fp32 rows, w_taps (kvol,cin,cout) fp32; a packed table with x-run windows (neighbors_xrun / build_windows) runs a
     cin == cout layer of 32 / 64 / 128 channels on the exact-fp32 x-run kernel (dz_spconv_forward_x_f32).
     f32_engine / f32_gather (math 0 only; the split modes ignore them) are explicit - a table or layer the named kernel does not
     cover is an error: 'xrun_bf16x3' = that table and those rows on the three-limb kernel of csrc/sparse_conv_xt.hip; 'bf16x3' = a
-    plain table with tile masks on the three-limb gather kernel of csrc/sparse_conv_gt.hip.  Both read `w_taps` in the
+    plain table with tile masks on the three-limb gather kernel of csrc/sparse_conv_gt.hip; f32_small 'wave_bf16x3' = such a table
+    and a 16 -> 16 or 16 -> 32 layer on the wave-private three-limb kernel of csrc/sparse_conv_wt.hip (it goes before f32_gather;
+    max_workgroups, for tests and tools, caps its persistent grid: 0 = as many as fit).  All read `w_taps` in the
     pack_weight_limb3(w, cout_mult=32) layout (kvol, cout_pad, cin * 3 / 2), with `cout=` the true width where it is below 32
     (default: the BatchNorm vector's, else the weights').  None, 'gather', 'xrun', 'mfma32' ask for nothing.
     math != 0: pair16 rows (in, residual, out), w_taps (kvol,cout_pad,cin) pair16 from pack_weight_split."""
@@ -514,7 +525,10 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
         raise L.DetZeroHipError('unknown fp32 sparse engine %r (%s)' % (f32_engine, ' | '.join(SPARSE_F32_ENGINES)))
     if f32_gather not in (None,) + SPARSE_F32_GATHER_ENGINES:
         raise L.DetZeroHipError('unknown fp32 gather arithmetic %r (%s)' % (f32_gather, ' | '.join(SPARSE_F32_GATHER_ENGINES)))
-    limb = not math and (f32_engine == 'xrun_bf16x3' or f32_gather == 'bf16x3')
+    if f32_small not in (None,) + SPARSE_F32_SMALL_ENGINES:
+        raise L.DetZeroHipError('unknown fp32 small-layer engine %r (%s)' % (f32_small, ' | '.join(SPARSE_F32_SMALL_ENGINES)))
+    wave = not math and f32_small == 'wave_bf16x3'
+    limb = not math and (f32_engine == 'xrun_bf16x3' or f32_gather == 'bf16x3' or wave)
     if math or limb:
         # (split and limb weights are padded to 32 output channels: the true count comes from `cout=`, the BatchNorm vector, else the weights)
         if limb and (w_taps.dim() != 3 or w_taps.shape[0] != nbr.kvol or w_taps.shape[2] % 12 != 0):
@@ -527,8 +541,14 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
                                     % (cin, cout, w_taps.shape[1]))
     else:
         cin, cout = w_taps.shape[1], w_taps.shape[2]
-    route = spconv_route(nbr, cin, cout, math, f32_engine, f32_gather, feats.shape[0])
-    if limb and route.engine != ('xrun_bf16x3' if f32_engine == 'xrun_bf16x3' else 'gather_bf16x3'):
+    route = spconv_route(nbr, cin, cout, math, f32_engine, f32_gather, feats.shape[0], f32_small)
+    if wave and f32_engine != 'xrun_bf16x3' and route.engine != 'wave_bf16x3':
+        raise L.DetZeroHipError("spconv_forward: this %s table and %d -> %d layer run on %r - f32_small 'wave_bf16x3' needs a plain table with tile "
+                                'masks, a 16 -> 16 or 16 -> 32 layer the library covers and tensors below 2 GiB'
+                                % ('packed' if nbr.packed else 'plain', cin, cout, route.engine))
+    if max_workgroups and route.engine != 'wave_bf16x3':
+        raise L.DetZeroHipError('spconv_forward: max_workgroups caps the grid of the wave_bf16x3 engine only, this layer runs on %r' % (route.engine,))
+    if limb and route.engine != ('xrun_bf16x3' if f32_engine == 'xrun_bf16x3' else 'wave_bf16x3' if wave else 'gather_bf16x3'):
         raise L.DetZeroHipError("spconv_forward: this %s table and %d -> %d layer run on %r - f32_engine 'xrun_bf16x3' needs a packed table with x-run "
                                 "windows in the unit of a cin == cout layer it covers, f32_gather 'bf16x3' a plain table with tile masks, a layer it "
                                 'covers and tensors below 2 GiB' % ('packed' if nbr.packed else 'plain', cin, cout, route.engine))
@@ -542,7 +562,7 @@ def spconv_forward(feats, nbr, out_level, w_taps, scale, shift, residual=None, r
     def launch():
         rc = getattr(lib, entry)(L.ptr(feats), feats.shape[0], cin, *table_args(nbr), cap, L.ptr(out_level.d_m), L.ptr(w_taps), L.ptr(scale),
                                  L.ptr(shift), L.ptr(residual), 1 if relu else 0, L.ptr(out), cout, *((int(math),) if form == 'split' else ()),
-                                 L.stream())
+                                 *((int(max_workgroups),) if route.engine == 'wave_bf16x3' else ()), L.stream())
         L.check(rc, 'dz_spconv_forward')
     if PROFILER is None:
         launch()

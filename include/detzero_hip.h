@@ -385,6 +385,24 @@ int dz_spconv_forward_limb3(const float *in, int in_rows, int cin, const int *nb
                             int relu, float *out, int cout, void *stream);
 int dz_spconv_limb3_tile_rows(int cin, int cout);
 const char *dz_spconv_limb3_variant(int cin, int cout);
+/* The wave-private form of dz_spconv_forward_limb3 for the 16-channel layers (csrc/sparse_conv_wt.hip, opt-in): channels 16 -> 16
+ * and 16 -> 32, the same table, tile masks, fp32 rows, w_limb words (rows at or beyond cout are not read), epilogue and write
+ * contract.  A wave owns 32 output rows, the limbs of all kvol taps of the weights stay in LDS, gathered rows go straight into
+ * registers and are split there; per (tap, 16-row half, 16-channel output block) three v_mfma_f32_16x16x32_bf16 carry the same six
+ * limb terms, smallest first: [w_h | w_l].[x_l | x_h], [w_m | w_m].[x_h | x_m], [w_h | w_h].[x_h | x_m].  Per output element: taps
+ * ascending, then those three, whatever the grid: launches agree bit for bit.
+ *   max_workgroups: 0 = as many persistent workgroups as fit; n > 0 is rounded up to a multiple of 8 and caps the grid (tests and
+ *   tools: a small input then reaches a wave's second batch of 64 tile masks and several deal rounds).
+ *   Refused before any launch, as dz_spconv_forward_limb3: null pointers (tile_masks included), kvol outside 1..27 and a negative
+ *   max_workgroups (DZ_ERR_INVALID), channels the selector does not cover, and an input, output or table of 2 GiB or more
+ *   (DZ_ERR_UNSUPPORTED).
+ *   dz_spconv_limb3_w_tile_rows: rows one workgroup takes per deal step (32 x its waves), 0 = not covered (the layer keeps the
+ *   kernel it has).  dz_spconv_limb3_w_variant: "k_spconv_wt<16x16>", "k_spconv_wt<16x32>" or "none". */
+int dz_spconv_forward_limb3_w(const float *in, int in_rows, int cin, const int *nbr, const uint32_t *tile_masks, int kvol, int cap_out,
+                              const int *d_m_out, const float *w_limb, const float *scale, const float *shift, const float *residual,
+                              int relu, float *out, int cout, int max_workgroups, void *stream);
+int dz_spconv_limb3_w_tile_rows(int cin, int cout);
+const char *dz_spconv_limb3_w_variant(int cin, int cout);
 /* HeightCompression WITHOUT the dense image (round 5): idx (batch, h + 2 pad, w + 2 pad, 2) int32 = the feature row of every
  * (pixel, z slab) of a two-slab level, -1 = empty cell / border / rank >= feat_rows (overflowed capacity).  The first block of
  * BaseBEVBackbone reads the level's rows through it (dz_conv2d_desc.in_rowidx): height_compression.py:20-24 and the ZeroPad2d of

@@ -4,11 +4,14 @@
     python tools/bench_spconv.py [--batch 4] [--reps 20] [--points 160000]
     python tools/bench_spconv.py --math f32 --f32-engine gather,xrun,xrun_bf16x3 [--rounds 2]
     python tools/bench_spconv.py --math f32 --f32-gather mfma32,bf16x3 [--rounds 2]
+    python tools/bench_spconv.py --math f32 --f32-small gather,wave_bf16x3 [--rounds 2]
 
 With --f32-engine: the submanifold layers of the 32 / 64 / 128-channel levels in exact fp32 on each listed engine, on the same
 tensors and tables of one level, launches interleaved in one process (blocks of 5 launches per engine, alternating).
 With --f32-gather: every distinct layer of the backbone on its plain table (the strided layers and conv_out included) in exact fp32
 on each listed gather arithmetic - k_spconv and k_spconv_gt - on the same tensors and tables, interleaved in the same way.
+With --f32-small: the layers the wave-private bf16x3 kernel covers (16 -> 16 with and without residual, 16 -> 32) on k_spconv_gt (what
+f32_gather='bf16x3' runs, the 'gather' arm) and on k_spconv_wt, on the same tensors and tables, interleaved in the same way.
 
 Builds the sparse levels of a batch of synthetic frames once, then times every distinct sparse conv of
 VoxelResBackBone8x separately (HIP events on the launch stream) and prints rows, rulebook pairs, mean valid
@@ -34,12 +37,15 @@ def main():
     ap.add_argument('--only', default='', help='comma list of cin-cout pairs to time (default: every layer)')
     ap.add_argument('--f32-engine', default='', help='comma list of gather | xrun | xrun_bf16x3: A/B of the fp32 engines per submanifold layer')
     ap.add_argument('--f32-gather', default='', help='comma list of mfma32 | bf16x3: A/B of the fp32 gather arithmetics per layer, strided ones included')
-    ap.add_argument('--rounds', type=int, default=2, help='with --f32-engine / --f32-gather: repetitions of the whole comparison')
+    ap.add_argument('--f32-small', default='', help='comma list of gather | wave_bf16x3: A/B of k_spconv_gt and k_spconv_wt on the 16-input-channel layers')
+    ap.add_argument('--rounds', type=int, default=2, help='with --f32-engine / --f32-gather / --f32-small: repetitions of the whole comparison')
     args = ap.parse_args()
     if args.f32_engine:
         return compare_f32_engines(args)
     if args.f32_gather:
         return compare_f32_gather(args)
+    if args.f32_small:
+        return compare_f32_small(args)
     dev = torch.device('cuda', 0)
     from detzero_amd import ops
     from detzero_amd.centerpoint import FramePipeline, synth_detector
@@ -212,8 +218,6 @@ def compare_f32_gather(args):
     dev = torch.device('cuda', 0)
     from detzero_amd import lib as L
     from detzero_amd import ops
-    from detzero_amd.centerpoint import FramePipeline, set_sparse_engine, synth_detector
-    from detzero_amd.synth import VOXEL_SIZE_01, synth_waymo_frame
     arith = [e for e in args.f32_gather.split(',') if e]
     for e in arith:
         if e not in ops.SPARSE_F32_GATHER_ENGINES:
@@ -221,6 +225,56 @@ def compare_f32_gather(args):
     if args.math != 'f32':
         raise SystemExit('--f32-gather compares the gather arithmetics of --math f32')
     lib = L.load()
+    real = ops.spconv_forward
+    layers = _plain_layers(args, dev)
+    for rnd in range(args.rounds):
+        for (f, nbr, lvl, w, scale, shift, residual, relu) in layers:
+            kvol, cin, cout = (int(v) for v in w.shape)
+            out = torch.empty((lvl.cap, cout), dtype=torch.float32, device=dev)
+            runs = {}
+            for e in arith:
+                if e == 'bf16x3' and lib.dz_spconv_limb3_tile_rows(cin, cout) > 0:
+                    wl = ops.pack_weight_limb3(w, cout_mult=32)
+                    runs[e] = (lib.dz_spconv_limb3_variant(cin, cout).decode(),
+                               lambda wl=wl: real(f, nbr, lvl, wl, scale, shift, residual, relu, out, cout=cout, f32_gather='bf16x3'))
+                else:               # 'mfma32', and a layer the bf16x3 kernel does not ship for: what the backbone launches then
+                    runs[e] = (lib.dz_spconv_variant(cin, cout).decode(), lambda: real(f, nbr, lvl, w, scale, shift, residual, relu, out))
+            _alternate_and_print(args, rnd, arith, runs, nbr, lvl, w, residual)
+
+
+def compare_f32_small(args):
+    dev = torch.device('cuda', 0)
+    from detzero_amd import lib as L
+    from detzero_amd import ops
+    arms = [e for e in args.f32_small.split(',') if e]
+    for e in arms:
+        if e not in ops.SPARSE_F32_SMALL_ENGINES:
+            raise SystemExit('unknown fp32 small-layer engine %r (%s)' % (e, ' | '.join(ops.SPARSE_F32_SMALL_ENGINES)))
+    if args.math != 'f32':
+        raise SystemExit('--f32-small compares the kernels of --math f32')
+    lib = L.load()
+    real = ops.spconv_forward
+    layers = [l for l in _plain_layers(args, dev) if lib.dz_spconv_limb3_w_tile_rows(int(l[3].shape[1]), int(l[3].shape[2])) > 0]
+    if not layers:
+        raise SystemExit('--f32-small: the library ships k_spconv_wt for none of the selected layers')
+    for rnd in range(args.rounds):
+        for (f, nbr, lvl, w, scale, shift, residual, relu) in layers:
+            kvol, cin, cout = (int(v) for v in w.shape)
+            out = torch.empty((lvl.cap, cout), dtype=torch.float32, device=dev)
+            wl = ops.pack_weight_limb3(w, cout_mult=32)
+            runs = {'gather': (lib.dz_spconv_limb3_variant(cin, cout).decode(),
+                               lambda: real(f, nbr, lvl, wl, scale, shift, residual, relu, out, cout=cout, f32_gather='bf16x3')),
+                    'wave_bf16x3': (lib.dz_spconv_limb3_w_variant(cin, cout).decode(),
+                                    lambda: real(f, nbr, lvl, wl, scale, shift, residual, relu, out, cout=cout, f32_small='wave_bf16x3'))}
+            _alternate_and_print(args, rnd, arms, runs, nbr, lvl, w, residual)
+
+
+def _plain_layers(args, dev):
+    """Every distinct sparse convolution of one exact-fp32 backbone pass on plain tables: (feats, table, level, taps, scale, shift,
+    residual, relu) per layer."""
+    from detzero_amd import ops
+    from detzero_amd.centerpoint import FramePipeline, set_sparse_engine, synth_detector
+    from detzero_amd.synth import VOXEL_SIZE_01, synth_waymo_frame
     model, cfg, info = synth_detector(VOXEL_SIZE_01, seed=0)
     model = model.to(dev)
     bb = model.backbone3d
@@ -249,44 +303,40 @@ def compare_f32_gather(args):
             continue
         seen.add(key)
         layers.append(call)
-    for rnd in range(args.rounds):
-        for (f, nbr, lvl, w, scale, shift, residual, relu) in layers:
-            kvol, cin, cout = (int(v) for v in w.shape)
-            m = lvl.num_active()
-            pairs = ops.table_pairs(nbr, m)
-            out = torch.empty((lvl.cap, cout), dtype=torch.float32, device=dev)
-            runs = {}
-            for e in arith:
-                if e == 'bf16x3' and lib.dz_spconv_limb3_tile_rows(cin, cout) > 0:
-                    wl = ops.pack_weight_limb3(w, cout_mult=32)
-                    runs[e] = (lib.dz_spconv_limb3_variant(cin, cout).decode(),
-                               lambda wl=wl: real(f, nbr, lvl, wl, scale, shift, residual, relu, out, cout=cout, f32_gather='bf16x3'))
-                else:               # 'mfma32', and a layer the bf16x3 kernel does not ship for: what the backbone launches then
-                    runs[e] = (lib.dz_spconv_variant(cin, cout).decode(), lambda: real(f, nbr, lvl, w, scale, shift, residual, relu, out))
-            for e in arith:
-                for _ in range(3):
-                    runs[e][1]()
-            ms = {e: 0.0 for e in arith}
-            blocks, per = max(1, args.reps // 5), 5
-            evs = []
-            for _ in range(blocks):
-                for e in arith:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(per):
-                        runs[e][1]()
-                    e1.record()
-                    evs.append((e, e0, e1))
-            torch.cuda.synchronize()
-            for e, e0, e1 in evs:
-                ms[e] += e0.elapsed_time(e1)
-            flop = 2.0 * pairs * cin * cout
-            for e in arith:
-                us = 1000.0 * ms[e] / (blocks * per)
-                tfs = flop / us / 1e6
-                print('round %d  k%-2d %3d->%-3d rows %8d pairs/row %5.2f %s  %-7s %-24s %9.1f us  alg %6.2f TF/s  %5.1f %% of the %.0f TF/s six-MFMA peak'
-                      % (rnd, kvol, cin, cout, m, pairs / max(m, 1), '+res' if residual is not None else '    ', e, runs[e][0], us, tfs,
-                         100.0 * tfs / BF16X3_PEAK_TFS, BF16X3_PEAK_TFS), flush=True)
+    return layers
+
+
+def _alternate_and_print(args, rnd, arms, runs, nbr, lvl, w, residual):
+    """runs: arm -> (kernel name, launch).  Three warm-up launches per arm, then blocks of 5 launches per arm alternating in this process,
+    each block between two events; one line per arm."""
+    from detzero_amd import ops
+    kvol, cin, cout = (int(v) for v in w.shape)
+    m = lvl.num_active()
+    pairs = ops.table_pairs(nbr, m)
+    for e in arms:
+        for _ in range(3):
+            runs[e][1]()
+    ms = {e: 0.0 for e in arms}
+    blocks, per = max(1, args.reps // 5), 5
+    evs = []
+    for _ in range(blocks):
+        for e in arms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(per):
+                runs[e][1]()
+            e1.record()
+            evs.append((e, e0, e1))
+    torch.cuda.synchronize()
+    for e, e0, e1 in evs:
+        ms[e] += e0.elapsed_time(e1)
+    flop = 2.0 * pairs * cin * cout
+    for e in arms:
+        us = 1000.0 * ms[e] / (blocks * per)
+        tfs = flop / us / 1e6
+        print('round %d  k%-2d %3d->%-3d rows %8d pairs/row %5.2f %s  %-11s %-24s %9.1f us  alg %6.2f TF/s  %5.1f %% of the %.0f TF/s six-MFMA peak'
+              % (rnd, kvol, cin, cout, m, pairs / max(m, 1), '+res' if residual is not None else '    ', e, runs[e][0], us, tfs,
+                 100.0 * tfs / BF16X3_PEAK_TFS, BF16X3_PEAK_TFS), flush=True)
 
 
 if __name__ == '__main__':
