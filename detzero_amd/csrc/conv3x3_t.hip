@@ -195,14 +195,13 @@ __global__ __launch_bounds__(T3_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             for (int s = 0; s < 3; ++s) f.cf[ct][s] = cp[ct * 32 * T3_ROW_U4 + s];
     };
     auto mma = [&](const Frag &f) {
-        // (weight limb, input limb) of the six terms, smallest first; term-major, so consecutive MFMAs go to different accumulators
-        constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int term = 0; term < 6; ++term)
+        // term-major, so consecutive MFMAs go to different accumulators
+        limb3_terms([&](auto wl, auto xl) {
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-                for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = MathBF16::mma(f.cf[ct][TW[term]], f.pf[pt][TX[term]], acc[ct][pt]);
+                for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = MathBF16::mma(f.cf[ct][wl], f.pf[pt][xl], acc[ct][pt]);
+        });
     };
     auto tap_mma = [&](int tap, int buf) {
         // both k-steps' fragments are requested up front: the second set lands under the first set's MFMAs

@@ -48,25 +48,9 @@ struct SpConvGTArgs {
     unsigned int in_bytes, w_bytes, nbr_bytes;
 };
 
-// BP rows (MFMA N side) x BC output channels (MFMA M side, = cout_pad), KC channels of one tap per chunk, WP x WC waves
-template <int BP_, int BC_, int KC_, int WP_, int WC_>
-struct GTile {
-    static constexpr int BP = BP_, BC = BC_, KC = KC_, WP = WP_, WC = WC_;
-    static constexpr int THREADS = 64 * WP * WC;
-    static constexpr int PT = BP / (32 * WP);               // 32-row fragments per wave
-    static constexpr int CT = BC / (32 * WC);               // 32-channel fragments per wave
-    static constexpr int G = KC / 8;                        // 48-byte limb groups per LDS row
-    static constexpr int ROWB = G * 48 + 16;                // LDS row stride
-    static constexpr int P_PER_THREAD = BP * G / THREADS;   // 8-channel groups of the gathered chunk per thread
-    static constexpr int C_PIECES = BC * G * 3;             // 16-byte pieces of a tap's weight slice
-    static constexpr int C_PER_THREAD = (C_PIECES + THREADS - 1) / THREADS;
-    static constexpr int PS_BYTES = BP * ROWB, CS_BYTES = BC * ROWB;
-    static constexpr int LDS_BYTES = 2 * (PS_BYTES + CS_BYTES);
-    static_assert(KC == 16 || KC == 32, "KC is one or two 16-deep MFMA steps");
-    static_assert(BP % (32 * WP) == 0 && BC % (32 * WC) == 0 && (BP * G) % THREADS == 0, "tile must split into 32x32 fragments and whole groups per thread");
-    static_assert((ROWB / 16) % 2 == 1, "odd slot stride: conflict-free ds_read_b128");
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-};
+// The tile (limb3.h): BP rows x BC output channels (= cout_pad), KC channels of one tap per chunk, WP x WC waves
+template <int BP, int BC, int KC, int WP, int WC>
+struct GTile : Limb3Tile<BP, BC, KC, WP, WC> {};
 
 template <class T>
 __global__ __launch_bounds__(T::THREADS) void k_spconv_gt(SpConvGTArgs a) {
@@ -83,18 +67,9 @@ __global__ __launch_bounds__(T::THREADS) void k_spconv_gt(SpConvGTArgs a) {
     const unsigned int row_bytes = (unsigned int)a.cin * 4u, wrow_bytes = (unsigned int)a.cin * 6u;
     const unsigned int tap_bytes = (unsigned int)a.cout_pad * wrow_bytes, nbr_tap_bytes = (unsigned int)a.cap * 4u;
 
-    // my pieces of a tap's weight slice: row n of the BC channels, 16-byte piece q of its KC / 8 groups
-    unsigned int cvoff[C], clds[C];
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        const int idx = tid + i * T::THREADS;
-        const int n = idx / (G * 3), q = idx % (G * 3);
-        const bool own = T::C_PIECES % T::THREADS == 0 || idx < T::C_PIECES;
-        cvoff[i] = own ? (unsigned int)n * wrow_bytes + (unsigned int)q * 16u : OOB_OFFSET;
-        clds[i] = own ? (unsigned int)(n * ROWB + q * 16) : 0xFFFFFFFFu;
-    }
-    // fragment addresses: my row of the wave's first fragment, limb group kh of a k-step
-    const int poff = (wp * PT * 32 + l31) * ROWB + kh * 48, coff = (wc * CT * 32 + l31) * ROWB + kh * 48;
+    unsigned int cvoff[C], clds[C];         // my pieces of a tap's weight slice: all BC = cout_pad rows of the tap
+    limb3_weight_pieces<T>(tid, 0, T::BC, wrow_bytes, cvoff, clds);
+    const int poff = limb3_frag_base<T>(wp, PT, lane), coff = limb3_frag_base<T>(wc, CT, lane);
 
     // XCD-aware persistent schedule (k_spconv_h's): workgroup b runs on XCD b % 8; tiles are dealt to the XCDs in runs of XRUN
     // consecutive (spatially sorted) row tiles, which share their gathered neighbour rows in one L2
@@ -112,12 +87,7 @@ __global__ __launch_bounds__(T::THREADS) void k_spconv_gt(SpConvGTArgs a) {
         if (a.kvol < 32) taps &= (1u << a.kvol) - 1u;
 
         f32x16 acc[CT][PT];
-#pragma unroll
-        for (int i = 0; i < CT; ++i)
-#pragma unroll
-            for (int j = 0; j < PT; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        limb3_zero<T>(acc);
 
         const int nchunks = __popc(taps) * kchunks;
         if (nchunks > 0) {
@@ -163,25 +133,7 @@ __global__ __launch_bounds__(T::THREADS) void k_spconv_gt(SpConvGTArgs a) {
 #pragma unroll
                 for (int i = 0; i < C; ++i) sw[i] = __builtin_amdgcn_raw_buffer_load_b128(crsrc, cvoff[i] == OOB_OFFSET ? OOB_OFFSET : cvoff[i] + cadd, 0, 0);
             };
-            auto store = [&](int buf) {
-                unsigned char *const Ps = Ps0 + buf * T::PS_BYTES, *const Cs = Cs0 + buf * T::CS_BYTES;
-#pragma unroll
-                for (int i = 0; i < P; ++i) {
-                    const v4u x0 = sp[i][0], x1 = sp[i][1];
-                    unsigned int h0, h1, h2, h3, m0, m1, m2, m3, l0, l1, l2, l3;
-                    split3x2(__uint_as_float(x0.x), __uint_as_float(x0.y), h0, m0, l0);
-                    split3x2(__uint_as_float(x0.z), __uint_as_float(x0.w), h1, m1, l1);
-                    split3x2(__uint_as_float(x1.x), __uint_as_float(x1.y), h2, m2, l2);
-                    split3x2(__uint_as_float(x1.z), __uint_as_float(x1.w), h3, m3, l3);
-                    v4u *const d = reinterpret_cast<v4u *>(Ps + plds[i]);
-                    d[0] = v4u{h0, h1, h2, h3};
-                    d[1] = v4u{m0, m1, m2, m3};
-                    d[2] = v4u{l0, l1, l2, l3};
-                }
-#pragma unroll
-                for (int i = 0; i < C; ++i)
-                    if (T::C_PIECES % T::THREADS == 0 || clds[i] != 0xFFFFFFFFu) *reinterpret_cast<v4u *>(Cs + clds[i]) = sw[i];
-            };
+            auto store = [&](int buf) { limb3_store<T>(Ps0 + buf * T::PS_BYTES, Cs0 + buf * T::CS_BYTES, sp, sw, plds, clds); };
 
             fetch_nbr();
             issue();                // chunk 0 (waits for its indices)
@@ -197,42 +149,7 @@ __global__ __launch_bounds__(T::THREADS) void k_spconv_gt(SpConvGTArgs a) {
                     advance();
                     fetch_nbr();    // indices of chunk c + 2
                 }
-                __builtin_amdgcn_sched_barrier(0);
-                const unsigned char *const Pc = Ps0 + cur * T::PS_BYTES + poff, *const Cc = Cs0 + cur * T::CS_BYTES + coff;
-#pragma unroll
-                for (int q = 0; q < T::KC / 16; ++q) {
-                    v4u xh[PT], xm[PT], xl[PT], wh[CT], wm[CT], wl[CT];
-#pragma unroll
-                    for (int pt = 0; pt < PT; ++pt) {
-                        const v4u *const s = reinterpret_cast<const v4u *>(Pc + pt * 32 * ROWB + q * 96);
-                        xh[pt] = s[0];
-                        xm[pt] = s[1];
-                        xl[pt] = s[2];
-                    }
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) {
-                        const v4u *const s = reinterpret_cast<const v4u *>(Cc + ct * 32 * ROWB + q * 96);
-                        wh[ct] = s[0];
-                        wm[ct] = s[1];
-                        wl[ct] = s[2];
-                    }
-                    // the six terms (weight limb . input limb), smallest first; term-major, so that with CT x PT > 1 consecutive MFMAs go to
-                    // different accumulators.  The two 32-channel instances have CT = PT = 1: their six MFMAs are one dependent chain per
-                    // wave, and only the other waves of the SIMD (4 workgroups per CU at KC = 16, 2 at KC = 32) fill its gaps
-                    auto term = [&](const v4u (&wa)[CT], const v4u (&xb)[PT]) {
-#pragma unroll
-                        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                            for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = MathBF16::mma(wa[ct], xb[pt], acc[ct][pt]);
-                    };
-                    term(wl, xh);
-                    term(wh, xl);
-                    term(wm, xm);
-                    term(wm, xh);
-                    term(wh, xm);
-                    term(wh, xh);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                limb3_mma<T>(Ps0 + cur * T::PS_BYTES + poff, Cs0 + cur * T::CS_BYTES + coff, acc);
                 if (has1) store(cur ^ 1);
                 __syncthreads();
             }

@@ -175,36 +175,19 @@ __global__ __launch_bounds__(C::THREADS) void k_spconv_xt(SpConvXWArgs a) {
                 x1 = *reinterpret_cast<const float4 *>(winb + (ra ^ 16u));
             }
             const unsigned char *const wt = wbuf + t * C::TAP_BYTES;
-            v4u wh[CT], wm[CT], wl[CT];
+            v4u w[3][CT], x[3];                              // limb operands: h, m, l
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                wh[ct] = *reinterpret_cast<const v4u *>(wt + ct * 32 * 96 + wslot_h);
-                wm[ct] = *reinterpret_cast<const v4u *>(wt + ct * 32 * 96 + wslot_m);
-                wl[ct] = *reinterpret_cast<const v4u *>(wt + ct * 32 * 96 + wslot_l);
+                w[0][ct] = *reinterpret_cast<const v4u *>(wt + ct * 32 * 96 + wslot_h);
+                w[1][ct] = *reinterpret_cast<const v4u *>(wt + ct * 32 * 96 + wslot_m);
+                w[2][ct] = *reinterpret_cast<const v4u *>(wt + ct * 32 * 96 + wslot_l);
             }
-            // the 8 channels of my half of the chunk -> three limb operands (two channels per word, the first in the low half)
-            v4u xh, xm, xl;
-            {
-                unsigned int h0, h1, h2, h3, m0, m1, m2, m3, l0, l1, l2, l3;
-                split3x2(x0.x, x0.y, h0, m0, l0);
-                split3x2(x0.z, x0.w, h1, m1, l1);
-                split3x2(x1.x, x1.y, h2, m2, l2);
-                split3x2(x1.z, x1.w, h3, m3, l3);
-                xh = v4u{h0, h1, h2, h3};
-                xm = v4u{m0, m1, m2, m3};
-                xl = v4u{l0, l1, l2, l3};
-            }
-            // the six terms (weight limb . input limb), smallest first; term-major, so consecutive MFMAs go to different accumulators
-            auto term = [&](const v4u (&wa)[CT], const v4u &xb) {
+            // the 8 channels of my half of the chunk, split here; term-major, so consecutive MFMAs go to different accumulators
+            split3x8(__builtin_bit_cast(v4u, x0), __builtin_bit_cast(v4u, x1), x[0], x[1], x[2]);
+            limb3_terms([&](auto wl, auto xl) {
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) acc[ct] = MathBF16::mma(wa[ct], xb, acc[ct]);
-            };
-            term(wl, xh);
-            term(wh, xl);
-            term(wm, xm);
-            term(wm, xh);
-            term(wh, xm);
-            term(wh, xh);
+                for (int ct = 0; ct < CT; ++ct) acc[ct] = MathBF16::mma(w[wl][ct], x[xl], acc[ct]);
+            });
         };
         // the next step's loads go out behind the first tap's MFMAs: no barrier is followed by address arithmetic and load issue in
         // front of a cold matrix pipe

@@ -143,7 +143,7 @@ def test_kernels_have_no_scratch_and_fit_lds(tmp_path):
         assert int(k['ScratchSize [bytes/lane]']) == 0 and int(k['VGPRs Spill']) == 0, k
         assert int(k['LDS Size [bytes/block]']) <= 160 * 1024, k
         assert int(k['VGPRs']) + int(k['AGPRs']) <= 256, k
-    txt = open(SRC).read()
+    txt = open(os.path.join(os.path.dirname(SRC), 'limb3.h')).read()           # the tile C2TTile derives from
     assert 'static_assert(LDS_BYTES <= 160 * 1024' in txt
     for n in names:
         bp, bc, kc = (int(v) for v in re.match(r'k_conv2d_t<(\d+)x(\d+)x(\d+)>', n).groups())

@@ -64,7 +64,7 @@ def test_kernels_have_no_scratch_and_fit_lds(tmp_path):
         print(k)
         assert int(k['ScratchSize [bytes/lane]']) == 0 and int(k['VGPRs Spill']) == 0 and int(k['SGPRs Spill']) == 0, k
         assert int(k['LDS Size [bytes/block]']) <= 160 * 1024, k
-    txt = open(src).read()
+    txt = open(os.path.join(os.path.dirname(src), 'limb3.h')).read()           # the tile GTile derives from
     assert 'static_assert(LDS_BYTES <= 160 * 1024' in txt
     # rows of KC / 8 limb groups + 16 bytes: the dynamic LDS of each instance, restated
     for bp, bc, kc in tiles:
