@@ -268,6 +268,19 @@ def set_dense_engine(model, f32_engine, f32_generic=None):
     return model
 
 
+def set_linear_engine(model, f32_engine):
+    """Engine of the linear layers of a detector's second stage (the PDV head's MLP / FC stacks, attention projections and feed-forward
+    block) in the exact-fp32 mode: 'mfma32' (default: dz_linear_forward on the fp32 matrix cores) or 'bf16x3' (csrc/linear_t.hip, the
+    three-limb arithmetic of set_dense_engine) for the layers that engine covers.  Set on every module of the model that runs linears;
+    the split math modes ignore it.  A refused value changes nothing."""
+    if f32_engine not in ops.LINEAR_F32_ENGINES:
+        raise DetZeroHipError('unknown fp32 linear engine %r (%s)' % (f32_engine, ' | '.join(ops.LINEAR_F32_ENGINES)))
+    for mod in model.modules():
+        if hasattr(mod, 'set_linear_engine') and hasattr(mod, 'stack_math'):
+            mod.set_linear_engine(f32_engine)
+    return model
+
+
 # development switch: DZ_TUNE_EAGER_PYRAMID=1 builds the whole index pyramid before the first convolution (the r01c-r03f schedule)
 STAGGERED_PYRAMID = not os.environ.get('DZ_TUNE_EAGER_PYRAMID')
 

@@ -1,10 +1,10 @@
-// The three-limb arithmetic of the exact-fp32 mode's bf16x3 engines (conv3x3_t.hip, conv2d_t.hip, sparse_conv_xt.hip,
+// The three-limb arithmetic of the exact-fp32 mode's bf16x3 engines (conv3x3_t.hip, conv2d_t.hip, linear_t.hip, sparse_conv_xt.hip,
 // sparse_conv_gt.hip, sparse_conv_wt.hip): any finite fp32 x is exactly
 //        h = rn(x),   m = rn(x - h),   l = x - h - m                      (three bf16 values, 8 + 8 + 8 = 24 significant bits)
 // with x clamped to +-bf16-max (0x7F7F) before the FIRST rounding only (the rule of MathF16::split): a finite fp32 near the top of
 // the range gets no inf limb, the rest goes to m and l, and the sum stays exact.  The host mirror is ops.limb3_pack.
-// Below the split: the order of the six limb products (limb3_terms) and the LDS tile of limb rows that k_spconv_gt and k_conv2d_t
-// stage their chunks into and multiply from (Limb3Tile and the limb3_* function templates on it).
+// Below the split: the order of the six limb products (limb3_terms) and the LDS tile of limb rows that k_spconv_gt, k_conv2d_t and
+// k_linear_t stage their chunks into and multiply from (Limb3Tile and the limb3_* function templates on it).
 #pragma once
 
 #include <type_traits>
@@ -57,7 +57,7 @@ __device__ __forceinline__ void limb3_terms(F &&term) {
     term(H, H);
 }
 
-// ---- the limb tile of k_spconv_gt / k_conv2d_t: BP rows (MFMA N side) x BC output channels (MFMA M side), KC channels of one tap per
+// ---- the limb tile of k_spconv_gt / k_conv2d_t / k_linear_t: BP rows (MFMA N side) x BC output channels (MFMA M side), KC channels of one tap per
 // chunk, WP x WC waves.  An LDS row is KC / 8 groups of 48 bytes (16 B of h, 16 of m, 16 of l of 8 channels: the group layout of
 // conv3x3_t.hip and of the packed weights) + 16 bytes of padding; two buffers of BP input rows, two of BC weight rows.
 template <int BP_, int BC_, int KC_, int WP_, int WC_>

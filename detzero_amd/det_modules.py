@@ -132,6 +132,7 @@ class _Cached(nn.Module):
         self.math = 0       # ops.MATH_MODES: 0 = fp32 MFMA, 1 = fp16-pair split, 2 = bf16-pair split, 3 = fp16 pairs with one product (csrc/hgemm.h)
         self.f32_dense_engine = 'mfma32'    # BaseBEVBackbone / CenterHead: set_dense_engine
         self.f32_dense_generic = 'mfma32'   # ... and its f32_generic (csrc/conv2d_t.hip; no environment knob yet: DESIGN.md 2a-quater)
+        self.f32_linear_engine = 'mfma32'   # refiner modules / PDV head: set_linear_engine (csrc/linear_t.hip; Python-only like f32_generic)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._weights_loaded())
 
     def invalidate(self):
@@ -231,6 +232,16 @@ class _Cached(nn.Module):
         self.f32_dense_engine = f32_engine
         if f32_generic is not None:
             self.f32_dense_generic = f32_generic
+        CACHE_GEN[0] += 1
+        return self
+
+    def set_linear_engine(self, name):
+        """Engine of the linear layers (Conv1d / Conv2d(1x1) / Linear stacks, attention projections, FFNs, FC stacks) in the exact-fp32
+        mode: 'mfma32' (dz_linear_forward, the default) or 'bf16x3' (three bf16 limbs per operand, csrc/linear_t.hip) for the layers
+        that engine covers.  The split modes ignore it.  A refused name changes nothing."""
+        if name not in ops.LINEAR_F32_ENGINES:
+            raise DetZeroHipError('unknown fp32 linear engine %r (%s)' % (name, ' | '.join(ops.LINEAR_F32_ENGINES)))
+        self.f32_linear_engine = name
         CACHE_GEN[0] += 1
         return self
 

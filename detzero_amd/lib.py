@@ -248,6 +248,10 @@ _SIGS = {
                             c_void_p]),
     'dz_linear_forward': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   c_int, c_int, c_void_p, c_int, c_void_p]),
+    'dz_linear_limb3_forward': (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_int, c_void_p, c_int, ctypes.c_long, c_void_p]),
+    'dz_linear_limb3_supported': (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    'dz_linear_limb3_variant': (ctypes.c_char_p, [c_int, c_int]),
     'dz_group_max': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'dz_rows_all_zero': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'dz_add_layernorm_combine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

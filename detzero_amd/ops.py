@@ -921,14 +921,36 @@ def conv2d(desc_kwargs, math=0, out_f32=False, tiles=None, f32_engine=None, f32_
     PROFILER.wrap(name, flops, nbytes, launch)
 
 
-def linear(x, w, scale, shift, relu, cout, out=None, group_shift=None, group_rows=0):
-    """x (rows, cin) @ w (cin, cout_pad) -> (rows, cout); optional per-row-group pre-activation addend."""
+LINEAR_F32_ENGINES = ('mfma32', 'bf16x3')
+
+
+def linear_limb3_supported(cin, x_stride, cout, cout_pad, y_stride):
+    """Whether the bf16x3 engine of the f32 mode's linear layers (dz_linear_limb3_forward, csrc/linear_t.hip) takes a layer of these
+    sizes.  Host only."""
+    return bool(L.load().dz_linear_limb3_supported(int(cin), int(x_stride), int(cout), int(cout_pad), int(y_stride)))
+
+
+def linear(x, w, scale, shift, relu, cout, out=None, group_shift=None, group_rows=0, f32_engine=None, w_limb=None, max_launch_rows=0):
+    """x (rows, cin) @ w (cin, cout_pad) -> (rows, cout); optional per-row-group pre-activation addend.
+    f32_engine='bf16x3': the three-limb kernel of csrc/linear_t.hip with w_limb = pack_weight_limb3_generic(w[None]) (w itself only
+    gives cout_pad); a layer it does not cover is an error.  max_launch_rows (that engine only): cap on the rows of one launch."""
     lib = L.load()
+    if f32_engine not in (None,) + LINEAR_F32_ENGINES:
+        raise L.DetZeroHipError('unknown fp32 linear engine %r (%s)' % (f32_engine, ' | '.join(LINEAR_F32_ENGINES)))
     L.require_cuda(x, w, scale, shift, group_shift)
     rows, cin = x.shape
     cout_pad = w.shape[1]
     if out is None:
         out = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
+    if f32_engine == 'bf16x3':
+        if w_limb is None:
+            raise L.DetZeroHipError('linear: f32_engine bf16x3 needs w_limb (pack_weight_limb3_generic of the weights)')
+        L.require_cuda(w_limb)
+        rc = lib.dz_linear_limb3_forward(L.ptr(x), rows, cin, x.stride(0), L.ptr(w_limb), cout, cout_pad, L.ptr(scale), L.ptr(shift),
+                                         L.ptr(group_shift), int(group_rows), 1 if relu else 0, L.ptr(out), out.stride(0),
+                                         int(max_launch_rows), L.stream())
+        L.check(rc, 'dz_linear_limb3_forward')
+        return out
     rc = lib.dz_linear_forward(L.ptr(x), rows, cin, x.stride(0), L.ptr(w), cout, cout_pad, L.ptr(scale),
                                L.ptr(shift), L.ptr(group_shift), int(group_rows), 1 if relu else 0, L.ptr(out),
                                out.stride(0), L.stream())

@@ -30,7 +30,7 @@ from . import iou3d_nms_utils, ops
 from . import lib as L
 from .det_modules import _Cached
 from .lib import DetZeroHipError
-from .refine_modules import _mha_plan, _pad16, _run_stack, _stack_plan
+from .refine_modules import _linear, _mha_plan, _pad16, _run_stack, _stack_plan
 
 
 # ================================================================================================
@@ -552,7 +552,7 @@ class PDVHead(_Cached):
                     pooled.append(sa_pool(new_xyz, per_batch, xyz, feats, level, idx, cnt, stack))
                 else:
                     rows = group_features(new_xyz, per_batch, xyz, feats, level, idx, cnt, p['pool'][k][s]['stride'])
-                    out, _ = _run_stack(rows, stack, math=self.stack_math())
+                    out, _ = _run_stack(rows, stack, math=self.stack_math(), engine=self.f32_linear_engine)
                     pooled.append(ops.group_max(out, new_xyz.shape[0], nsample))
                 balls.append(idx)
         in_place = wide is not None and len(placed) == len(pooled)          # every branch wrote its column block of `wide`
@@ -589,21 +589,22 @@ class PDVHead(_Cached):
                 L.load().dz_self_attention_split_supported(l, e) and self._fused_encoder_ok(p, positional_input)):
             return self._attention_fused(p, sm, point_features, positional_input, key_padding_mask, empty, add_pos, r, l, e, pair16_ok)
         pos_rows = torch.nn.functional.pad(pos_in, (0, 16 - pos_in.shape[1]))      # (one launch: zero-padded to the stack's input width)
-        pos, _ = _run_stack(pos_rows, p['pos'], math=self.stack_math())
+        pos, _ = _run_stack(pos_rows, p['pos'], math=self.stack_math(), engine=self.f32_linear_engine)
         # feats + pos where add_pos, feats elsewhere, in one pass: pos * 1.0 and feats + 0.0 are exact (the encodings are finite)
         src = torch.addcmul(feats, pos, add_pos.reshape(r * l, 1).to(feats.dtype))
         if FOLDED_ATTENTION[0] and sm in (1, 2) and m['heads'] == 1 and L.load().dz_self_attention_split_supported(l, e) and e % 32 == 0:
             return self._attention_split(p, sm, point_features, src, key_padding_mask, empty, r, l, e, combine)
-        q = ops.linear(src, m['wq'], m['one'], m['bq'], False, e)
-        k = ops.linear(src, m['wk'], m['one'], m['bk'], False, e)
-        v = ops.linear(src, m['wv'], m['one'], m['bv'], False, e)
+        lin = dict(math=sm, engine=self.f32_linear_engine)      # the head's own math and f32 linear engine, as for its stacks
+        q = _linear(src, m, 'wq', m['one'], m['bq'], False, e, **lin)
+        k = _linear(src, m, 'wk', m['one'], m['bk'], False, e, **lin)
+        v = _linear(src, m, 'wv', m['one'], m['bv'], False, e, **lin)
         mask = key_padding_mask & (~empty)[:, None]                        # (an all-masked row would divide 0 by 0; its result is discarded)
         o = attention_single_head(q.view(r, l, e), k.view(r, l, e), v.view(r, l, e), mask, float(e) ** -0.5)
-        o = ops.linear(o.view(r * l, e), m['wo'], m['one'], m['bo'], False, e)
+        o = _linear(o.view(r * l, e), m, 'wo', m['one'], m['bo'], False, e, **lin)
         enc = p['enc']
         x = ops.add_layernorm(src, o, *enc['ln'][0])
-        h = ops.linear(x, enc['w1'], enc['one1'], enc['b1'], True, enc['w1'].shape[1])
-        y = ops.linear(h, enc['w2'], enc['one2'], enc['b2'], False, enc['w2'].shape[1])
+        h = _linear(x, enc, 'w1', enc['one1'], enc['b1'], True, enc['w1'].shape[1], **lin)
+        y = _linear(h, enc, 'w2', enc['one2'], enc['b2'], False, enc['w2'].shape[1], **lin)
         y = ops.add_layernorm(x, y, *enc['ln'][1])
         out = torch.where(empty[:, None, None], point_features, y.view(r, l, e))
         return point_features + out if combine else out
@@ -709,9 +710,9 @@ class PDVHead(_Cached):
             att = lambda: ops.pair16_to_f32(attp, sm).view(pooled.shape)      # noqa: E731  (fp32 view for whoever reads forward_ret_dict)
         else:
             rows = att.reshape(att.shape[0], -1).contiguous()               # (RoI, 216 * C): the shared FC's columns were permuted to match
-            shared, _ = _run_stack(rows, p['shared'], math=self.stack_math())
-        rcnn_reg, _ = _run_stack(shared, p['reg'], math=self.stack_math())
-        rcnn_cls, _ = _run_stack(shared, p['cls'], math=self.stack_math())
+            shared, _ = _run_stack(rows, p['shared'], math=self.stack_math(), engine=self.f32_linear_engine)
+        rcnn_reg, _ = _run_stack(shared, p['reg'], math=self.stack_math(), engine=self.f32_linear_engine)
+        rcnn_cls, _ = _run_stack(shared, p['cls'], math=self.stack_math(), engine=self.f32_linear_engine)
         cls_preds, box_preds = self.generate_predicted_boxes(batch_dict['batch_size'], batch_dict['rois'], rcnn_cls.contiguous(), rcnn_reg.contiguous())
         batch_dict['batch_cls_preds'], batch_dict['batch_box_preds'] = cls_preds, box_preds
         batch_dict['cls_preds_normalized'] = False

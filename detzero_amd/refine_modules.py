@@ -9,7 +9,8 @@ Same constructor arguments, ``forward(data_dict)`` keys and ``state_dict()`` nam
 reference's own manifest in tests/golden/refine_golden.npz).  Inference only.
 
 Execution (all tensors channel-last, one row per point / query):
-  * every Conv1d/Conv2d(1x1)/Linear + BatchNorm(eval) + ReLU is one ``dz_linear_forward`` (fp32 MFMA, folded BN);
+  * every Conv1d/Conv2d(1x1)/Linear + BatchNorm(eval) + ReLU is one ``dz_linear_forward`` (fp32 MFMA, folded BN) - or, with
+    ``set_linear_engine('bf16x3')`` in f32 mode, one ``dz_linear_limb3_forward`` (three bf16 limbs) where that engine covers the layer;
   * ``torch.max`` over points = ``dz_group_max``; the ``repeat`` + ``cat`` of the pooled feature with the
     per-point feature is never materialised: its product with the first MLP layer is a per-object vector that
     enters the GEMM epilogue as a row-group addend;
@@ -208,25 +209,58 @@ def _stack_plan(seq, cin_pad=None):
 # matrix cores (csrc/hgemm.h) - set by the model's forward from its `math` (set_math).  Only stacks with many
 # rows switch (the conversion pass has to pay), and only when every hidden width is a multiple of 32.
 _REFINE_MATH = [0]
+# Engine of the linear layers in the exact-fp32 mode: 'mfma32' (dz_linear_forward, default) or 'bf16x3' (dz_linear_limb3_forward,
+# csrc/linear_t.hip) - set next to _REFINE_MATH by the model's forward from its `f32_linear_engine` (set_linear_engine).
+_REFINE_LINEAR = ['mfma32']
 SPLIT_MIN_ROWS = 2048
 
 
 @contextlib.contextmanager
-def _math_mode(m):
-    prev = _REFINE_MATH[0]
-    _REFINE_MATH[0] = int(m)
+def _math_mode(m, linear_engine='mfma32'):
+    prev = _REFINE_MATH[0], _REFINE_LINEAR[0]
+    _REFINE_MATH[0], _REFINE_LINEAR[0] = int(m), linear_engine
     try:
         yield
     finally:
-        _REFINE_MATH[0] = prev
+        _REFINE_MATH[0], _REFINE_LINEAR[0] = prev
 
 
 def _with_math(fn):
-    """Model forward under the module's arithmetic (`set_math('f16x2')`; default fp32)."""
+    """Model forward under the module's arithmetic (`set_math('f16x2')`; default fp32) and its f32 linear engine."""
     def wrapper(self, data_dict):
-        with _math_mode(self.math):
+        with _math_mode(self.math, getattr(self, 'f32_linear_engine', 'mfma32')):
             return fn(self, data_dict)
     return wrapper
+
+
+def _limb3_ok(x, w, cout, math, engine):
+    """The routing predicate of `_linear`: the module's math is 0, its switch says 'bf16x3', and the engine covers the layer."""
+    return (not math and engine == 'bf16x3' and x.shape[1] == w.shape[0] and x.stride(1) == 1 and
+            ops.linear_limb3_supported(x.shape[1], x.stride(0), cout, w.shape[1], cout))
+
+
+def _limb_w(holder, key='w'):
+    """Three-limb weights of a plan entry for dz_linear_limb3_forward, packed once and cached beside the fp32 ones (like `_split_w`);
+    they go with the plan when the weights change."""
+    ck = '%s_limb3' % key
+    if ck not in holder:
+        holder[ck] = ops.pack_weight_limb3_generic(holder[key][None])
+    return holder[ck]
+
+
+def _linear(x, holder, key, scale, shift, relu, cout, group_shift=None, group_rows=0, math=None, engine=None):
+    """The one place an fp32-rows linear layer of the refiner and of the PDV head is launched from: x @ holder[key] (a plan entry's
+    (cin, cout_pad) fp32 weights).  math / engine: None = the running model's (_REFINE_MATH / _REFINE_LINEAR); the PDV head passes its
+    own.  The layer runs on the bf16x3 engine exactly when `_limb3_ok`; otherwise the dz_linear_forward call is what it always was."""
+    m = _REFINE_MATH[0] if math is None else math
+    eng = _REFINE_LINEAR[0] if engine is None else engine
+    w = holder[key]
+    if _limb3_ok(x, w, cout, m, eng):
+        return ops.linear(x, w, scale, shift, relu, cout, group_shift=group_shift, group_rows=group_rows, f32_engine='bf16x3',
+                          w_limb=_limb_w(holder, key))
+    if group_shift is None:
+        return ops.linear(x, w, scale, shift, relu, cout)
+    return ops.linear(x, w, scale, shift, relu, cout, group_shift=group_shift, group_rows=group_rows)
 
 
 def _r32(n):
@@ -298,8 +332,8 @@ def _run_stack_split(xp, layers, keep_pair=False, math=None, gmax=None, tap=Fals
     return xp, outs
 
 
-def _run_stack(x, layers, upto=None, math=None, gmax=None):
-    """math: None = the refiner's global mode (set_refine_math); an explicit mode (0 = fp32 engine, 1 / 2 = split pairs) pins the
+def _run_stack(x, layers, upto=None, math=None, gmax=None, engine=None):
+    """engine: the f32 linear engine, None = the running refiner's (the PDV head passes its own next to its math).  math: None = the refiner's global mode (set_refine_math); an explicit mode (0 = fp32 engine, 1 / 2 = split pairs) pins the
     stack's arithmetic whatever the refiner is set to (the PDV head passes its own)."""
     layers = layers if upto is None else layers[:upto]
     if _splittable(layers, x.shape[0], math):
@@ -310,7 +344,7 @@ def _run_stack(x, layers, upto=None, math=None, gmax=None):
         if ops.linear_splitk_ok(x.shape[0], x.shape[1]) and x.shape[1] == l['w'].shape[0]:       # a few rows, a very long input
             x = ops.linear_splitk(x, l['w'], l['scale'], l['shift'], l['relu'], l['cout'])
         else:
-            x = ops.linear(x, l['w'], l['scale'], l['shift'], l['relu'], l['cout'])
+            x = _linear(x, l, 'w', l['scale'], l['shift'], l['relu'], l['cout'], math=math, engine=engine)
         outs.append(x)
     if gmax is not None:
         x = ops.group_max(x, gmax[0], gmax[1])
@@ -340,15 +374,15 @@ def _mha_forward(p, q_rows, k_rows, v_rows, b, lq, lk, key_padding_mask, kv=None
     """rows are (B*L, E) channel-last.  multi_head_attention.py:199-288.  kv: the key / value projections of the memory when the
     caller already has them (dz_mlp_chain_forward produces them with the memory rows)."""
     e = p['e']
-    q = ops.linear(q_rows, p['wq'], p['one'], p['bq'], False, e)
+    q = _linear(q_rows, p, 'wq', p['one'], p['bq'], False, e)
     am = _REFINE_MATH[0] if (SPLIT_ATTENTION[0] and lk >= SPLIT_ATTN_MIN_KEYS and _REFINE_MATH[0] in (1, 2)) else 0   # long key lists only
     if kv is not None:
         o = ops.mha_core(q.view(b, lq, e), kv[0].view(b, lk, e), kv[1].view(b, lk, e), key_padding_mask, p['heads'], p['scale'], math=am)
-        return ops.linear(o.view(b * lq, e), p['wo'], p['one'], p['bo'], False, e)
+        return _linear(o.view(b * lq, e), p, 'wo', p['one'], p['bo'], False, e)
     if FOLDED_XATTN[0] and k_rows is v_rows and lk >= FOLD_MIN_KEYS and ops.xattn_folded_supported(lq, e, p['heads']):
         # a few queries over a long memory (GRM: 3 x 4096): the key / value projections fold into the queries, the memory is read once
         o = ops.xattn_folded(q.view(b, lq, e), k_rows.view(b, lk, e), key_padding_mask, p['wk_oi'], p['wv'], p['bv'], p['heads'], p['scale'])
-        return ops.linear(o.view(b * lq, e), p['wo'], p['one'], p['bo'], False, e)
+        return _linear(o.view(b * lq, e), p, 'wo', p['one'], p['bo'], False, e)
     m = _REFINE_MATH[0]
     if m and k_rows is v_rows and k_rows.shape[0] >= SPLIT_MIN_ROWS and e % 32 == 0:
         # key / value projections of a long memory: one conversion of the memory rows, two split GEMMs
@@ -359,10 +393,10 @@ def _mha_forward(p, q_rows, k_rows, v_rows, b, lq, lk, key_padding_mask, kv=None
         k = ops.linear_split(mp, wk, p['one'], p['bk'], False, e, m, out_f32=True)
         v = ops.linear_split(mp, wv, p['one'], p['bv'], False, e, m, out_f32=True)
     else:
-        k = ops.linear(k_rows, p['wk'], p['one'], p['bk'], False, e)
-        v = ops.linear(v_rows, p['wv'], p['one'], p['bv'], False, e)
+        k = _linear(k_rows, p, 'wk', p['one'], p['bk'], False, e)
+        v = _linear(v_rows, p, 'wv', p['one'], p['bv'], False, e)
     o = ops.mha_core(q.view(b, lq, e), k.view(b, lk, e), v.view(b, lk, e), key_padding_mask, p['heads'], p['scale'], math=am)
-    return ops.linear(o.view(b * lq, e), p['wo'], p['one'], p['bo'], False, e)
+    return _linear(o.view(b * lq, e), p, 'wo', p['one'], p['bo'], False, e)
 
 
 def decoder_layer_plan(layer):
@@ -391,8 +425,8 @@ def decoder_layer_forward(p, query, memory, query_pos, b, lq, lk, sa_mask=None, 
     q2 = _mha_forward(p['ca'], qp, memory, memory, b, lq, lk, ca_mask, kv=memory_kv)
     g, be, eps = p['ln'][1]
     query = ops.add_layernorm(query, q2, g, be, eps)
-    h = ops.linear(query, p['w1'], p['one1'], p['b1'], True, p['w1'].shape[1])
-    q2 = ops.linear(h, p['w2'], p['one2'], p['b2'], False, p['w2'].shape[1])
+    h = _linear(query, p, 'w1', p['one1'], p['b1'], True, p['w1'].shape[1])
+    q2 = _linear(h, p, 'w2', p['one2'], p['b2'], False, p['w2'].shape[1])
     g, be, eps = p['ln'][2]
     return ops.add_layernorm(query, q2, g, be, eps)
 
@@ -431,6 +465,7 @@ class _PointNetPlan:
         else:                                       # GRM: cat([intermediate, pooled])
             w_mid, w_pool = w[:c_mid], w[c_mid:]
         self.w_pool = w_pool.contiguous()
+        self.pool = {'w': self.w_pool}              # the pooled feature's product as a plan entry (`_linear` caches its limb weights here)
         self.mlp = _stack_plan(mlp)
         self.mlp[0]['w'] = w_mid.contiguous()
         self.ones = torch.ones(w.shape[1], device=w.device)
@@ -454,7 +489,7 @@ class _PointNetPlan:
             m = _REFINE_MATH[0]
             # max over the points fused; the tapped layer pair16; 16- / 32-column fp32 rows go in as they are
             pooled, outs = _run_stack_split(pts_rows.contiguous(), self.enc, gmax=(groups, length), tap=True, x_f32=True)
-            gshift = ops.linear(pooled, self.w_pool, self.ones, self.zeros, False, self.w_pool.shape[1])
+            gshift = _linear(pooled, self.pool, 'w', self.ones, self.zeros, False, self.w_pool.shape[1])
             l0 = self.mlp[0]
             w0 = _split_w(l0, m)
             if outs[1] is not None and self._chain_ok(pts_rows.shape[0], length, m):
@@ -477,9 +512,9 @@ class _PointNetPlan:
         x = _pad_cols(pts_rows, self.cin_pad)
         feat, outs = _run_stack(x, self.enc)
         pooled = ops.group_max(feat, groups, length)                               # (G, Cpool)
-        gshift = ops.linear(pooled, self.w_pool, self.ones, self.zeros, False, self.w_pool.shape[1])   # (G, C1) pre-BN addend
+        gshift = _linear(pooled, self.pool, 'w', self.ones, self.zeros, False, self.w_pool.shape[1])   # (G, C1) pre-BN addend
         l0 = self.mlp[0]
-        y = ops.linear(outs[1], l0['w'], l0['scale'], l0['shift'], l0['relu'], l0['cout'], group_shift=gshift, group_rows=length)
+        y = _linear(outs[1], l0, 'w', l0['scale'], l0['shift'], l0['relu'], l0['cout'], group_shift=gshift, group_rows=length)
         y, _ = _run_stack(y, self.mlp[1:])
         return y
 
@@ -690,9 +725,9 @@ class ConfidencePointnet(_Cached):
         box, outs = _run_stack(box, p['boxes'])
         tapped = outs[1]                                                                     # pts_mlp[5]
         pooled = ops.group_max(box, b, nb)                                                   # (B, E)
-        gshift = ops.linear(pooled, p['reg_w_pool'], p['ones'], p['zeros'], False, p['reg_w_pool'].shape[1])
+        gshift = _linear(pooled, p, 'reg_w_pool', p['ones'], p['zeros'], False, p['reg_w_pool'].shape[1])
         l0 = p['reg'][0]
-        y = ops.linear(tapped, l0['w'], l0['scale'], l0['shift'], l0['relu'], l0['cout'], group_shift=gshift, group_rows=nb)
+        y = _linear(tapped, l0, 'w', l0['scale'], l0['shift'], l0['relu'], l0['cout'], group_shift=gshift, group_rows=nb)
         y, _ = _run_stack(y, p['reg'][1:])
         preds = {k: torch.sigmoid(_run_stack(y, layers)[0].view(b, nb, -1)) for k, layers in p['heads'].items()}
         self.preds_dict = preds

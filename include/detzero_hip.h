@@ -705,6 +705,32 @@ int dz_mha_core_split(const float *q, const float *k, const float *v, const uint
 int dz_linear_forward(const float *x, int rows, int cin, int x_stride, const float *w, int cout, int cout_pad,
                       const float *scale, const float *shift, const float *group_shift, int group_rows, int relu,
                       float *y, int y_stride, void *stream);
+/* Opt-in engine of the exact-fp32 mode for these linear layers (csrc/linear_t.hip): dz_linear_forward's row GEMM in the three-limb
+ * arithmetic of dz_conv3x3_limb3_forward above - fp32 rows in and out, every operand as three exact bf16 limbs h + m + l, a product
+ * as the six terms l.h  h.l  m.m  m.h  h.m  h.h (weight limb . input limb, smallest first) on the bf16 matrix pipe; the dropped terms
+ * m.l + l.m + l.l are at most 2^-26 of |x.w|.
+ *   x (rows, x_stride) fp32, columns [0, cin) read, cin .. x_stride - 1 never; w_limb = (round_up(cout_pad, 32), cin / 8, 3, 8) bf16:
+ *   ops.pack_weight_limb3_generic of the (1, cin, cout_pad) weights of dz_linear_forward (zero rows behind cout_pad).
+ *   y = relu?(fma(acc + group_shift[row / group_rows][col], scale[col], shift[col])): group_shift (row groups, cout_pad) fp32 or NULL
+ *   goes in once, before scale / shift; group_rows < 1 means 1; the last group may be ragged; scale / shift NULL = 1 / 0.
+ * Accumulation order per output element: 16-channel k-steps ascending, the six terms in the order above, one accumulator - whatever
+ * the tile or the launch split; no atomics, two launches agree bit for bit.
+ * Write contract: columns [0, cout) of rows [0, rows) only (float4 where y_stride % 4 == 0 and y is 16-byte aligned, word by word
+ * otherwise); columns cout .. y_stride - 1 and everything behind the last row keep their contents.
+ * Rows beyond the 2 GiB buffer window run as several launches over row chunks, aligned to group_rows when there is an addend.
+ * max_launch_rows: 0 = the window alone; n > 0 additionally caps the rows of a launch (rounded down to a multiple of group_rows with
+ * an addend) - the result does not depend on it.
+ * dz_linear_limb3_supported (host only, no GPU needed) is 1 exactly for cin % 32 == 0, cout_pad % 16 == 0, 1 <= cout <= cout_pad,
+ * x_stride >= cin, x_stride % 4 == 0, y_stride >= cout and weights below 2 GiB; dz_linear_limb3_forward returns DZ_ERR_UNSUPPORTED,
+ * naming the field, for anything else, for one row group beyond the window and for a max_launch_rows below group_rows - before any
+ * launch.  Null x / y / w_limb, negative rows or max_launch_rows: DZ_ERR_INVALID.  rows == 0: DZ_OK, no launch.
+ * dz_linear_limb3_variant: "k_linear_t<128x128x16>" (cout_pad % 128 == 0), "k_linear_t<128x64x32>" (other cout_pad above 32),
+ * "k_linear_t<128x32x32>" (cout_pad 16 or 32) or "none" (cin or cout_pad the engine does not cover). */
+int dz_linear_limb3_forward(const float *x, long rows, int cin, int x_stride, const float *w_limb, int cout, int cout_pad,
+                            const float *scale, const float *shift, const float *group_shift, int group_rows, int relu,
+                            float *y, int y_stride, long max_launch_rows, void *stream);
+int dz_linear_limb3_supported(int cin, int x_stride, int cout, int cout_pad, int y_stride);
+const char *dz_linear_limb3_variant(int cin, int cout_pad);
 
 /* dz_linear_forward for a few rows against a very long input (the PDV head's first FC layer, pdv_head.py:154-172: 41 472 -> 256 for
  * some hundred RoIs): the input channels are cut into `splits` (1..8, cin % (splits * 32) == 0) groups that run side by side (one

@@ -29,8 +29,9 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps
 
 
-def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True):
-    """Refiner throughput on `dev` -> dict (also the `refine` leg of bench.py: BASELINE configs[3])."""
+def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True, *, f32_linear=None):
+    """Refiner throughput on `dev` -> dict (also the `refine` leg of bench.py: BASELINE configs[3]).  f32_linear: None = the modules'
+    default, or a name for set_linear_engine ('mfma32' | 'bf16x3'; it matters in math 'f32' only) - reported as 'f32_linear'."""
     from detzero_amd import ops
     from detzero_amd.refine_modules import GeometryTransformer, PositionTransformer
     from detzero_amd.synth import synth_boxes, synth_state_dict, synth_waymo_frame
@@ -46,6 +47,8 @@ def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True):
     grm = GeometryTransformer(GCFG, 11, 4).eval()
     grm.load_state_dict(synth_state_dict({k: tuple(v.shape) for k, v in grm.state_dict().items()}, 1))
     grm = grm.to(dev).set_math(math)
+    if f32_linear is not None:
+        out['f32_linear'] = grm.set_linear_engine(f32_linear).f32_linear_engine
     gd = {'geo_memory_points': torch.randn((b, 4096, 11), generator=gen).to(dev),
           'geo_query_points': torch.randn((b, 3, 256, 4), generator=gen).to(dev),
           'geo_query_boxes': torch.randn((b, 3, 7), generator=gen).to(dev), 'geo_query_num': torch.full((b,), 3)}
@@ -76,6 +79,8 @@ def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True):
     prm = PositionTransformer(PCFG, 32, 32).eval()
     prm.load_state_dict(synth_state_dict({k: tuple(v.shape) for k, v in prm.state_dict().items()}, 2))
     prm = prm.to(dev).set_math(math)
+    if f32_linear is not None:
+        prm.set_linear_engine(f32_linear)
     bp = min(b, 96)
     pchunks = max(objects // bp, 1)
     lens = torch.randint(5, 201, (bp,), generator=gen)
@@ -135,8 +140,9 @@ def main():
     ap.add_argument('--chunk', type=int, default=128, help='objects per forward (reference BATCH_SIZE_PER_GPU 128 / 96)')
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--math', default='f32', choices=['f32', 'f16x2', 'bf16x2'], help="arithmetic of the big MLP stacks (set_math)")
+    ap.add_argument('--f32-linear', default=None, choices=['mfma32', 'bf16x3'], help="engine of the f32 mode's linear layers (set_linear_engine)")
     args = ap.parse_args()
-    print(json.dumps(measure(torch.device('cuda', 0), args.objects, args.chunk, args.steps, args.math)))
+    print(json.dumps(measure(torch.device('cuda', 0), args.objects, args.chunk, args.steps, args.math, f32_linear=args.f32_linear)))
 
 
 if __name__ == '__main__':

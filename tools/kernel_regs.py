@@ -2,6 +2,7 @@
 
     python tools/kernel_regs.py detzero_amd/csrc/sparse_conv_h.hip [filter]
     python tools/kernel_regs.py detzero_amd/csrc/conv2d_t.hip k_conv2d_t        (the three instances of the generic bf16x3 dense engine)
+    python tools/kernel_regs.py detzero_amd/csrc/linear_t.hip k_linear_t        (... and of the bf16x3 linear engine)
 """
 import os
 import re
