@@ -133,6 +133,7 @@ class _Cached(nn.Module):
         self.f32_dense_engine = 'mfma32'    # BaseBEVBackbone / CenterHead: set_dense_engine
         self.f32_dense_generic = 'mfma32'   # ... and its f32_generic (csrc/conv2d_t.hip; no environment knob yet: DESIGN.md 2a-quater)
         self.f32_linear_engine = 'mfma32'   # refiner modules / PDV head: set_linear_engine (csrc/linear_t.hip; Python-only like f32_generic)
+        self.f32_attention_engine = 'mfma32'    # refiner modules: set_attention_engine (csrc/mha_t.hip; Python-only like the linear engine)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._weights_loaded())
 
     def invalidate(self):
@@ -242,6 +243,16 @@ class _Cached(nn.Module):
         if name not in ops.LINEAR_F32_ENGINES:
             raise DetZeroHipError('unknown fp32 linear engine %r (%s)' % (name, ' | '.join(ops.LINEAR_F32_ENGINES)))
         self.f32_linear_engine = name
+        CACHE_GEN[0] += 1
+        return self
+
+    def set_attention_engine(self, name):
+        """Engine of the refiner's multi-head attention core in the exact-fp32 mode: 'mfma32' (dz_mha_core, the default) or 'bf16x3'
+        (three bf16 limbs per operand, csrc/mha_t.hip) for the calls `refine_modules._mha_forward` sends there (key lists of at least
+        LIMB3_ATTN_MIN_KEYS).  Independent of set_linear_engine; the split modes ignore it.  A refused name changes nothing."""
+        if name not in ops.ATTENTION_F32_ENGINES:
+            raise DetZeroHipError('unknown fp32 attention engine %r (%s)' % (name, ' | '.join(ops.ATTENTION_F32_ENGINES)))
+        self.f32_attention_engine = name
         CACHE_GEN[0] += 1
         return self
 

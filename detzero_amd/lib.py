@@ -180,6 +180,8 @@ _SIGS = {
     'dz_linear_forward_splitk': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                                          ctypes.c_size_t, c_void_p]),
     'dz_mha_core_split': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_int, c_void_p]),
+    'dz_mha_core_limb3': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),
+    'dz_mha_core_limb3_supported': (c_int, [c_int, c_int, c_int, c_int]),
     'dz_pdv_sa_pool_supported': (c_int, [c_int] * 7),
     'dz_pdv_sa_pool': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

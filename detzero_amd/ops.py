@@ -1464,14 +1464,34 @@ def seq_crop(xyz, boxes, payload, plan, want_index=False):
     return out, index, seg_off, total
 
 
-def mha_core(q, k, v, key_padding_mask, heads, scale, math=0):
+ATTENTION_F32_ENGINES = ('mfma32', 'bf16x3')
+
+
+def mha_core_limb3_supported(batch, lq, lk, heads):
+    """Whether the bf16x3 engine of the f32 mode's attention core (dz_mha_core_limb3, csrc/mha_t.hip) takes a call of these sizes.
+    Host only."""
+    return bool(L.load().dz_mha_core_limb3_supported(int(batch), int(lq), int(lk), int(heads)))
+
+
+def mha_core(q, k, v, key_padding_mask, heads, scale, math=0, f32_engine=None):
     """q (B,Lq,E), k/v (B,Lk,E), mask (B,Lk) bool/uint8 or None -> (B,Lq,E).  math 0: exact fp32 (dz_mha_core); 1 / 2: operands as
     16-bit pairs on the 16-bit matrix cores (dz_mha_core_split).  The split cores stay within their bound (tests/test_gpu_refine_kernels.py:
     8 x the host emulation of their roundings, 4.0e-3 / 3.2e-3 of sum_j p_j |v_j| for f16x2 / bf16x2) for logits (scale q.k) of standard
     deviation 2^-12 .. 2^8 and |v| of the order 2^-12 .. 2^8 in f16x2 (below |v| ~ 2^-4 the fp16 lo halves of v turn subnormal and the error
     grows from 2e-7 to 5e-5 at 2^-12; |q scale log2 e|, |k|, |v| beyond 65504 saturate) and for logits of standard deviation up to 2^4, any
     v, in bf16x2.  The refiner is well inside: with the synthetic weights on the golden inputs (tests/test_refine.py) its attention layers
-    see logits of standard deviation 1.0 - 1.5 (largest 9) and |v| of median 0.6 - 0.8 (largest 5)."""
+    see logits of standard deviation 1.0 - 1.5 (largest 9) and |v| of median 0.6 - 0.8 (largest 5).
+    f32_engine (math 0 only): None / 'mfma32' - the dz_mha_core call, word for word; 'bf16x3' - dz_mha_core_limb3 (csrc/mha_t.hip): q, k,
+    v and the probabilities as three exact bf16 limbs, all six limb products of both matrix products on the bf16 matrix pipe, fp32
+    accumulation and softmax.  It keeps dz_mha_core's own bound (8.0e-5 of sum_j p_j |v_j|, tests/test_gpu_mha_limb3.py) over the
+    whole sweep, logits of standard deviation 2^-12 .. 2^8 and |v| of the order 2^-12 .. 2^8 (measured at (2, 40, 130): 2.5e-7 at every
+    gain on v; on q.k 1.5e-7 .. 2.5e-7 up to 2^0, 4.8e-6 at 2^4 and 4.6e-5 at 2^8, where the float32 host evaluation is at 4.8e-5 itself); operands
+    are clamped to +-3.39e38 (bf16 max) before the first limb only, so every finite fp32 value is carried exactly.  'bf16x3' with a
+    split math, or an unknown name: DetZeroHipError."""
+    if f32_engine not in (None,) + ATTENTION_F32_ENGINES:
+        raise L.DetZeroHipError('unknown fp32 attention engine %r (%s)' % (f32_engine, ' | '.join(ATTENTION_F32_ENGINES)))
+    if f32_engine == 'bf16x3' and math:
+        raise L.DetZeroHipError('mha_core: f32_engine bf16x3 is an engine of the exact-fp32 mode (math 0), not of split math %r' % (math,))
     lib = L.load()
     L.require_cuda(q, k, v)
     b, lq, e = q.shape
@@ -1485,6 +1505,10 @@ def mha_core(q, k, v, key_padding_mask, heads, scale, math=0):
     if math:
         rc = lib.dz_mha_core_split(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(m8), b, lq, lk, heads, float(scale), L.ptr(out), storage_math(math), L.stream())
         L.check(rc, 'dz_mha_core_split')
+        return out
+    if f32_engine == 'bf16x3':
+        rc = lib.dz_mha_core_limb3(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(m8), b, lq, lk, heads, float(scale), L.ptr(out), L.stream())
+        L.check(rc, 'dz_mha_core_limb3')
         return out
     rc = lib.dz_mha_core(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(m8), b, lq, lk, heads, float(scale), L.ptr(out),
                          L.stream())
@@ -1795,7 +1819,7 @@ def _install_guards():
     import types
     g = globals()
     for name, obj in list(g.items()):
-        if isinstance(obj, types.FunctionType) and obj.__module__ == __name__ and not name.startswith('_') and name not in ('grid_size_of', 'math_id', 'pair16_pack', 'pair16_unpack', 'limb3_pack', 'limb3_unpack', 'conv3x3_limb3_supported', 'conv2d_limb3_supported'):
+        if isinstance(obj, types.FunctionType) and obj.__module__ == __name__ and not name.startswith('_') and name not in ('grid_size_of', 'math_id', 'pair16_pack', 'pair16_unpack', 'limb3_pack', 'limb3_unpack', 'conv3x3_limb3_supported', 'conv2d_limb3_supported', 'mha_core_limb3_supported'):
             g[name] = _guarded(obj)
     for name in ('build_from_coords', 'downsample', 'neighbors_to'):
         setattr(SparseLevel, name, _guarded(getattr(SparseLevel, name)))

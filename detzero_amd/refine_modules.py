@@ -212,23 +212,26 @@ _REFINE_MATH = [0]
 # Engine of the linear layers in the exact-fp32 mode: 'mfma32' (dz_linear_forward, default) or 'bf16x3' (dz_linear_limb3_forward,
 # csrc/linear_t.hip) - set next to _REFINE_MATH by the model's forward from its `f32_linear_engine` (set_linear_engine).
 _REFINE_LINEAR = ['mfma32']
+# Engine of the attention core in the exact-fp32 mode: 'mfma32' (dz_mha_core, default) or 'bf16x3' (dz_mha_core_limb3, csrc/mha_t.hip) -
+# set the same way from the model's `f32_attention_engine` (set_attention_engine).
+_REFINE_ATTN = ['mfma32']
 SPLIT_MIN_ROWS = 2048
 
 
 @contextlib.contextmanager
-def _math_mode(m, linear_engine='mfma32'):
-    prev = _REFINE_MATH[0], _REFINE_LINEAR[0]
-    _REFINE_MATH[0], _REFINE_LINEAR[0] = int(m), linear_engine
+def _math_mode(m, linear_engine='mfma32', attention_engine='mfma32'):
+    prev = _REFINE_MATH[0], _REFINE_LINEAR[0], _REFINE_ATTN[0]
+    _REFINE_MATH[0], _REFINE_LINEAR[0], _REFINE_ATTN[0] = int(m), linear_engine, attention_engine
     try:
         yield
     finally:
-        _REFINE_MATH[0], _REFINE_LINEAR[0] = prev
+        _REFINE_MATH[0], _REFINE_LINEAR[0], _REFINE_ATTN[0] = prev
 
 
 def _with_math(fn):
-    """Model forward under the module's arithmetic (`set_math('f16x2')`; default fp32) and its f32 linear engine."""
+    """Model forward under the module's arithmetic (`set_math('f16x2')`; default fp32) and its f32 linear and attention engines."""
     def wrapper(self, data_dict):
-        with _math_mode(self.math, getattr(self, 'f32_linear_engine', 'mfma32')):
+        with _math_mode(self.math, getattr(self, 'f32_linear_engine', 'mfma32'), getattr(self, 'f32_attention_engine', 'mfma32')):
             return fn(self, data_dict)
     return wrapper
 
@@ -294,6 +297,8 @@ FOLDED_XATTN = [True]         # development switch: dz_xattn_folded for few-quer
 FOLD_MIN_KEYS = 256
 SPLIT_ATTENTION = [True]      # development switch: dz_mha_core_split for long key lists in the split math modes vs the fp32 core
 SPLIT_ATTN_MIN_KEYS = 1024
+LIMB3_ATTN_MIN_KEYS = 64      # f32 mode, set_attention_engine('bf16x3'): the shortest key list sent to dz_mha_core_limb3 - the smallest lk of
+                              # tools/bench_mha.py from which it is not slower than dz_mha_core (lk 3: 0.80 x, lk 64: 1.20 x)
 FUSED_CHAIN = [True]          # development switch: dz_mlp_chain_forward (memory MLP + K / V in one kernel) vs one launch per layer
 FUSED_POINTNET = [True]       # development switch: the fused encoder kernel (csrc/pointnet.hip) vs layer-by-layer launches
 
@@ -370,6 +375,21 @@ def _mha_plan(m):
             'one': one, 'heads': m.num_heads, 'scale': float(m.head_dim) ** -0.5, 'e': e}
 
 
+def _limb3_attn_ok(b, lq, lk, heads):
+    """The routing predicate of `_mha_core`: the module's math is 0 (the split modes ignore the switch, also where their short key
+    lists fall back to the fp32 core), its switch says 'bf16x3', the engine takes the sizes and the key list is long enough."""
+    return (not _REFINE_MATH[0] and _REFINE_ATTN[0] == 'bf16x3' and lk >= LIMB3_ATTN_MIN_KEYS and
+            ops.mha_core_limb3_supported(b, lq, lk, heads))
+
+
+def _mha_core(q, k, v, key_padding_mask, heads, scale, am):
+    """The one place `_mha_forward` launches the attention core from: on the bf16x3 engine exactly when `_limb3_attn_ok`; otherwise
+    the ops.mha_core call is what it always was."""
+    if _limb3_attn_ok(q.shape[0], q.shape[1], k.shape[1], heads):
+        return ops.mha_core(q, k, v, key_padding_mask, heads, scale, math=0, f32_engine='bf16x3')
+    return ops.mha_core(q, k, v, key_padding_mask, heads, scale, math=am)
+
+
 def _mha_forward(p, q_rows, k_rows, v_rows, b, lq, lk, key_padding_mask, kv=None):
     """rows are (B*L, E) channel-last.  multi_head_attention.py:199-288.  kv: the key / value projections of the memory when the
     caller already has them (dz_mlp_chain_forward produces them with the memory rows)."""
@@ -377,7 +397,7 @@ def _mha_forward(p, q_rows, k_rows, v_rows, b, lq, lk, key_padding_mask, kv=None
     q = _linear(q_rows, p, 'wq', p['one'], p['bq'], False, e)
     am = _REFINE_MATH[0] if (SPLIT_ATTENTION[0] and lk >= SPLIT_ATTN_MIN_KEYS and _REFINE_MATH[0] in (1, 2)) else 0   # long key lists only
     if kv is not None:
-        o = ops.mha_core(q.view(b, lq, e), kv[0].view(b, lk, e), kv[1].view(b, lk, e), key_padding_mask, p['heads'], p['scale'], math=am)
+        o = _mha_core(q.view(b, lq, e), kv[0].view(b, lk, e), kv[1].view(b, lk, e), key_padding_mask, p['heads'], p['scale'], am)
         return _linear(o.view(b * lq, e), p, 'wo', p['one'], p['bo'], False, e)
     if FOLDED_XATTN[0] and k_rows is v_rows and lk >= FOLD_MIN_KEYS and ops.xattn_folded_supported(lq, e, p['heads']):
         # a few queries over a long memory (GRM: 3 x 4096): the key / value projections fold into the queries, the memory is read once
@@ -395,7 +415,7 @@ def _mha_forward(p, q_rows, k_rows, v_rows, b, lq, lk, key_padding_mask, kv=None
     else:
         k = _linear(k_rows, p, 'wk', p['one'], p['bk'], False, e)
         v = _linear(v_rows, p, 'wv', p['one'], p['bv'], False, e)
-    o = ops.mha_core(q.view(b, lq, e), k.view(b, lk, e), v.view(b, lk, e), key_padding_mask, p['heads'], p['scale'], math=am)
+    o = _mha_core(q.view(b, lq, e), k.view(b, lk, e), v.view(b, lk, e), key_padding_mask, p['heads'], p['scale'], am)
     return _linear(o.view(b * lq, e), p, 'wo', p['one'], p['bo'], False, e)
 
 

@@ -698,6 +698,19 @@ int dz_mha_core(const float *q, const float *k, const float *v, const uint8_t *k
  * cross-attention: 200 queries x 9600 keys).  Same arguments; math = DZ_MATH_F16X2 or DZ_MATH_BF16X2; head dim 32. */
 int dz_mha_core_split(const float *q, const float *k, const float *v, const uint8_t *key_padding_mask, int batch, int lq, int lk, int heads,
                       float scale, float *out, int math, void *stream);
+/* Opt-in engine of the exact-fp32 mode for the same core (csrc/mha_t.hip, k_mha_block_t): dz_mha_core's arguments and semantics, fp32 in
+ * and out, on the bf16 matrix pipe in the three-limb arithmetic of dz_linear_limb3_forward below - q (times scale * log2 e, rounded
+ * once), K, V and the probabilities p = exp2(s - max) each as three exact bf16 limbs h + m + l, both products as the six terms
+ * l.h  h.l  m.m  m.h  h.m  h.h (K or V limb . q or p limb, smallest first), fp32 accumulation, keys ascending, no atomics: two launches
+ * agree bit for bit.  One route for every lq >= 1 (a workgroup = one (batch, head), up to 8 waves of 32 queries, key blocks of 64).
+ * A masked key's score is replaced by -inf (its K row may hold NaN or any finite value); a fully masked batch entry is NaN for that
+ * entry only; only rows [0, lq) of out are written.
+ * dz_mha_core_limb3_supported (host only, no GPU needed) is 1 exactly when the sizes pass: batch >= 0, lq >= 0, lk >= 1,
+ * 1 <= heads <= 65535, batch <= 65535 (the grid's limits).  Anything else, and a null q / k / v / out: DZ_ERR_INVALID with
+ * dz_mha_core's wording, before any launch and before a pointer is read.  batch == 0 or lq == 0: DZ_OK, no launch. */
+int dz_mha_core_limb3(const float *q, const float *k, const float *v, const uint8_t *key_padding_mask, int batch, int lq, int lk, int heads,
+                      float scale, float *out, void *stream);
+int dz_mha_core_limb3_supported(int batch, int lq, int lk, int heads);
 
 /* y (rows, cout) = relu?( x (rows, cin) . W (cin, cout_pad) * scale + shift ) — the 1x1 Conv1d/Conv2d
  * + BatchNorm + ReLU stacks of the GRM/PRM PointNet encoders

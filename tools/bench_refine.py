@@ -2,6 +2,7 @@
 """Secondary kernel set (BASELINE.json configs[3]): refining module throughput on one MI355X.
 
     python tools/bench_refine.py [--objects 1024] [--steps 5]
+    python tools/bench_refine.py --four-arms 3        (f32: linear off / on x attention off / on, alternating in one process)
 
 GRM: per object 3 proposals x 256 query points + 4096 memory points (reference defaults,
 refining/tools/cfgs/ref_dataset_cfgs/waymo_grm_dataset.yaml); PRM: per track 200 boxes x 256 query points +
@@ -29,9 +30,10 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps
 
 
-def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True, *, f32_linear=None):
+def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True, *, f32_linear=None, f32_attention=None):
     """Refiner throughput on `dev` -> dict (also the `refine` leg of bench.py: BASELINE configs[3]).  f32_linear: None = the modules'
-    default, or a name for set_linear_engine ('mfma32' | 'bf16x3'; it matters in math 'f32' only) - reported as 'f32_linear'."""
+    default, or a name for set_linear_engine ('mfma32' | 'bf16x3'; it matters in math 'f32' only) - reported as 'f32_linear'.
+    f32_attention: the same for set_attention_engine (csrc/mha_t.hip), reported as 'f32_attention'."""
     from detzero_amd import ops
     from detzero_amd.refine_modules import GeometryTransformer, PositionTransformer
     from detzero_amd.synth import synth_boxes, synth_state_dict, synth_waymo_frame
@@ -49,6 +51,8 @@ def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True, *
     grm = grm.to(dev).set_math(math)
     if f32_linear is not None:
         out['f32_linear'] = grm.set_linear_engine(f32_linear).f32_linear_engine
+    if f32_attention is not None:
+        out['f32_attention'] = grm.set_attention_engine(f32_attention).f32_attention_engine
     gd = {'geo_memory_points': torch.randn((b, 4096, 11), generator=gen).to(dev),
           'geo_query_points': torch.randn((b, 3, 256, 4), generator=gen).to(dev),
           'geo_query_boxes': torch.randn((b, 3, 7), generator=gen).to(dev), 'geo_query_num': torch.full((b,), 3)}
@@ -81,6 +85,8 @@ def measure(dev, objects=1024, chunk=128, steps=3, math='f32', with_crop=True, *
     prm = prm.to(dev).set_math(math)
     if f32_linear is not None:
         prm.set_linear_engine(f32_linear)
+    if f32_attention is not None:
+        prm.set_attention_engine(f32_attention)
     bp = min(b, 96)
     pchunks = max(objects // bp, 1)
     lens = torch.randint(5, 201, (bp,), generator=gen)
@@ -141,8 +147,22 @@ def main():
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--math', default='f32', choices=['f32', 'f16x2', 'bf16x2'], help="arithmetic of the big MLP stacks (set_math)")
     ap.add_argument('--f32-linear', default=None, choices=['mfma32', 'bf16x3'], help="engine of the f32 mode's linear layers (set_linear_engine)")
+    ap.add_argument('--f32-attention', default=None, choices=['mfma32', 'bf16x3'], help="engine of the f32 mode's attention core (set_attention_engine)")
+    ap.add_argument('--four-arms', type=int, default=0, metavar='ROUNDS',
+                    help="f32 mode: linear off / on x attention off / on, alternating in this process, ROUNDS rounds, one JSON line per arm and "
+                         "round (GRM objects/s, PRM tracks/s), then one f16x2 line for orientation; no crop timing")
     args = ap.parse_args()
-    print(json.dumps(measure(torch.device('cuda', 0), args.objects, args.chunk, args.steps, args.math, f32_linear=args.f32_linear)))
+    dev = torch.device('cuda', 0)
+    if args.four_arms:
+        for rnd in range(args.four_arms):
+            for lin in ('mfma32', 'bf16x3'):
+                for att in ('mfma32', 'bf16x3'):
+                    r = measure(dev, args.objects, args.chunk, args.steps, 'f32', with_crop=False, f32_linear=lin, f32_attention=att)
+                    r['round'] = rnd
+                    print(json.dumps(r), flush=True)
+        print(json.dumps(measure(dev, args.objects, args.chunk, args.steps, 'f16x2', with_crop=False)), flush=True)
+        return
+    print(json.dumps(measure(dev, args.objects, args.chunk, args.steps, args.math, f32_linear=args.f32_linear, f32_attention=args.f32_attention)))
 
 
 if __name__ == '__main__':
