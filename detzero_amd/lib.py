@@ -51,6 +51,22 @@ class TrackTable(ctypes.Structure):
 
 
 _TT = ctypes.POINTER(TrackTable)
+_F8 = c_float * 8          # DZ_TRACK_MAX_CLASSES
+
+
+class TrackSeqParams(ctypes.Structure):
+    """Mirror of ``dz_track_seq_params``."""
+    _fields_ = [(k, c_int) for k in ('metric', 'distinguish_class', 'gate_class', 'n_cls', 'two_stage', 'merge_enable', 'death_age',
+                                     'init_track_id')] + \
+               [(k, _F8) for k in ('thr_first', 'thr_second', 'thr_merge')] + [(k, c_float) for k in ('p0', 'p1', 'q0', 'q1', 'r', 'dt')]
+
+
+class TrackSeqIO(ctypes.Structure):
+    """Mirror of ``dz_track_seq_io``."""
+    _fields_ = [(k, c_void_p) for k in ('det', 'det_flags', 'frame_row', 'seq_frame')] + \
+               [(k, c_int) for k in ('n_seq', 'n_frames', 'n_det_rows', 'track_cap', 'row_cap', 'det_cap', 'log_cap')] + \
+               [(k, c_void_p) for k in ('ext', 'ext_count', 'going_at', 'going_idx', 'start_at', 'start_idx')] + \
+               [(k, c_int) for k in ('ext_cap', 'n_going', 'n_start')]
 
 # name -> (restype, argtypes); must list every symbol of include/detzero_hip.h (tests check this)
 _SIGS = {
@@ -271,6 +287,12 @@ _SIGS = {
                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dz_traj_pair_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_int, c_void_p, c_void_p]),
+    'dz_track_seq_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'dz_track_seq_pass': (c_int, [ctypes.POINTER(TrackSeqParams), ctypes.POINTER(TrackSeqIO), c_int, _TT, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
+    'dz_lsa_ws_bytes': (c_size_t, [c_int, c_int]),
+    'dz_lsa_batch': (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, ctypes.c_longlong,
+                             c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -1786,6 +1786,136 @@ def traj_pair_rows(a_box, a_cls, a_slot, b_box, b_cls, b_slot, metric, distingui
     return rows
 
 
+# ------------------------------------------------------------------------------------------------
+# a pass of a batch of sequences in one launch (csrc/track_seq.hip)
+# ------------------------------------------------------------------------------------------------
+TRACK_SEQ_MAX_TRACKS = 4096          # DZ_TRACK_SEQ_MAX_TRACKS
+TRACK_SEQ_MAX_DET = 1024             # DZ_TRACK_SEQ_MAX_DET
+TRACK_SEQ_OVF_TRACKS, TRACK_SEQ_OVF_LOG, TRACK_SEQ_OVF_LSA, TRACK_SEQ_OVF_DESC = 1, 2, 4, 8
+
+
+def track_seq_params(metric, distinguish_class, gate_class, n_cls, two_stage, merge_enable, death_age, init_track_id, thr_first, thr_second,
+                     thr_merge, p, q, r, dt):
+    """``dz_track_seq_params`` from the tracker's configuration (threshold lists may be shorter than 8 or None)."""
+    def thr(v):
+        v = [float(x) for x in (v if v is not None else [])][:TRACK_MAX_CLASSES]
+        return L._F8(*(v + [0.] * (TRACK_MAX_CLASSES - len(v))))
+    return L.TrackSeqParams(int(metric), int(bool(distinguish_class)), int(gate_class), int(n_cls), int(bool(two_stage)), int(bool(merge_enable)),
+                            int(death_age), int(init_track_id), thr(thr_first), thr(thr_second), thr(thr_merge), float(p[0]), float(p[1]),
+                            float(q[0]), float(q[1]), float(r), float(dt))
+
+
+def _seq_i32(t, n, what):
+    if t is None:
+        if n:
+            raise L.DetZeroHipError('track_seq_pass: %s is missing' % what)
+        return None
+    L.require_cuda(t)
+    if t.dtype != torch.int32 or t.numel() < n:
+        raise L.DetZeroHipError('track_seq_pass: %s is int32 with at least %d entries, got %s %s' % (what, n, tuple(t.shape), t.dtype))
+    return t
+
+
+def track_seq_pass_nosync(params, det, det_flags, frame_row, seq_frame, track_cap, row_cap, det_cap, log_cap, reverse=None):
+    """One pass (forward, or reverse when ``reverse`` = (ext (S, ext_cap, 16), ext_count (S,), going_at, going_idx, start_at,
+    start_idx)) of every sequence in one launch.  det (rows, 16) i32, det_flags (rows,), frame_row (frames + 1,), seq_frame (S + 1,)
+    on the device.  -> (log (S, log_cap, 16) i32, log_count (S,) i32, overflow (S,) i32) on the device; nothing is read here."""
+    lib = L.load()
+    det, n_rows = _track_rows(det, 'track_seq_pass')
+    n_seq, n_frames = seq_frame.shape[0] - 1, frame_row.shape[0] - 1
+    _seq_i32(det_flags, n_rows, 'det_flags'), _seq_i32(frame_row, 1, 'frame_row'), _seq_i32(seq_frame, 1, 'seq_frame')
+    dev = det.device
+    io = L.TrackSeqIO(L.ptr(det), L.ptr(det_flags), L.ptr(frame_row), L.ptr(seq_frame), n_seq, n_frames, n_rows, int(track_cap), int(row_cap),
+                      int(det_cap), int(log_cap))
+    if reverse is not None:
+        ext, ext_count, going_at, going_idx, start_at, start_idx = reverse
+        L.require_cuda(ext)
+        if ext.dtype != torch.int32 or ext.dim() != 3 or ext.shape[0] != n_seq or ext.shape[2] != TRACK_ROW_WORDS:
+            raise L.DetZeroHipError('track_seq_pass: ext is (%d, ext_cap, %d) int32, got %s' % (n_seq, TRACK_ROW_WORDS, tuple(ext.shape)))
+        _seq_i32(ext_count, n_seq, 'ext_count'), _seq_i32(going_at, n_frames + 1, 'going_at'), _seq_i32(start_at, n_frames + 1, 'start_at')
+        io.ext, io.ext_count, io.going_at, io.start_at = L.ptr(ext), L.ptr(ext_count), L.ptr(going_at), L.ptr(start_at)
+        io.going_idx, io.start_idx = L.ptr(_seq_i32(going_idx, 0, 'going_idx')), L.ptr(_seq_i32(start_idx, 0, 'start_idx'))
+        io.ext_cap, io.n_going, io.n_start = ext.shape[1], going_idx.numel(), start_idx.numel()
+    tables = TrackTable(max(n_seq * 2 * int(track_cap), 1), dev)
+    log = torch.empty((max(n_seq, 1), max(int(log_cap), 1), TRACK_ROW_WORDS), dtype=torch.int32, device=dev)     # rows below log_count are written
+    state = torch.zeros((2, max(n_seq, 1)), dtype=torch.int32, device=dev)
+    ws = _ws(lib.dz_track_seq_ws_bytes(n_seq, int(track_cap), int(row_cap), int(det_cap)))
+    rc = lib.dz_track_seq_pass(ctypes.byref(params), ctypes.byref(io), 0 if reverse is None else 1, ctypes.byref(tables.c), L.ptr(log),
+                               L.ptr(state[0]), L.ptr(state[1]), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, 'dz_track_seq_pass')
+    return log[:n_seq], state[0, :n_seq], state[1, :n_seq]
+
+
+# ------------------------------------------------------------------------------------------------
+# linear sum assignment (csrc/lsa.h, csrc/lsa.hip): GNN_assignment for a batch of problems, one workgroup each
+# ------------------------------------------------------------------------------------------------
+LSA_MAX_DIM = 4096                 # DZ_LSA_MAX_DIM
+LSA_STATUS = {1: 'no finite cost left (NaN costs)', 2: 'a loop bound was reached', 3: 'descriptor outside its buffers'}
+
+
+def linear_assignment_batch_nosync(cost, shapes, threshold=1.):
+    """cost: 1-d float32 device tensor, the row-major matrices of ``shapes`` = [(rows, cols), ...] back to back.
+    -> (row_to_col (sum rows,) i32, unmatched_rows (sum rows,) i32, unmatched_cols (sum cols,) i32, counts (P,4) i32
+    [matched, unmatched rows, unmatched cols, status]) on the device and the host lists (row_off, col_off) of each problem's
+    offsets.  No host read: the caller looks at counts[:, 3] when it reads the results."""
+    lib = L.load()
+    L.require_cuda(cost)
+    if cost.dtype != torch.float32 or cost.dim() != 1:
+        raise L.DetZeroHipError('linear_assignment_batch: cost is a 1-d float32 device tensor, got %s %s' % (tuple(cost.shape), cost.dtype))
+    shapes = [(int(r), int(c)) for r, c in shapes]
+    if any(r < 0 or c < 0 for r, c in shapes):
+        raise L.DetZeroHipError('linear_assignment_batch: negative shape in %s' % (shapes,))
+    desc = np.zeros((len(shapes), 6), dtype=np.int64)
+    cost_at = row_at = col_at = ws_at = 0
+    for p, (r, c) in enumerate(shapes):
+        desc[p] = (r, c, cost_at, row_at, col_at, ws_at)
+        cost_at, row_at, col_at = cost_at + r * c, row_at + r, col_at + c
+        if max(r, c) <= LSA_MAX_DIM:        # (a larger side is refused below by the library)
+            ws_at += lib.dz_lsa_ws_bytes(r, c)          # 0 for a problem that fits LDS; the slices stand back to back
+    if cost_at != cost.shape[0]:
+        raise L.DetZeroHipError('linear_assignment_batch: %d costs for shapes that hold %d' % (cost.shape[0], cost_at))
+    dev = cost.device
+    p = len(shapes)
+    row_to_col = torch.empty((max(row_at, 1),), dtype=torch.int32, device=dev)
+    rows_free = torch.empty((max(row_at, 1),), dtype=torch.int32, device=dev)
+    cols_free = torch.empty((max(col_at, 1),), dtype=torch.int32, device=dev)
+    counts = torch.zeros((max(p, 1), 4), dtype=torch.int32, device=dev)
+    ws = _ws(ws_at)
+    d_desc = torch.from_numpy(desc).to(dev) if p else None
+    rc = lib.dz_lsa_batch(L.ptr(cost), cost_at, L.ptr(d_desc), p, max([r for r, _ in shapes] + [0]), max([c for _, c in shapes] + [0]),
+                          float(threshold), L.ptr(row_to_col), L.ptr(rows_free), row_at, L.ptr(cols_free), col_at, L.ptr(counts), L.ptr(ws),
+                          ws.numel(), L.stream())
+    L.check(rc, 'dz_lsa_batch')
+    return row_to_col[:row_at], rows_free[:row_at], cols_free[:col_at], counts[:p], desc[:, 3].tolist(), desc[:, 4].tolist()
+
+
+def linear_assignment_batch(costs, threshold=1.):
+    """GNN_assignment (track_models.py) for a list of (rows, cols) float32 device matrices in one launch: a list of
+    (matched (K,2) int [row, col] in row order, unmatched rows, unmatched columns) host arrays.  One host read.  The matrices are
+    not modified (GNN_assignment writes the 5000 into its argument)."""
+    costs = list(costs)
+    if not costs:
+        return []
+    for c in costs:
+        L.require_cuda(c)
+        if c.dtype != torch.float32 or c.dim() != 2:
+            raise L.DetZeroHipError('linear_assignment_batch: a cost matrix is (rows, cols) float32, got %s %s' % (tuple(c.shape), c.dtype))
+    flat = torch.cat([c.reshape(-1) for c in costs]) if len(costs) > 1 else costs[0].reshape(-1)
+    shapes = [tuple(c.shape) for c in costs]
+    row_to_col, rows_free, cols_free, counts, row_off, col_off = linear_assignment_batch_nosync(flat, shapes, threshold)
+    row_to_col, rows_free, cols_free, counts = row_to_col.cpu().numpy(), rows_free.cpu().numpy(), cols_free.cpu().numpy(), counts.cpu().numpy()
+    out = []
+    for p, (r, c) in enumerate(shapes):
+        matched, n_rows_free, n_cols_free, status = counts[p].tolist()
+        if status != 0:
+            raise L.DetZeroHipError('linear_assignment_batch: problem %d (%d x %d): %s' % (p, r, c, LSA_STATUS.get(status, status)))
+        r2c = row_to_col[row_off[p]:row_off[p] + r]
+        at = np.flatnonzero(r2c >= 0)
+        out.append((np.stack([at, r2c[at]], axis=1).astype(int), rows_free[row_off[p]:row_off[p] + n_rows_free].astype(int),
+                    cols_free[col_off[p]:col_off[p] + n_cols_free].astype(int)))
+    return out
+
+
 PROFILER = None
 
 

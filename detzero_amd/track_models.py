@@ -22,6 +22,13 @@ them, are addressed as rows of that log on the device.
 All per-frame arithmetic goes through one narrow ops object (``HipTrackOps`` is the only implementation in the product); the
 tests drive the same orchestration with a numpy restatement of the seven ops.
 
+Opt-in second way (``TrackManager.forward_batch``, ``DetZeroTracker.forward_batch``, ``run_model(..., batch=N)`` /
+``DZ_TRACK_BATCH``): the whole frame loop of a pass on the device, one workgroup per sequence, the assignment included
+(csrc/track_seq.hip, csrc/lsa.h), for a list of sequences at once.  The host packs all detections into one row buffer, reads the
+forward logs once, regroups them per frame with the ``start`` flags exactly as ``forward`` does, uploads that and reads the reverse
+logs: two launches per batch.  That host work goes through one sequence-ops object (``HipSeqTrackOps``; the tests have a stand-in
+on the numpy ops).  The results are those of ``forward``.
+
 Arithmetic is fp32, which is what the reference computes when its detections are float32; float64 ``boxes_global`` (what
 transform_to_global produces) are rounded to fp32 when a frame is uploaded.  The size and heading of a track equal columns 3:7 of
 its box wherever the reference reads them, so the table stores the box only.
@@ -185,6 +192,186 @@ class HipTrackOps:
 
 
 # ------------------------------------------------------------------------------------------------
+# sequence ops: a pass of a batch of sequences in one launch
+# ------------------------------------------------------------------------------------------------
+class SeqPack:
+    """The detections of a batch of sequences as ONE row buffer with per-frame offsets (what dz_track_seq_pass reads).
+
+      frame_lists[s]   the sequence's frame ids in time order
+      rows             (N,16) int32: every frame's row buffer (det_rows), sequences and frames back to back
+      flags            (N,) int32: bit 0 = passes the first stage's score / point thresholds, bit 1 = enough points
+                       (TrackManager._stage_masks on the frame's own arrays; 0 with the one_stage association)
+      frame_row        (frames + 1,) first row of every frame, frames numbered through the batch
+      seq_frame        (S + 1,) first frame of every sequence
+      max_det[s]       the largest frame of the sequence
+      dtypes[s]        the result dtypes of score / num_points (TrackManager._note_dtypes)
+    """
+
+    def __init__(self, mgr, data_dicts):
+        self.data_dicts = data_dicts
+        self.frame_lists = [sorted(list(dd.keys()), key=int) for dd in data_dicts]
+        rows, flags, frame_row, seq_frame = [], [], [0], [0]
+        self.max_det, self.dtypes = [], []
+        for dd, frame_list in zip(data_dicts, self.frame_lists):
+            dtypes = {'score': np.float32, 'num_points': np.int64}
+            biggest = 0
+            for frm_id in frame_list:
+                det = dd[frm_id]
+                cls, r = mgr._frame_rows(det)
+                if mgr.stage == 'one_stage':
+                    f = np.zeros(len(cls), dtype=np.int32)
+                else:
+                    first, enough = mgr._stage_masks(det, cls)
+                    f = np.asarray(first).astype(np.int32).reshape(-1) | (np.asarray(enough).astype(np.int32).reshape(-1) << 1)
+                rows.append(r)
+                flags.append(f)
+                frame_row.append(frame_row[-1] + len(cls))
+                biggest = max(biggest, len(cls))
+                mgr._note_dtypes(dtypes, det)
+            seq_frame.append(len(frame_row) - 1)
+            self.max_det.append(biggest)
+            self.dtypes.append(dtypes)
+        self.rows = np.concatenate(rows, axis=0) if rows else np.zeros((0, ROW_WORDS), dtype=np.int32)
+        self.flags = np.concatenate(flags) if flags else np.zeros(0, dtype=np.int32)
+        self.frame_row = np.array(frame_row, dtype=np.int64)
+        self.seq_frame = np.array(seq_frame, dtype=np.int64)
+
+    def frames_of(self, s):
+        return range(int(self.seq_frame[s]), int(self.seq_frame[s + 1]))
+
+    def frame_rows(self, g):
+        """(rows, flags) of frame g (numbered through the batch)."""
+        return self.rows[self.frame_row[g]:self.frame_row[g + 1]], self.flags[self.frame_row[g]:self.frame_row[g + 1]]
+
+    def subset(self, seqs):
+        """The buffers of the listed sequences only, renumbered: (rows, flags, frame_row, seq_frame) as int32 arrays."""
+        rows, flags, frame_row, seq_frame = [], [], [0], [0]
+        for s in seqs:
+            for g in self.frames_of(s):
+                r, f = self.frame_rows(g)
+                rows.append(r)
+                flags.append(f)
+                frame_row.append(frame_row[-1] + len(f))
+            seq_frame.append(len(frame_row) - 1)
+        return (np.concatenate(rows, axis=0) if rows else np.zeros((0, ROW_WORDS), dtype=np.int32),
+                np.concatenate(flags) if flags else np.zeros(0, dtype=np.int32), np.array(frame_row, dtype=np.int32),
+                np.array(seq_frame, dtype=np.int32))
+
+
+class HipSeqTrackOps:
+    """forward_batch's two passes on csrc/track_seq.hip.
+
+    Interface (what a stand-in for tests implements):
+      forward_pass(mgr, pack, seqs)               -> {s: (L,16) int32 host log rows, or None}
+      reverse_pass(mgr, pack, seqs, fwd, groups)  -> {s: (L,16) int32 host log rows, or None}
+                                                     fwd[s] = the forward rows, groups[s] = TrackManager._regroup(fwd[s])
+    None = the sequence does not fit the batched path (the caller tracks it with TrackManager.forward).
+
+    Capacities (tracks and log rows per sequence) start from the detections' counts, or from ``track_cap`` / ``log_cap``; a sequence
+    that runs out of one sets its overflow word and is rerun, alone with the others that overflowed, with that capacity doubled
+    (tracks: up to ops.TRACK_SEQ_MAX_TRACKS, which is tried before a sequence is given up; ``reruns`` counts the extra launches).
+    Per pass and launch: one upload of the packed buffers, one read of the counts and overflow words, one read of the log rows."""
+
+    def __init__(self, device=None, track_cap=None, log_cap=None):
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.track_cap, self.log_cap = track_cap, log_cap
+        self.reruns = 0
+
+    def _dev(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    @staticmethod
+    def _params(mgr):
+        two = mgr.stage == 'two_stage'
+        return ops.track_seq_params(mgr.metric, mgr.distinguish_class, mgr.gate_class, len(mgr.class_names), two, mgr.merge_enable,
+                                    mgr.death_age, mgr.init_track_id, mgr.dist_thr, mgr.second_dist_thr if two else None,
+                                    mgr.merge_thr if mgr.merge_enable else None, mgr.p, mgr.q, mgr.r, mgr.delta_t)
+
+    def _run(self, mgr, pack, seqs, track_cap, log_cap, reverse_of=None):
+        """Launch until no sequence overflows: {s: rows or None}.  reverse_of(sub) -> (the reverse pass's device lists, extra rows)."""
+        out, todo = {}, list(seqs)
+        params = self._params(mgr)
+        first = True
+        while todo:
+            if not first:
+                self.reruns += 1
+            first = False
+            rows, flags, frame_row, seq_frame = pack.subset(todo)
+            det_cap = max([pack.max_det[s] for s in todo] + [1])
+            reverse, extra = reverse_of(todo) if reverse_of is not None else (None, 0)
+            log, count, overflow = ops.track_seq_pass_nosync(params, self._dev(rows).reshape(-1, ROW_WORDS), self._dev(flags), self._dev(frame_row),
+                                                             self._dev(seq_frame), track_cap, track_cap + extra, det_cap, log_cap, reverse)
+            state = torch.stack([count, overflow]).cpu().numpy()
+            keep = torch.from_numpy((np.arange(log_cap)[None, :] < state[0][:, None]).reshape(-1)).to(self.device)
+            got = log.reshape(-1, ROW_WORDS)[keep].cpu().numpy()
+            at, again, grow_tracks, grow_log = 0, [], False, False
+            for k, s in enumerate(todo):
+                n, ovf = int(state[0, k]), int(state[1, k])
+                if ovf == 0:
+                    out[s] = got[at:at + n]
+                elif ovf & (ops.TRACK_SEQ_OVF_LSA | ops.TRACK_SEQ_OVF_DESC):
+                    out[s] = None
+                else:
+                    again.append(s)
+                    grow_tracks, grow_log = grow_tracks or bool(ovf & ops.TRACK_SEQ_OVF_TRACKS), grow_log or bool(ovf & ops.TRACK_SEQ_OVF_LOG)
+                at += n
+            give_up = False
+            if grow_tracks:                 # doubled, but tried at the limit itself before the sequences are given up
+                give_up = track_cap >= ops.TRACK_SEQ_MAX_TRACKS
+                track_cap = min(2 * track_cap, ops.TRACK_SEQ_MAX_TRACKS)
+            if grow_log:
+                log_cap *= 2
+                give_up = give_up or log_cap * ROW_WORDS >= 2 ** 31
+            if give_up:
+                for s in again:
+                    out[s] = None
+                again = []
+            todo = again
+        return out
+
+    def forward_pass(self, mgr, pack, seqs):
+        if not seqs:
+            return {}
+        most = max([pack.max_det[s] for s in seqs] + [1])
+        total = max([int(pack.frame_row[pack.seq_frame[s + 1]] - pack.frame_row[pack.seq_frame[s]]) for s in seqs] + [1])
+        track_cap = self.track_cap if self.track_cap is not None else min(max(64, 2 * most), ops.TRACK_SEQ_MAX_TRACKS)
+        log_cap = self.log_cap if self.log_cap is not None else max(256, 2 * total)
+        return self._run(mgr, pack, seqs, track_cap, log_cap)
+
+    def reverse_pass(self, mgr, pack, seqs, fwd, groups):
+        if not seqs:
+            return {}
+        n_tracks = max([int(groups[s][1].sum()) for s in seqs] + [1])
+        if n_tracks > ops.TRACK_SEQ_MAX_TRACKS:
+            big = [s for s in seqs if int(groups[s][1].sum()) > ops.TRACK_SEQ_MAX_TRACKS]
+            out = self.reverse_pass(mgr, pack, [s for s in seqs if s not in big], fwd, groups)
+            out.update({s: None for s in big})
+            return out
+        track_cap = self.track_cap if self.track_cap is not None else n_tracks
+        log_cap = self.log_cap if self.log_cap is not None else max([len(fwd[s]) for s in seqs] + [256])
+
+        def reverse_of(todo):
+            ext_cap = max([len(fwd[s]) for s in todo] + [1])
+            ext = np.zeros((len(todo), ext_cap, ROW_WORDS), dtype=np.int32)
+            going, start, going_at, start_at, most_going = [], [], [0], [0], 0
+            for k, s in enumerate(todo):
+                ext[k, :len(fwd[s])] = fwd[s]
+                _, is_start, per_frame = groups[s]
+                for at in per_frame:
+                    going.append(at[~is_start[at]])
+                    start.append(at[is_start[at]])
+                    going_at.append(going_at[-1] + len(going[-1]))
+                    start_at.append(start_at[-1] + len(start[-1]))
+                    most_going = max(most_going, len(going[-1]))
+            cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+            dev = (self._dev(ext), self._dev([len(fwd[s]) for s in todo]), self._dev(going_at), self._dev(cat(going)), self._dev(start_at),
+                   self._dev(cat(start)))
+            return dev, most_going
+
+        return self._run(mgr, pack, seqs, track_cap, log_cap, reverse_of)
+
+
+# ------------------------------------------------------------------------------------------------
 # TrackManager
 # ------------------------------------------------------------------------------------------------
 def _lower(cfg):
@@ -195,11 +382,15 @@ class TrackManager:
     """``forward({sample_idx: frame})`` -> ``{track_id: {boxes_global, name, score, sample_idx, hit, num_points, obj_ids, pose}}``
     (track_manager.py:85-143).  ``ops_factory`` builds the ops object of a sequence (default: HipTrackOps)."""
 
-    def __init__(self, model_cfg, init_track_id=0, ops_factory=None):
+    def __init__(self, model_cfg, init_track_id=0, ops_factory=None, seq_ops_factory=None):
         self.model_cfg = model_cfg
         self.init_track_id = init_track_id
         self.ops_factory = ops_factory if ops_factory is not None else HipTrackOps
         self.ops = None
+        self.seq_ops_factory = seq_ops_factory      # forward_batch's sequence-ops object (default: HipSeqTrackOps)
+        self.seq_ops = None
+        self.batched = 0            # sequences forward_batch tracked on the batched path ...
+        self.fallbacks = 0          # ... and those it handed to forward (beyond a limit, or an assignment stopped with a status)
 
         flt = _lower(model_cfg.FILTER)
         if flt['name'] != 'KalmanFilter':
@@ -252,14 +443,19 @@ class TrackManager:
         except KeyError as e:
             raise DetZeroHipError('detection class %s is not in DATA_ASSOCIATION.CLASS_NAME %s' % (e, self.class_names))
 
-    def _upload(self, ops, det_data):
-        """-> class codes; the num_points default of track_manager.py:166-167 is written into det_data as the reference does."""
+    def _frame_rows(self, det_data):
+        """-> (class codes, the frame's row buffer); the num_points default of track_manager.py:166-167 is written into det_data
+        as the reference does."""
         one = self.stage == 'one_stage'
         if not one and 'num_points' not in det_data:
             det_data['num_points'] = np.zeros_like(det_data['score'])
         cls = self._codes(det_data['name'])
         npts = np.zeros(len(cls), dtype=np.int32) if one else det_data['num_points']
-        ops.set_detections(det_rows(det_data['boxes_global'], cls, det_data['score'], npts))
+        return cls, det_rows(det_data['boxes_global'], cls, det_data['score'], npts)
+
+    def _upload(self, ops, det_data):
+        cls, rows = self._frame_rows(det_data)
+        ops.set_detections(rows)
         return cls
 
     # ---- association (data_association.py) -------------------------------------------------------
@@ -371,6 +567,37 @@ class TrackManager:
             }
         return out
 
+    def _note_dtypes(self, dtypes, det_data):
+        """The score / num_points dtypes of the results are those of the last frame that holds a detection."""
+        if len(det_data['score']):
+            dtypes['score'] = np.asarray(det_data['score']).dtype
+            if self.stage != 'one_stage':
+                dtypes['num_points'] = np.asarray(det_data['num_points']).dtype
+
+    @staticmethod
+    def _regroup(rows, n_frames):
+        """Forward results per frame in track order, with the flag of each track's first frame (track_manager.py:117-128):
+        -> (ids (L,), is_start (L,) bool, [rows of frame 0 in track order, rows of frame 1, ...])."""
+        ids = rows[:, ROW_ID] if len(rows) else np.zeros(0, dtype=np.int32)
+        _, first = np.unique(ids, return_index=True)
+        is_start = np.zeros(len(rows), dtype=bool)
+        is_start[first] = True
+        rank = {int(ids[at]): k for k, at in enumerate(np.sort(first))}
+        order = np.array([rank[int(i)] for i in ids], dtype=int)
+        per_frame = []
+        for ordinal in range(n_frames):
+            at = np.flatnonzero(rows[:, ROW_FRAME] == ordinal) if len(rows) else np.zeros(0, dtype=int)
+            per_frame.append(at[np.argsort(order[at], kind='stable')])
+        return ids, is_start, per_frame
+
+    @staticmethod
+    def _prepend(tk_result, back_tracks):
+        for tk_id, early in back_tracks.items():
+            # the reverse pass inserts every row at the front (track_manager.py:134-141): the last one processed comes first
+            for key, val in tk_result[tk_id].items():
+                tk_result[tk_id][key] = np.concatenate((early[key][::-1].astype(val.dtype), val), axis=0)
+        return tk_result
+
     def forward(self, data_dict):
         frame_list = sorted(list(data_dict.keys()), key=int)
         ops = self.ops if self.ops is not None else self.ops_factory()
@@ -380,34 +607,48 @@ class TrackManager:
         dtypes = {'score': np.float32, 'num_points': np.int64}
         for ordinal, frm_id in enumerate(frame_list):
             track_id_count = self.online_track_module(ops, ordinal, data_dict[frm_id], track_id_count)
-            if len(data_dict[frm_id]['score']):
-                dtypes['score'] = np.asarray(data_dict[frm_id]['score']).dtype
-                if self.stage != 'one_stage':
-                    dtypes['num_points'] = np.asarray(data_dict[frm_id]['num_points']).dtype
+            self._note_dtypes(dtypes, data_dict[frm_id])
         rows, handle = ops.fetch_log()
         tk_result = self._tracks_of(rows, frame_list, data_dict, dtypes)
         if not self.reverse_enable:
             return tk_result
 
-        # forward results per frame in track order, with the flag of each track's first frame (track_manager.py:117-128)
-        ids = rows[:, ROW_ID] if len(rows) else np.zeros(0, dtype=np.int32)
-        _, first = np.unique(ids, return_index=True)
-        is_start = np.zeros(len(rows), dtype=bool)
-        is_start[first] = True
-        rank = {int(ids[at]): k for k, at in enumerate(np.sort(first))}
-        order = np.array([rank[int(i)] for i in ids], dtype=int)
+        ids, is_start, per_frame = self._regroup(rows, len(frame_list))
         ops.start_pass(ext=handle)
         for ordinal in range(len(frame_list) - 1, -1, -1):
-            at = np.flatnonzero(rows[:, ROW_FRAME] == ordinal) if len(rows) else np.zeros(0, dtype=int)
-            at = at[np.argsort(order[at], kind='stable')]
+            at = per_frame[ordinal]
             self.reverse_tracking_module(ops, ordinal, data_dict[frame_list[ordinal]], at, is_start[at], ids[at].astype(np.int64))
         back, _ = ops.fetch_log()
-        back_tracks = self._tracks_of(back, frame_list, data_dict, dtypes)
-        for tk_id, early in back_tracks.items():
-            # the reverse pass inserts every row at the front (track_manager.py:134-141): the last one processed comes first
-            for key, val in tk_result[tk_id].items():
-                tk_result[tk_id][key] = np.concatenate((early[key][::-1].astype(val.dtype), val), axis=0)
-        return tk_result
+        return self._prepend(tk_result, self._tracks_of(back, frame_list, data_dict, dtypes))
+
+    # ---- a batch of sequences, a pass in one launch ------------------------------------------------------
+    def forward_batch(self, data_dicts):
+        """``forward`` for a list of sequences -> the list of their results, the same as ``forward`` gives one by one.
+        The frame loop of a pass runs on the device for all sequences at once (csrc/track_seq.hip) through the sequence-ops object
+        (``seq_ops_factory``, default HipSeqTrackOps).  A sequence the batched path cannot hold - a frame with more than
+        ops.TRACK_SEQ_MAX_DET detections, more than ops.TRACK_SEQ_MAX_TRACKS tracks, an assignment that stops with a status - is
+        tracked by ``forward`` inside the same call; ``batched`` / ``fallbacks`` count the sequences that went either way."""
+        data_dicts = list(data_dicts)
+        if self.seq_ops is None:
+            self.seq_ops = self.seq_ops_factory() if self.seq_ops_factory is not None else HipSeqTrackOps()
+        pack = SeqPack(self, data_dicts)
+        if self.reverse_enable and self.stage != 'two_stage' and any(len(fl) for fl in pack.frame_lists):
+            raise DetZeroHipError('REVERSE_TRACKING needs the two_stage association (only_two_stage reads its SECOND_STAGE thresholds)')
+        seqs = [s for s in range(len(data_dicts)) if pack.max_det[s] <= ops.TRACK_SEQ_MAX_DET]
+        fwd = self.seq_ops.forward_pass(self, pack, seqs)
+        seqs = [s for s in seqs if fwd[s] is not None]
+        results = {s: self._tracks_of(fwd[s], pack.frame_lists[s], data_dicts[s], pack.dtypes[s]) for s in seqs}
+        if self.reverse_enable:
+            groups = {s: self._regroup(fwd[s], len(pack.frame_lists[s])) for s in seqs}
+            back = self.seq_ops.reverse_pass(self, pack, seqs, fwd, groups)
+            for s in seqs:
+                if back[s] is None:
+                    del results[s]
+                else:
+                    self._prepend(results[s], self._tracks_of(back[s], pack.frame_lists[s], data_dicts[s], pack.dtypes[s]))
+        self.batched += len(results)
+        self.fallbacks += len(data_dicts) - len(results)
+        return [results[s] if s in results else self.forward(dd) for s, dd in enumerate(data_dicts)]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -536,6 +777,17 @@ class DetZeroTracker:
             data_dict = module.forward(data_dict=data_dict)
         return data_dict
 
+    def forward_batch(self, data_dicts):
+        """``forward`` for a list of sequences: TRACKING for all of them at once (TrackManager.forward_batch), then POST_PROCESS per
+        sequence on the host as ``forward`` does."""
+        outputs = list(data_dicts)
+        for module in self.module_list:
+            if hasattr(module, 'forward_batch'):
+                outputs = module.forward_batch(outputs)
+            else:
+                outputs = [module.forward(data_dict=d) for d in outputs]
+        return outputs
+
 
 __all__ = {'DetZeroTracker': DetZeroTracker}
 
@@ -548,9 +800,11 @@ def _banner(text, total=100):
     return text.center(max(total, len(text)), '-')
 
 
-def run_model(model, dataloader, dataset, workers, cfgs=None, logger=None, assign_ops=None):
-    """Tracks every sequence of every batch, one after another in this process (``workers`` is accepted for the reference's
-    signature; no process pool ever opens the GPU), and writes tracking-<split>-<time>.pkl and drop-<split>-<time>.pkl.  In assign
+def run_model(model, dataloader, dataset, workers, cfgs=None, logger=None, assign_ops=None, batch=None):
+    """Tracks every sequence of every batch in this process and writes tracking-<split>-<time>.pkl and drop-<split>-<time>.pkl.
+    ``workers`` is accepted for the reference's signature; no process pool ever opens the GPU - concurrency comes from ``batch``:
+    None reads the environment variable DZ_TRACK_BATCH; unset or 0 tracks the sequences one after another (``model.forward``),
+    N > 0 sends the sequences of each loader batch through ``model.forward_batch`` in groups of N, a pass of a group in one launch.  In assign
     mode (every split but 'test') each sequence's tracks are matched to the ground truth (track_assign.assign_track_target, with
     ``cfgs.REFINING.IOU_THRESHOLDS``) and the tracking pickle holds the ``{'label', 'unlabel'}`` dicts instead (models/__init__.py:26-56).
     ``assign_ops`` = the ops object of the assignment (default: track_assign.HipTrajOps)."""
@@ -563,9 +817,20 @@ def run_model(model, dataloader, dataset, workers, cfgs=None, logger=None, assig
                                   'config, or run with --split test' % getattr(dataset, 'split', None))
     if logger is not None:
         logger.info(_banner('Running Tracking Module!'))
+    if batch is None:
+        batch = int(os.environ.get('DZ_TRACK_BATCH', '0') or 0)
+    batch = int(batch)
+    if batch < 0:
+        raise DetZeroHipError('run_model: batch %d (0 = one sequence after another, N > 0 = groups of N)' % batch)
     track_data, drop_data = {}, {}
     for seq_names, data_dicts in dataloader:
-        outputs = [model.forward(seq) for seq in data_dicts['detection']]
+        seqs = data_dicts['detection']
+        if batch > 0:
+            outputs = []
+            for i in range(0, len(seqs), batch):
+                outputs += model.forward_batch(seqs[i:i + batch])
+        else:
+            outputs = [model.forward(seq) for seq in seqs]
         if dataset.assign_mode:
             outputs = [track_assign.assign_track_target(item, iou_thresholds=iou_thresholds, ops=assign_ops)
                        for item in zip(data_dicts['detection'], outputs, data_dicts['gt'])]

@@ -1008,6 +1008,70 @@ int dz_track_compact(const dz_track_table *src, int n, const int *removed, int d
 int dz_track_log(const dz_track_table *t, int n, int frame, int *log, long log_n, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A pass of a sequence as one workgroup (csrc/track_seq.hip): grid = sequences; a workgroup walks its sequence's frames in order
+ * and performs per frame what TrackManager.online_track_module (forward) / reverse_tracking_module (reverse = 1) perform through
+ * the entry points above, with the assignment on the device (dz_lsa_batch's core): predict, the cost matrices, the index
+ * bookkeeping of one_stage / two_stage / only_two_stage, update with the stage flag, spawn with ids counted from init_track_id
+ * per sequence, overlap_track_merge + stable removal, the info() log rows, the DEATH_AGE removal.  The per-track and per-pair
+ * arithmetic is the same code as the per-op kernels' (csrc/track_body.h).
+ *
+ * Detections: ONE row buffer `det` for all frames of all sequences; frame g (global index) holds rows [frame_row[g], frame_row[g+1]),
+ * sequence s holds frames [seq_frame[s], seq_frame[s+1]) in time order.  det_flags per row: bit 0 = the detection passes the score
+ * and point thresholds of the first stage, bit 1 = it has enough points (data_association.py:80-87; computed by the host from the
+ * frame's own arrays, whatever their dtype).  one_stage reads no flag.
+ * Storage per sequence s: rows [2 s track_cap, 2 (s+1) track_cap) of `tables` (a table and its spare), rows [s log_cap, (s+1) log_cap)
+ * of `log` with log_count[s] rows written, one slice of ws (dz_track_seq_ws_bytes).  row_cap >= track_cap bounds the rows of an
+ * assignment (reverse: live tracks + the forward rows that join), det_cap the detections of a frame.
+ * overflow[s] (sticky, 0 = the pass is complete): DZ_TRACK_SEQ_OVF_TRACKS / _LOG = the capacity ran out (rerun with more),
+ * _LSA = an assignment stopped with a status (NaN costs), _DESC = an offset list leaves its buffer or a frame / assignment exceeds
+ * det_cap / row_cap.  Such a sequence stops at that frame; the others finish.
+ * Reverse: ext = the forward pass's log (ext_cap rows per sequence, ext_count[s] valid); per global frame g the forward rows of
+ * that frame in track order, split by the host: going_idx[going_at[g] .. going_at[g+1]) join the association as extra rows,
+ * start_idx[start_at[g] .. start_at[g+1]) become reverse tracks after the frame (ids from the rows).  Indices are rows of the
+ * sequence's ext slice; one outside it is never followed.
+ * Limits: classes <= DZ_TRACK_MAX_CLASSES, track_cap <= DZ_TRACK_SEQ_MAX_TRACKS (the sweep's sets in LDS: 2 x 64 words),
+ * det_cap <= DZ_TRACK_SEQ_MAX_DET, row_cap <= 2 x DZ_TRACK_SEQ_MAX_TRACKS (cost slice row_cap x det_cap x 4 <= 32 MiB per sequence);
+ * beyond them, and where 32-bit offsets would overflow: DZ_ERR_UNSUPPORTED.  The workgroup keeps 45 KiB of LDS: rect_overlap's
+ * scratch, the assignment's vectors up to 512 x 512 (larger ones in ws), the sweep's sets. */
+#define DZ_TRACK_SEQ_MAX_TRACKS 4096
+#define DZ_TRACK_SEQ_MAX_DET 1024
+#define DZ_TRACK_SEQ_OVF_TRACKS 1
+#define DZ_TRACK_SEQ_OVF_LOG 2
+#define DZ_TRACK_SEQ_OVF_LSA 4
+#define DZ_TRACK_SEQ_OVF_DESC 8
+typedef struct {
+    int metric;              /* DZ_TRACK_AFF_IOU_BEV, DZ_BOXM_IOU3D, DZ_BOXM_GIOU3D */
+    int distinguish_class;
+    int gate_class;          /* as dz_track_predict */
+    int n_cls;
+    int two_stage;           /* forward: 0 = one_stage, 1 = two_stage; the reverse pass is only_two_stage */
+    int merge_enable;
+    int death_age;           /* -1 = off */
+    int init_track_id;
+    float thr_first[DZ_TRACK_MAX_CLASSES], thr_second[DZ_TRACK_MAX_CLASSES], thr_merge[DZ_TRACK_MAX_CLASSES];
+    float p0, p1, q0, q1, r, dt;
+} dz_track_seq_params;
+typedef struct {
+    const int *det;          /* (n_det_rows, DZ_TRACK_ROW_WORDS) */
+    const int *det_flags;    /* (n_det_rows) */
+    const int *frame_row;    /* (n_frames + 1) */
+    const int *seq_frame;    /* (n_seq + 1) */
+    int n_seq, n_frames, n_det_rows;
+    int track_cap, row_cap, det_cap, log_cap;
+    /* reverse pass only */
+    const int *ext;          /* (n_seq, ext_cap, DZ_TRACK_ROW_WORDS) */
+    const int *ext_count;    /* (n_seq) */
+    const int *going_at;     /* (n_frames + 1) */
+    const int *going_idx;    /* (n_going) */
+    const int *start_at;     /* (n_frames + 1) */
+    const int *start_idx;    /* (n_start) */
+    int ext_cap, n_going, n_start;
+} dz_track_seq_io;
+size_t dz_track_seq_ws_bytes(int n_seq, int track_cap, int row_cap, int det_cap);
+int dz_track_seq_pass(const dz_track_seq_params *p, const dz_track_seq_io *io, int reverse, const dz_track_table *tables, int *log,
+                      int *log_count, int *overflow, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Trajectory-pair table of one sequence (csrc/traj_pair.hip): the sums and counts that assign_track_target
  * (tracking/.../tracking_modules/target_assign.py:44-75) and TrackRecall.eval_single_seq (utils/track_recall.py:187-203 through
  * track_calculation.py:84-123) both take per (ground-truth trajectory, track) pair over the frames the two share.
@@ -1032,6 +1096,44 @@ int dz_traj_pair_table(const float *a_box, const int *a_cls, const int *a_slot, 
 int dz_traj_pair_rows(const float *a_box, const int *a_cls, const int *a_slot, int n_a, int a_rows, const float *b_box,
                       const int *b_cls, const int *b_slot, int n_b, int b_rows, int n_frames, int metric, int distinguish_class,
                       const int *pairs, int n_pairs, float *rows, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Linear sum assignment on the device (csrc/lsa.h, csrc/lsa.hip): GNN_assignment (tracking/.../data_association/distance.py:9-41)
+ * for a batch of independent problems in one launch, one workgroup per problem.  The solver is the shortest-augmenting-path
+ * algorithm of scipy.optimize.linear_sum_assignment: duals and path lengths in double, the fp32 costs widened to double, the
+ * problem transposed when rows > cols.  A cost >= threshold counts as 5000; after the assignment a pair whose cost is not
+ * < threshold is dropped.  Where the optimum is not unique, which optimal assignment comes out is not scipy's choice by contract.
+ *
+ *   cost (cost_len) f32: the problems' row-major matrices, anywhere in the buffer.
+ *   desc (n_problems, DZ_LSA_DESC_WORDS) int64 on the device, per problem:
+ *     [0] rows  [1] cols  [2] offset of its matrix in cost (elements)  [3] offset of its rows in row_to_col / unmatched_rows
+ *     [4] offset of its columns in unmatched_cols  [5] byte offset of its slice in ws, a multiple of 16 (read only when
+ *     max(rows, cols) > 1024: smaller problems keep their vectors in LDS and dz_lsa_ws_bytes is 0 for them)
+ *   row_to_col (rows_len) i32: matched column of each row, -1 = unmatched.
+ *   unmatched_rows (rows_len), unmatched_cols (cols_len) i32: ascending lists at the problem's offsets.
+ *   counts (n_problems, 4) i32: matched pairs, unmatched rows, unmatched columns, status.
+ * Status 0 = solved.  1 = no finite cost left (NaN costs), 2 = a loop bound was reached (at most min(rows, cols) augmentations of at
+ * most max(rows, cols) column scans each: every loop of the kernel is bounded by the problem size), 3 = the descriptor leaves a
+ * buffer or a limit; such a problem writes its counts only (1, 2: all rows and columns unmatched) and the others finish.
+ * A 0 x k or k x 0 problem gives no matches and the full lists.
+ * Workspace: ws holds the slices of the problems with a side > 1024, each of dz_lsa_ws_bytes(rows, cols) bytes at the offset its
+ * descriptor names (back to back: the sum over the problems).  The kernel checks every slice against ws_bytes; a problem whose
+ * slice does not fit gets status 3 and the others finish.  The host checks nothing about ws beyond a null pointer with
+ * ws_bytes > 0: the offsets are on the device.
+ * Limits: each side <= DZ_LSA_MAX_DIM (max_rows / max_cols, the largest sides of the batch, which may come from different
+ * problems; beyond it: DZ_ERR_UNSUPPORTED, as are 2^40 costs or 2^31 rows / columns in one call).  DZ_ERR_INVALID for negative
+ * sizes and null pointers.  n_problems == 0: no launch.
+ * DZ_LSA_MAX_DIM bounds the time one workgroup can hold a compute unit: a problem makes at most min(rows, cols) x max(rows, cols)
+ * column scans, each max(rows, cols) / 256 columns per thread and two barriers, a few microseconds at 4096 columns.  4096 x 4096 is
+ * 1.7e7 scans at the bound, of the order of a minute (an estimate); a side of 32768 would be hours.  Measured on one MI355X, one
+ * problem per call, host time with the counts read: random 4096 x 4096 matrices 2.2 s (5 % of the costs below the threshold) and
+ * 2.8 s (dense, uniform), dense 2048 x 2048 0.37 s. */
+#define DZ_LSA_DESC_WORDS 6
+#define DZ_LSA_MAX_DIM 4096
+size_t dz_lsa_ws_bytes(int rows, int cols);
+int dz_lsa_batch(const float *cost, long long cost_len, const long long *desc, int n_problems, int max_rows, int max_cols, double threshold,
+                 int *row_to_col, int *unmatched_rows, long long rows_len, int *unmatched_cols, long long cols_len, int *counts, void *ws,
+                 size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,13 @@ two-stage IoUBEV association, TRACK_MERGE, REVERSE_TRACKING, DEATH_AGE -1) and t
 
 Input: one seeded sequence (detzero_amd.synth.synth_track_sequence) of --frames frames with about --objects detections each.
 Prints one JSON line: sequences/s and ms per frame-pass of both, the number of tracks, and whether the two results agree.
+
+    python tools/bench_track.py --batch 1 16 64 [--repeats 5]
+
+The batched path (TrackManager.forward_batch, csrc/track_seq.hip) beside the per-sequence path (TrackManager.forward): for every N
+the seeded sequence under N seeds, once through forward() one sequence after another and once through one forward_batch call.
+One JSON line per N: sequences/s of both (host time per call, median of --repeats after a warm-up call), whether tracks, hits
+and boxes agree, and how many sequences ran batched and how many fell back to forward() inside forward_batch.
 """
 import argparse
 import copy
@@ -31,8 +38,49 @@ MODEL = {
 }
 
 
+def bench_batch(cfg, n, args):
+    """n sequences (the seeded sequence under seeds seed .. seed + n - 1) through TrackManager.forward one after another and through
+    TrackManager.forward_batch in one call: host time per call, median of --repeats after a warm-up, results on the host when the
+    clock stops (both return host arrays)."""
+    import numpy as np
+    import torch
+    from detzero_amd.synth import TRACK_EVENTS, synth_track_sequence
+    from detzero_amd.track_models import TrackManager
+
+    seqs = [synth_track_sequence(args.seed + k, args.frames, args.objects, events=TRACK_EVENTS) for k in range(n)]
+
+    def timed(fn):
+        times, result = [], None
+        for k in range(args.repeats + 1):           # the first call is the warm-up
+            work = copy.deepcopy(seqs)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            result = fn(work)
+            torch.cuda.synchronize()
+            if k:
+                times.append(time.perf_counter() - t0)
+        return float(np.median(times)), result
+
+    one = TrackManager(cfg)
+    seq_s, seq_res = timed(lambda work: [one.forward(s) for s in work])
+    many = TrackManager(cfg)
+    bat_s, bat_res = timed(many.forward_batch)
+    same_tracks = all(list(a) == list(b) for a, b in zip(seq_res, bat_res))
+    same_hits = same_tracks and all(np.array_equal(a[t]['hit'], b[t]['hit']) for a, b in zip(seq_res, bat_res) for t in a)
+    same_boxes = same_hits and all(np.array_equal(a[t]['boxes_global'], b[t]['boxes_global']) for a, b in zip(seq_res, bat_res) for t in a)
+    return {'batch': n, 'frames': args.frames, 'repeats': args.repeats, 'tracks': [len(r) for r in bat_res][:4],
+            'per_sequence_path_sequences_per_s': round(n / seq_s, 3), 'per_sequence_path_s_per_call': round(seq_s, 4),
+            'forward_batch_sequences_per_s': round(n / bat_s, 3), 'forward_batch_s_per_call': round(bat_s, 4),
+            'speedup': round(seq_s / bat_s, 3), 'reruns': many.seq_ops.reruns,
+            'batched': many.batched, 'fallbacks': many.fallbacks,       # sequences over all calls (warm-up included): batched path / forward
+            'same_tracks': same_tracks, 'same_hits': same_hits, 'same_boxes_bitwise': same_boxes}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, nargs='+', default=None,
+                    help='compare the per-sequence path with forward_batch on N sequences at once, for every N given')
+    ap.add_argument('--repeats', type=int, default=5, help='--batch: timed calls per path (median), after one warm-up call')
     ap.add_argument('--frames', type=int, default=200)
     ap.add_argument('--objects', type=int, default=150)
     ap.add_argument('--steps', type=int, default=3)
@@ -46,9 +94,14 @@ def main():
     from detzero_amd.synth import TRACK_EVENTS, synth_track_sequence
     from detzero_amd.track_models import TrackManager
 
+    cfg = AttrDict(MODEL)
+    if args.batch:
+        for n in args.batch:
+            print(json.dumps(bench_batch(cfg, n, args)), flush=True)
+        return
+
     seq = synth_track_sequence(args.seed, args.frames, args.objects, events=TRACK_EVENTS)
     dets = sum(len(f['score']) for f in seq.values())
-    cfg = AttrDict(MODEL)
 
     manager = TrackManager(cfg)
     result = manager.forward(copy.deepcopy(seq))            # warm-up: library load, allocator
