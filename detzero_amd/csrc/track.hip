@@ -9,11 +9,14 @@
 // sees cost matrices and a track count only.  Everything is fp32 as in the reference (its arrays are float32 when the detections
 // are), FMA contraction off: the pair metrics are the bodies of box_geom.h and so agree with dz_boxes_iou_bev /
 // dz_boxes_pairwise_metric bit for bit.  Plain C++ only; every store is a vector store.
+// The AB3DMOT filter (kalman_filter/ab3dmot.py) is the second set of per-track kernels below: float64 state in a companion table
+// (dz_track_ab3d), bodies in track_ab3dmot.h; affinity and merge are the same kernels for both filters (they read the float32 box).
 #include "common.h"
 
 #pragma clang fp contract(off)
 
 #include "track_body.h"
+#include "track_ab3dmot.h"
 
 namespace dz {
 
@@ -104,8 +107,61 @@ __global__ __launch_bounds__(256) void k_track_compact(dz_track_table s, int n, 
     if (threadIdx.x == 0) *d_count = (int)base;
 }
 
+// ---- the AB3DMOT filter (bodies: track_ab3dmot.h), one thread per track ----
+__global__ __launch_bounds__(TRK_THREADS) void k_track_ab3d_predict(dz_track_table t, dz_track_ab3d a, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    ab3d_predict_body(t, a, i);
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void k_track_ab3d_update(dz_track_table t, dz_track_ab3d a, int n, const int *__restrict__ det,
+                                                                   const double *__restrict__ det64, int n_det,
+                                                                   const int *__restrict__ match, int m) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int i = match[k * 3 + 0], di = match[k * 3 + 1];
+    if (i < 0 || i >= n || di < 0 || di >= n_det) return;
+    ab3d_update_body(t, a, i, det + di * ROW, det64 + (long)di * AB_NZ);
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void k_track_ab3d_spawn(dz_track_table t, dz_track_ab3d a, int n, const int *__restrict__ src,
+                                                                  const double *__restrict__ src64, int n_src,
+                                                                  const int *__restrict__ src_idx, const int *__restrict__ ids, int m) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int si = src_idx[k];
+    const bool ok = si >= 0 && si < n_src;
+    ab3d_spawn_body(t, a, n + k, src + (ok ? si : 0) * ROW, src64 + (long)(ok ? si : 0) * AB_NZ, ok, ids[k]);
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void k_track_ab3d_log(dz_track_table t, dz_track_ab3d a, int n, int frame, int frame_id,
+                                                                int birth_age, int death_age, int *__restrict__ log,
+                                                                double *__restrict__ log64) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    ab3d_log_body(t, a, i, frame, frame_id, birth_age, death_age, log + (long)i * ROW, log64 + (long)i * 9);
+}
+
+__global__ __launch_bounds__(256) void k_track_ab3d_compact(dz_track_table s, dz_track_ab3d as, int n, const int *__restrict__ removed,
+                                                            int death_age, dz_track_table d, dz_track_ab3d ad, int *__restrict__ d_count) {
+    __shared__ uint32_t scan_s[4];
+    uint32_t base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + threadIdx.x;
+        const bool keep = i < n && track_keep_body(s, i, removed, death_age);
+        uint32_t total;
+        const uint32_t at = base + block_excl_scan_256(keep ? 1u : 0u, scan_s, total);
+        if (keep) ab3d_copy_body(s, as, i, d, ad, (int)at);
+        base += total;
+    }
+    if (threadIdx.x == 0) *d_count = (int)base;
+}
+
 static bool table_ok(const dz_track_table *t, long rows) {
     return t && rows <= t->cap && t->x && t->P && t->Q && t->dt && t->box && t->cls && t->score && t->update_score && t->num_points && t->hit && t->miss && t->id;
+}
+static bool ab3d_ok(const dz_track_ab3d *a, long rows) {
+    return a && rows <= a->stride && a->x && a->P && a->box && a->work && a->hits;
 }
 // rows * 25 floats (P, Q) is the widest offset of a table, rows * ROW words that of a row buffer
 static bool offsets_ok(const char *who, long table_rows, long buffer_rows) {
@@ -259,6 +315,71 @@ int dz_track_log(const dz_track_table *t, int n, int frame, int *log, long log_n
     if (n == 0) return DZ_OK;
     DZ_CHECK_ARG(table_ok(t, n) && log, "dz_track_log: null pointer or n > cap");
     hipLaunchKernelGGL(k_track_log, dim3(ceil_div(n, TRK_THREADS)), dim3(TRK_THREADS), 0, stream, *t, n, frame, log + log_n * ROW);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
+int dz_track_ab3d_predict(const dz_track_table *t, const dz_track_ab3d *a, int n, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(n >= 0, "dz_track_ab3d_predict: negative size");
+    if (!offsets_ok("dz_track_ab3d_predict", n, 0)) return DZ_ERR_UNSUPPORTED;
+    if (n == 0) return DZ_OK;
+    DZ_CHECK_ARG(table_ok(t, n) && ab3d_ok(a, n), "dz_track_ab3d_predict: null pointer or n > cap / stride");
+    hipLaunchKernelGGL(k_track_ab3d_predict, dim3(ceil_div(n, TRK_THREADS)), dim3(TRK_THREADS), 0, stream, *t, *a, n);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
+int dz_track_ab3d_update(const dz_track_table *t, const dz_track_ab3d *a, int n, const int *det, const double *det64, int n_det,
+                         const int *match, int m, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(n >= 0 && n_det >= 0 && m >= 0, "dz_track_ab3d_update: negative size");
+    if (!offsets_ok("dz_track_ab3d_update", n > m ? n : m, n_det)) return DZ_ERR_UNSUPPORTED;
+    if (m == 0) return DZ_OK;
+    DZ_CHECK_ARG(table_ok(t, n) && ab3d_ok(a, n) && det && det64 && match, "dz_track_ab3d_update: null pointer or n > cap / stride");
+    hipLaunchKernelGGL(k_track_ab3d_update, dim3(ceil_div(m, TRK_THREADS)), dim3(TRK_THREADS), 0, stream, *t, *a, n, det, det64, n_det, match,
+                       m);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
+int dz_track_ab3d_spawn(const dz_track_table *t, const dz_track_ab3d *a, int n, const int *src, const double *src64, int n_src,
+                        const int *src_idx, const int *ids, int m, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(n >= 0 && n_src >= 0 && m >= 0, "dz_track_ab3d_spawn: negative size");
+    if (!offsets_ok("dz_track_ab3d_spawn", (long)n + m, n_src)) return DZ_ERR_UNSUPPORTED;
+    if (m == 0) return DZ_OK;
+    DZ_CHECK_ARG(table_ok(t, (long)n + m) && ab3d_ok(a, (long)n + m) && src && src64 && src_idx && ids,
+                 "dz_track_ab3d_spawn: null pointer or n + m > cap / stride");
+    hipLaunchKernelGGL(k_track_ab3d_spawn, dim3(ceil_div(m, TRK_THREADS)), dim3(TRK_THREADS), 0, stream, *t, *a, n, src, src64, n_src, src_idx,
+                       ids, m);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
+int dz_track_ab3d_compact(const dz_track_table *src, const dz_track_ab3d *asrc, int n, const int *removed, int death_age,
+                          const dz_track_table *dst, const dz_track_ab3d *adst, int *d_count, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(n >= 0, "dz_track_ab3d_compact: negative size");
+    if (!offsets_ok("dz_track_ab3d_compact", n, 0)) return DZ_ERR_UNSUPPORTED;
+    DZ_CHECK_ARG(d_count, "dz_track_ab3d_compact: null count");
+    if (n == 0) return fill_u32(d_count, 0u, 1, stream);
+    DZ_CHECK_ARG(table_ok(src, n) && table_ok(dst, n) && src->x != dst->x && ab3d_ok(asrc, n) && ab3d_ok(adst, n) && asrc->x != adst->x,
+                 "dz_track_ab3d_compact: null pointer, n > cap / stride or dst == src");
+    hipLaunchKernelGGL(k_track_ab3d_compact, dim3(1), dim3(256), 0, stream, *src, *asrc, n, removed, death_age, *dst, *adst, d_count);
+    DZ_LAUNCH_CHECK();
+    return DZ_OK;
+}
+
+int dz_track_ab3d_log(const dz_track_table *t, const dz_track_ab3d *a, int n, int frame, int frame_id, int birth_age, int death_age,
+                      int *log, double *log64, long log_n, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DZ_CHECK_ARG(n >= 0 && log_n >= 0, "dz_track_ab3d_log: negative size");
+    if (!offsets_ok("dz_track_ab3d_log", n, log_n + n)) return DZ_ERR_UNSUPPORTED;
+    if (n == 0) return DZ_OK;
+    DZ_CHECK_ARG(table_ok(t, n) && ab3d_ok(a, n) && log && log64, "dz_track_ab3d_log: null pointer or n > cap / stride");
+    hipLaunchKernelGGL(k_track_ab3d_log, dim3(ceil_div(n, TRK_THREADS)), dim3(TRK_THREADS), 0, stream, *t, *a, n, frame, frame_id, birth_age,
+                       death_age, log + log_n * ROW, log64 + log_n * 9);
     DZ_LAUNCH_CHECK();
     return DZ_OK;
 }

@@ -17,6 +17,7 @@
 #pragma clang fp contract(off)
 
 #include "track_body.h"
+#include "track_ab3dmot.h"
 #include "lsa_wg.h"
 
 namespace dz {
@@ -141,15 +142,20 @@ __device__ __forceinline__ void seq_merge(SeqCtx &c, const dz_track_table &a, in
     __syncthreads();
 }
 
-// dz_track_compact's loop on a -> b; returns the new count (the caller swaps the tables)
-__device__ __forceinline__ int seq_compact(SeqCtx &c, const dz_track_table &a, const dz_track_table &b, int n, const int *removed, int death_age) {
+// dz_track_compact's (AB3D: dz_track_ab3d_compact's) loop on a -> b; returns the new count (the caller swaps the tables)
+template <bool AB3D>
+__device__ __forceinline__ int seq_compact(SeqCtx &c, const dz_track_table &a, const dz_track_table &b, const dz_track_ab3d &fa,
+                                           const dz_track_ab3d &fb, int n, const int *removed, int death_age) {
     int base = 0;
     for (int i0 = 0; i0 < n; i0 += SEQ_THREADS) {
         const int i = i0 + c.cx.tid;
         const bool keep = i < n && track_keep_body(a, i, removed, death_age);
         int total;
         const int at = base + c.cx.excl_scan(keep ? 1 : 0, total);
-        if (keep) track_copy_body(a, i, b, at);
+        if (keep) {
+            if (AB3D) ab3d_copy_body(a, fa, i, b, fb, at);
+            else track_copy_body(a, i, b, at);
+        }
         base += total;
     }
     __syncthreads();
@@ -166,7 +172,9 @@ struct SeqArgs {
     size_t ws_one;
 };
 
-template <bool REVERSE, int METRIC>
+// AB3D: the filter is AB3DMOT (track_ab3dmot.h) - its bodies at the five per-track call sites (predict, update, spawn, the two
+// removals' copy, log); the association, the merge verdicts and every capacity check are the same code.  Forward pass only.
+template <bool REVERSE, int METRIC, bool AB3D>
 __device__ __forceinline__ void seq_pass(const SeqArgs &g) {
     __shared__ P2 cp_s[16 * SEQ_THREADS];
     __shared__ float ang_s[16 * SEQ_THREADS];
@@ -185,6 +193,13 @@ __device__ __forceinline__ void seq_pass(const SeqArgs &g) {
     c.w = seq_ws_at(g.ws + (size_t)s * g.ws_one, TC, RC, DC);
     dz_track_table a = table_slice(g.tables, (long)s * 2 * TC, TC), b = table_slice(g.tables, (long)s * 2 * TC + TC, TC);
     int *log = g.log + (size_t)s * io.log_cap * ROW;
+    dz_track_ab3d fa = {}, fb = {};
+    double *log64 = nullptr;
+    if constexpr (AB3D) {
+        fa = ab3d_slice(io.ab3d, (long)s * 2 * TC);
+        fb = ab3d_slice(io.ab3d, (long)s * 2 * TC + TC);
+        log64 = io.log64 + (size_t)s * io.log_cap * 9;
+    }
 
     int n = 0, log_n = 0, id_count = p.init_track_id, ovf = 0;
     const int f0 = io.seq_frame[s], f1 = io.seq_frame[s + 1];
@@ -207,7 +222,10 @@ __device__ __forceinline__ void seq_pass(const SeqArgs &g) {
         const int *flags = io.det_flags + d0;
 
         // ---- predict -----------------------------------------------------------------------------------------------
-        for (int i = tid; i < n; i += SEQ_THREADS) track_predict_body(a, i, p.gate_class);
+        for (int i = tid; i < n; i += SEQ_THREADS) {
+            if (AB3D) ab3d_predict_body(a, fa, i);
+            else track_predict_body(a, i, p.gate_class);
+        }
         for (int i = tid; i < n; i += SEQ_THREADS) { c.w.mdet[i] = -1; c.w.mstage[i] = 0; }
         __syncthreads();
 
@@ -282,14 +300,18 @@ __device__ __forceinline__ void seq_pass(const SeqArgs &g) {
         // ---- update, forward spawn ---------------------------------------------------------------------------------
         for (int i = tid; i < n; i += SEQ_THREADS) {
             const int di = c.w.mdet[i];
-            if (di >= 0 && di < D) track_update_body(a, i, det + di * ROW, c.w.mstage[i], p.r);
+            if (di >= 0 && di < D) {
+                if (AB3D) ab3d_update_body(a, fa, i, det + di * ROW, io.det64 + ((size_t)d0 + di) * AB_NZ);
+                else track_update_body(a, i, det + di * ROW, c.w.mstage[i], p.r);
+            }
         }
         if (!REVERSE) {
             if (n + n_spawn > TC) { ovf = OVF_TRACKS; break; }
             for (int j = tid; j < n_spawn; j += SEQ_THREADS) {
                 const int si = c.w.spawn_list[j];
                 const bool ok = si >= 0 && si < D;
-                track_spawn_body(a, n + j, det + (ok ? si : 0) * ROW, ok, id_count + j, p.p0, p.p1, p.q0, p.q1, p.dt);
+                if (AB3D) ab3d_spawn_body(a, fa, n + j, det + (ok ? si : 0) * ROW, io.det64 + ((size_t)d0 + (ok ? si : 0)) * AB_NZ, ok, id_count + j);
+                else track_spawn_body(a, n + j, det + (ok ? si : 0) * ROW, ok, id_count + j, p.p0, p.p1, p.q0, p.q1, p.dt);
             }
             n += n_spawn;
             id_count += n_spawn;
@@ -299,18 +321,24 @@ __device__ __forceinline__ void seq_pass(const SeqArgs &g) {
         // ---- merge, log --------------------------------------------------------------------------------------------
         if (p.merge_enable && n > 0) {
             seq_merge(c, a, n, g.thr.merge);
-            n = seq_compact(c, a, b, n, c.w.removed, -1);
+            n = seq_compact<AB3D>(c, a, b, fa, fb, n, c.w.removed, -1);
             const dz_track_table t = a; a = b; b = t;
+            if constexpr (AB3D) { const dz_track_ab3d ft = fa; fa = fb; fb = ft; }
         }
         if (log_n + n > io.log_cap) { ovf = OVF_LOG; break; }
-        for (int i = tid; i < n; i += SEQ_THREADS) track_log_body(a, i, ordinal, log + (size_t)(log_n + i) * ROW);
+        for (int i = tid; i < n; i += SEQ_THREADS) {
+            if (AB3D) ab3d_log_body(a, fa, i, ordinal, io.frame_id[gf], p.birth_age, p.death_age, log + (size_t)(log_n + i) * ROW,
+                                    log64 + (size_t)(log_n + i) * 9);
+            else track_log_body(a, i, ordinal, log + (size_t)(log_n + i) * ROW);
+        }
         log_n += n;
 
         if (!REVERSE) {
             if (p.death_age != -1 && n > 0) {
                 __syncthreads();
-                n = seq_compact(c, a, b, n, nullptr, p.death_age);
+                n = seq_compact<AB3D>(c, a, b, fa, fb, n, nullptr, p.death_age);
                 const dz_track_table t = a; a = b; b = t;
+                if constexpr (AB3D) { const dz_track_ab3d ft = fa; fa = fb; fb = ft; }
             }
         } else {
             // the forward tracks that start at this frame become reverse tracks (track_manager.py:247-260)
@@ -332,9 +360,11 @@ __device__ __forceinline__ void seq_pass(const SeqArgs &g) {
 }
 
 template <int METRIC>
-__global__ __launch_bounds__(SEQ_THREADS) void k_track_seq_forward(SeqArgs g) { seq_pass<false, METRIC>(g); }
+__global__ __launch_bounds__(SEQ_THREADS) void k_track_seq_forward(SeqArgs g) { seq_pass<false, METRIC, false>(g); }
 template <int METRIC>
-__global__ __launch_bounds__(SEQ_THREADS) void k_track_seq_reverse(SeqArgs g) { seq_pass<true, METRIC>(g); }
+__global__ __launch_bounds__(SEQ_THREADS) void k_track_seq_reverse(SeqArgs g) { seq_pass<true, METRIC, false>(g); }
+template <int METRIC>
+__global__ __launch_bounds__(SEQ_THREADS) void k_track_seq_forward_ab3d(SeqArgs g) { seq_pass<false, METRIC, true>(g); }
 
 }  // namespace dz
 
@@ -379,6 +409,11 @@ int dz_track_seq_pass(const dz_track_seq_params *p, const dz_track_seq_io *io, i
                 set_error("dz_track_seq_pass: merge threshold %d is %g; the sweep needs thresholds > 0", k, (double)p->thr_merge[k]);
                 return DZ_ERR_UNSUPPORTED;
             }
+    const bool ab3d = p->filter == DZ_TRACK_FILTER_AB3DMOT;
+    if ((p->filter != DZ_TRACK_FILTER_KALMAN && !ab3d) || (ab3d && reverse)) {
+        set_error("dz_track_seq_pass: filter %d%s (0 = KalmanFilter, 1 = AB3DMOT on the forward pass)", p->filter, reverse ? ", reverse pass" : "");
+        return DZ_ERR_UNSUPPORTED;
+    }
     if (io->n_seq == 0) return DZ_OK;
     DZ_CHECK_ARG(io->frame_row && io->seq_frame && log_count && overflow && ws && (log || io->log_cap == 0) &&
                      (io->n_det_rows == 0 || (io->det && io->det_flags)),
@@ -386,6 +421,10 @@ int dz_track_seq_pass(const dz_track_seq_params *p, const dz_track_seq_io *io, i
     DZ_CHECK_ARG(tables && tables->cap >= (long)io->n_seq * 2 * io->track_cap && tables->x && tables->P && tables->Q && tables->dt && tables->box &&
                      tables->cls && tables->score && tables->update_score && tables->num_points && tables->hit && tables->miss && tables->id,
                  "dz_track_seq_pass: the table needs 2 x track_cap rows per sequence");
+    if (ab3d)
+        DZ_CHECK_ARG(io->frame_id && (io->log64 || io->log_cap == 0) && (io->n_det_rows == 0 || io->det64) && io->ab3d.x && io->ab3d.P &&
+                         io->ab3d.box && io->ab3d.work && io->ab3d.hits && io->ab3d.stride >= (long)io->n_seq * 2 * io->track_cap,
+                     "dz_track_seq_pass: AB3DMOT needs det64, frame_id, log64 and a companion of 2 x track_cap rows per sequence");
     if (reverse)
         DZ_CHECK_ARG(io->ext_cap >= 0 && io->n_going >= 0 && io->n_start >= 0 && io->ext_count && io->going_at && io->start_at &&
                          (io->ext || io->ext_cap == 0) && (io->going_idx || io->n_going == 0) && (io->start_idx || io->n_start == 0),
@@ -409,7 +448,8 @@ int dz_track_seq_pass(const dz_track_seq_params *p, const dz_track_seq_io *io, i
     const dim3 grid(io->n_seq), block(SEQ_THREADS);
 #define DZ_SEQ_LAUNCH(M)                                                                                   \
     do {                                                                                                   \
-        if (reverse) hipLaunchKernelGGL(k_track_seq_reverse<M>, grid, block, 0, stream, g);                \
+        if (ab3d) hipLaunchKernelGGL(k_track_seq_forward_ab3d<M>, grid, block, 0, stream, g);              \
+        else if (reverse) hipLaunchKernelGGL(k_track_seq_reverse<M>, grid, block, 0, stream, g);           \
         else hipLaunchKernelGGL(k_track_seq_forward<M>, grid, block, 0, stream, g);                        \
     } while (0)
     switch (p->metric) {

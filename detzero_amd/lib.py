@@ -50,7 +50,13 @@ class TrackTable(ctypes.Structure):
     _fields_ = [(k, c_void_p) for k in ('x', 'P', 'Q', 'dt', 'box', 'cls', 'score', 'update_score', 'num_points', 'hit', 'miss', 'id')] + [('cap', c_int)]
 
 
+class TrackAb3d(ctypes.Structure):
+    """Mirror of ``dz_track_ab3d``: the AB3DMOT filter's float64 companion of a track table."""
+    _fields_ = [(k, c_void_p) for k in ('x', 'P', 'box', 'work', 'hits')] + [('stride', c_int)]
+
+
 _TT = ctypes.POINTER(TrackTable)
+_TA = ctypes.POINTER(TrackAb3d)
 _F8 = c_float * 8          # DZ_TRACK_MAX_CLASSES
 
 
@@ -58,7 +64,8 @@ class TrackSeqParams(ctypes.Structure):
     """Mirror of ``dz_track_seq_params``."""
     _fields_ = [(k, c_int) for k in ('metric', 'distinguish_class', 'gate_class', 'n_cls', 'two_stage', 'merge_enable', 'death_age',
                                      'init_track_id')] + \
-               [(k, _F8) for k in ('thr_first', 'thr_second', 'thr_merge')] + [(k, c_float) for k in ('p0', 'p1', 'q0', 'q1', 'r', 'dt')]
+               [(k, _F8) for k in ('thr_first', 'thr_second', 'thr_merge')] + [(k, c_float) for k in ('p0', 'p1', 'q0', 'q1', 'r', 'dt')] + \
+               [(k, c_int) for k in ('filter', 'birth_age')]
 
 
 class TrackSeqIO(ctypes.Structure):
@@ -66,7 +73,8 @@ class TrackSeqIO(ctypes.Structure):
     _fields_ = [(k, c_void_p) for k in ('det', 'det_flags', 'frame_row', 'seq_frame')] + \
                [(k, c_int) for k in ('n_seq', 'n_frames', 'n_det_rows', 'track_cap', 'row_cap', 'det_cap', 'log_cap')] + \
                [(k, c_void_p) for k in ('ext', 'ext_count', 'going_at', 'going_idx', 'start_at', 'start_idx')] + \
-               [(k, c_int) for k in ('ext_cap', 'n_going', 'n_start')]
+               [(k, c_int) for k in ('ext_cap', 'n_going', 'n_start')] + \
+               [(k, c_void_p) for k in ('det64', 'frame_id', 'log64')] + [('ab3d', TrackAb3d)]
 
 # name -> (restype, argtypes); must list every symbol of include/detzero_hip.h (tests check this)
 _SIGS = {
@@ -283,6 +291,11 @@ _SIGS = {
     'dz_track_merge': (c_int, [_TT, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'dz_track_compact': (c_int, [_TT, c_int, c_void_p, c_int, _TT, c_void_p, c_void_p]),
     'dz_track_log': (c_int, [_TT, c_int, c_int, c_void_p, ctypes.c_long, c_void_p]),
+    'dz_track_ab3d_predict': (c_int, [_TT, _TA, c_int, c_void_p]),
+    'dz_track_ab3d_update': (c_int, [_TT, _TA, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'dz_track_ab3d_spawn': (c_int, [_TT, _TA, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    'dz_track_ab3d_compact': (c_int, [_TT, _TA, c_int, c_void_p, c_int, _TT, _TA, c_void_p, c_void_p]),
+    'dz_track_ab3d_log': (c_int, [_TT, _TA, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p]),
     'dz_traj_pair_table': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dz_traj_pair_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

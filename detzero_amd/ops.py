@@ -1714,6 +1714,117 @@ def track_log_nosync(table, n, frame, log, log_n):
 
 
 # ------------------------------------------------------------------------------------------------
+# the AB3DMOT filter on the same table (csrc/track_ab3dmot.h): float64 state in a companion of the track table
+# ------------------------------------------------------------------------------------------------
+TRACK_FILTER_KALMAN, TRACK_FILTER_AB3DMOT = 0, 1     # DZ_TRACK_FILTER_*
+TRACK_AB3D_WORK = 170                                # DZ_TRACK_AB3D_WORK
+TRACK_AB3D_ROW_DROP, TRACK_AB3D_ROW_BIRTH = 1, 2     # word 15 of a log row
+_AB3D_FIELDS = (('x', 10, torch.float64), ('P', 100, torch.float64), ('box', 9, torch.float64), ('work', TRACK_AB3D_WORK, torch.float64),
+                ('hits', 1, torch.int32))
+
+
+class TrackAb3dTable:
+    """``dz_track_ab3d``: the float64 companion of a TrackTable of the same capacity.  The arrays are (width, cap) - the track index
+    is the fastest one; ``x[:, i]`` is the state of track i, ``P[:, i].reshape(10, 10)`` its covariance."""
+
+    def __init__(self, cap, device=None):
+        self.cap = int(cap)
+        self.device = torch.device(device) if device is not None else _dev()
+        self.arrays = {name: torch.zeros((w, self.cap) if w > 1 else (self.cap,), dtype=dt, device=self.device) for name, w, dt in _AB3D_FIELDS}
+        self.c = L.TrackAb3d(*[L.ptr(self.arrays[name]) for name, _, _ in _AB3D_FIELDS], self.cap)
+
+    def __getattr__(self, name):
+        try:
+            return self.__dict__['arrays'][name]
+        except KeyError:
+            raise AttributeError(name)
+
+    def grown(self, n, need):
+        """This companion if ``need`` rows fit, else a new one of at least twice the capacity holding rows [0, n)."""
+        if need <= self.cap:
+            return self
+        cap = self.cap
+        while cap < need:
+            cap *= 2
+        new = TrackAb3dTable(cap, self.device)
+        for name in ('x', 'P', 'box', 'hits'):
+            new.arrays[name][..., :n].copy_(self.arrays[name][..., :n])
+        return new
+
+
+def _track_f64(a, rows, width, what):
+    L.require_cuda(a)
+    if a.dtype != torch.float64 or a.dim() != 2 or a.shape[1] != width or a.shape[0] < rows or not a.is_contiguous():
+        raise L.DetZeroHipError('%s: a contiguous (>= %d, %d) float64 device tensor, got %s %s' % (what, rows, width, tuple(a.shape), a.dtype))
+    return a
+
+
+def _ab3d_pair(table, ab, rows, what):
+    if ab.cap < rows or table.cap < rows:
+        raise L.DetZeroHipError('%s: %d rows in a table of %d / a companion of %d' % (what, rows, table.cap, ab.cap))
+
+
+def track_ab3d_predict_nosync(table, ab, n):
+    """AB3DMOT.predict on rows [0, n) in place; table.box[:n] = the float32 rounding of the predicted boxes."""
+    _ab3d_pair(table, ab, n, 'track_ab3d_predict')
+    L.check(L.load().dz_track_ab3d_predict(ctypes.byref(table.c), ctypes.byref(ab.c), int(n), L.stream()), 'dz_track_ab3d_predict')
+
+
+def track_ab3d_update_nosync(table, ab, n, det, det64, match):
+    """AB3DMOT.update for match (m,3) int32 rows [table row, det row, stage (ignored)]; det64 (D,7) float64 = the measurements."""
+    det, n_det = _track_rows(det, 'track_ab3d_update')
+    _ab3d_pair(table, ab, n, 'track_ab3d_update')
+    L.require_cuda(match)
+    if match.dtype != torch.int32 or match.dim() != 2 or match.shape[1] != 3:
+        raise L.DetZeroHipError('track_ab3d_update: match is (m, 3) int32')
+    det64 = _track_f64(det64, n_det, 7, 'track_ab3d_update: det64')
+    rc = L.load().dz_track_ab3d_update(ctypes.byref(table.c), ctypes.byref(ab.c), int(n), L.ptr(det), L.ptr(det64), n_det, L.ptr(match),
+                                       match.shape[0], L.stream())
+    L.check(rc, 'dz_track_ab3d_update')
+
+
+def track_ab3d_spawn_nosync(table, ab, n, src, src64, src_idx, ids):
+    """Append len(src_idx) AB3DMOT tracks at rows [n, n + m) from rows of the row buffer ``src`` and their measurements ``src64``."""
+    src, n_src = _track_rows(src, 'track_ab3d_spawn')
+    src_idx, ids = _track_idx(src_idx, 'track_ab3d_spawn'), _track_idx(ids, 'track_ab3d_spawn')
+    if ids.shape[0] != src_idx.shape[0]:
+        raise L.DetZeroHipError('track_ab3d_spawn: %d ids for %d rows' % (ids.shape[0], src_idx.shape[0]))
+    _ab3d_pair(table, ab, n + src_idx.shape[0], 'track_ab3d_spawn')
+    src64 = _track_f64(src64, n_src, 7, 'track_ab3d_spawn: src64')
+    rc = L.load().dz_track_ab3d_spawn(ctypes.byref(table.c), ctypes.byref(ab.c), int(n), L.ptr(src), L.ptr(src64), n_src, L.ptr(src_idx),
+                                      L.ptr(ids), src_idx.shape[0], L.stream())
+    L.check(rc, 'dz_track_ab3d_spawn')
+
+
+def track_ab3d_compact_nosync(src, asrc, n, removed, death_age, dst, adst):
+    """track_compact_nosync carrying the companion: survivors into (dst, adst); returns the new count as a (1,) int32 device tensor."""
+    if removed is not None:
+        L.require_cuda(removed)
+        if removed.dtype != torch.int32 or removed.shape[0] < n:
+            raise L.DetZeroHipError('track_ab3d_compact: removed is (n,) int32')
+    _ab3d_pair(src, asrc, n, 'track_ab3d_compact')
+    _ab3d_pair(dst, adst, n, 'track_ab3d_compact')
+    d_count = torch.empty((1,), dtype=torch.int32, device=src.device)
+    rc = L.load().dz_track_ab3d_compact(ctypes.byref(src.c), ctypes.byref(asrc.c), int(n), L.ptr(removed), int(death_age), ctypes.byref(dst.c),
+                                        ctypes.byref(adst.c), L.ptr(d_count), L.stream())
+    L.check(rc, 'dz_track_ab3d_compact')
+    return d_count
+
+
+def track_ab3d_log_nosync(table, ab, n, frame, frame_id, birth_age, death_age, log, log64, log_n):
+    """info() of rows [0, n) into rows [log_n, log_n + n) of the row buffer ``log`` and of ``log64`` (rows, 9) float64; word 15 of a
+    row carries the output rule's verdict (TRACK_AB3D_ROW_DROP) and the birth flag (TRACK_AB3D_ROW_BIRTH)."""
+    log, rows = _track_rows(log, 'track_ab3d_log')
+    if log_n + n > rows:
+        raise L.DetZeroHipError('track_ab3d_log: rows %d..%d of a log of %d' % (log_n, log_n + n, rows))
+    _ab3d_pair(table, ab, n, 'track_ab3d_log')
+    log64 = _track_f64(log64, log_n + n, 9, 'track_ab3d_log: log64')
+    rc = L.load().dz_track_ab3d_log(ctypes.byref(table.c), ctypes.byref(ab.c), int(n), int(frame), int(frame_id), int(birth_age),
+                                    int(death_age), L.ptr(log), L.ptr(log64), int(log_n), L.stream())
+    L.check(rc, 'dz_track_ab3d_log')
+
+
+# ------------------------------------------------------------------------------------------------
 # trajectory-pair table (csrc/traj_pair.hip): ground-truth trajectories against tracks over a whole sequence
 # ------------------------------------------------------------------------------------------------
 def _traj_sides(a_box, a_cls, a_slot, b_box, b_cls, b_slot, n_cls, what):
@@ -1795,14 +1906,14 @@ TRACK_SEQ_OVF_TRACKS, TRACK_SEQ_OVF_LOG, TRACK_SEQ_OVF_LSA, TRACK_SEQ_OVF_DESC =
 
 
 def track_seq_params(metric, distinguish_class, gate_class, n_cls, two_stage, merge_enable, death_age, init_track_id, thr_first, thr_second,
-                     thr_merge, p, q, r, dt):
+                     thr_merge, p, q, r, dt, filter=TRACK_FILTER_KALMAN, birth_age=1):
     """``dz_track_seq_params`` from the tracker's configuration (threshold lists may be shorter than 8 or None)."""
     def thr(v):
         v = [float(x) for x in (v if v is not None else [])][:TRACK_MAX_CLASSES]
         return L._F8(*(v + [0.] * (TRACK_MAX_CLASSES - len(v))))
     return L.TrackSeqParams(int(metric), int(bool(distinguish_class)), int(gate_class), int(n_cls), int(bool(two_stage)), int(bool(merge_enable)),
                             int(death_age), int(init_track_id), thr(thr_first), thr(thr_second), thr(thr_merge), float(p[0]), float(p[1]),
-                            float(q[0]), float(q[1]), float(r), float(dt))
+                            float(q[0]), float(q[1]), float(r), float(dt), int(filter), int(birth_age))
 
 
 def _seq_i32(t, n, what):
@@ -1816,10 +1927,12 @@ def _seq_i32(t, n, what):
     return t
 
 
-def track_seq_pass_nosync(params, det, det_flags, frame_row, seq_frame, track_cap, row_cap, det_cap, log_cap, reverse=None):
+def track_seq_pass_nosync(params, det, det_flags, frame_row, seq_frame, track_cap, row_cap, det_cap, log_cap, reverse=None, ab3d=None):
     """One pass (forward, or reverse when ``reverse`` = (ext (S, ext_cap, 16), ext_count (S,), going_at, going_idx, start_at,
     start_idx)) of every sequence in one launch.  det (rows, 16) i32, det_flags (rows,), frame_row (frames + 1,), seq_frame (S + 1,)
-    on the device.  -> (log (S, log_cap, 16) i32, log_count (S,) i32, overflow (S,) i32) on the device; nothing is read here."""
+    on the device.  -> (log (S, log_cap, 16) i32, log_count (S,) i32, overflow (S,) i32) on the device; nothing is read here.
+    With params.filter = TRACK_FILTER_AB3DMOT: ``ab3d`` = (det64 (rows, 7) f64, frame_id (frames,) i32) on the device, and a fourth
+    result, log64 (S, log_cap, 9) f64."""
     lib = L.load()
     det, n_rows = _track_rows(det, 'track_seq_pass')
     n_seq, n_frames = seq_frame.shape[0] - 1, frame_row.shape[0] - 1
@@ -1837,12 +1950,23 @@ def track_seq_pass_nosync(params, det, det_flags, frame_row, seq_frame, track_ca
         io.going_idx, io.start_idx = L.ptr(_seq_i32(going_idx, 0, 'going_idx')), L.ptr(_seq_i32(start_idx, 0, 'start_idx'))
         io.ext_cap, io.n_going, io.n_start = ext.shape[1], going_idx.numel(), start_idx.numel()
     tables = TrackTable(max(n_seq * 2 * int(track_cap), 1), dev)
+    log64 = None
+    if params.filter == TRACK_FILTER_AB3DMOT:
+        if ab3d is None or reverse is not None:
+            raise L.DetZeroHipError('track_seq_pass: the AB3DMOT filter needs (det64, frame_id) and has no reverse pass')
+        det64, frame_id = ab3d
+        companion = TrackAb3dTable(tables.cap, dev)
+        log64 = torch.empty((max(n_seq, 1), max(int(log_cap), 1), 9), dtype=torch.float64, device=dev)
+        io.det64 = L.ptr(_track_f64(det64, n_rows, 7, 'track_seq_pass: det64')) if n_rows else None
+        io.frame_id, io.log64, io.ab3d = L.ptr(_seq_i32(frame_id, n_frames, 'frame_id')), L.ptr(log64), companion.c
     log = torch.empty((max(n_seq, 1), max(int(log_cap), 1), TRACK_ROW_WORDS), dtype=torch.int32, device=dev)     # rows below log_count are written
     state = torch.zeros((2, max(n_seq, 1)), dtype=torch.int32, device=dev)
     ws = _ws(lib.dz_track_seq_ws_bytes(n_seq, int(track_cap), int(row_cap), int(det_cap)))
     rc = lib.dz_track_seq_pass(ctypes.byref(params), ctypes.byref(io), 0 if reverse is None else 1, ctypes.byref(tables.c), L.ptr(log),
                                L.ptr(state[0]), L.ptr(state[1]), L.ptr(ws), ws.numel(), L.stream())
     L.check(rc, 'dz_track_seq_pass')
+    if log64 is not None:
+        return log[:n_seq], state[0, :n_seq], state[1, :n_seq], log64[:n_seq]
     return log[:n_seq], state[0, :n_seq], state[1, :n_seq]
 
 

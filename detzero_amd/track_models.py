@@ -5,6 +5,7 @@ Mirror of the reference's tracking package, same class names and config keys:
   * ``tracking/detzero_track/models/tracking_modules/track_manager.py:12-310``   TrackManager
   * ``.../data_association/data_association.py:9-155``, ``distance.py:9-41``     two_stage / one_stage / only_two_stage, GNN_assignment
   * ``.../kalman_filter/kalman_filter.py:6-146``                                 KalmanFilter (as kernels: csrc/track.hip)
+  * ``.../kalman_filter/ab3dmot.py:9-149``                                       AB3DMOT (as kernels: csrc/track_ab3dmot.h)
   * ``.../post_process.py:10-138``                                               PostProcessor
   * ``tracking/detzero_track/models/{__init__,detzero_tracker}.py``              DetZeroTracker, build_model, run_model
   * ``tracking/detzero_track/datasets/{__init__,dataset,waymo_dataset}.py``      WaymoTrackDataset, build_dataloader
@@ -36,7 +37,21 @@ its box wherever the reference reads them, so the table stores the box only.
 Assign mode (every split but 'test') matches each sequence's tracks to the ground truth: track_assign.py, on the trajectory-pair
 kernel (csrc/traj_pair.hip).
 
-Not covered (DetZeroHipError naming it): FILTER.NAME AB3DMOT and DISTANCE_METHOD IoU2D.
+``FILTER.NAME: AB3DMOT`` (tools/cfgs/tk_model_cfgs/waymo_ab3dmot.yaml) is the reference's baseline filter: filterpy's
+``KalmanFilter(dim_x=10, dim_z=7)`` over the state [x y z l w h theta vx vy vz], float64, with its own heading corrections, and with
+it the BIRTH_AGE / DEATH_AGE output rule of track_manager.py:201-205.  On the device the filter's state lives in a float64
+companion of the track table (``ops.TrackAb3dTable``, csrc/track_ab3dmot.h); the table's float32 box is the rounding of the float64
+one, which is what the reference's association sees (track_manager.py:146-151).  A frame's detections then travel as the row buffer
+plus a (D, 7) float64 array, the log as rows plus an (L, 9) float64 array; rows that fail the output rule are marked in the row's
+word 15 on the device and dropped when the log is fetched.  The results are as the reference's: ``boxes_global`` float64 (n, 9) (a
+track whose only row is its birth row keeps the reference's float32), ``num_points`` -1, ``hit`` in {0, 1}.  The config's P, Q, R and
+DELTA_T are ignored as the reference's constructor ignores them, the stage flag of a match too (an update is always a full update).
+Not mirrored: the reference wraps the matched detection's heading in place in the caller's array (ab3dmot.py:128); the caller's
+detections are left alone here.  Refused: AB3DMOT with ``REVERSE_TRACKING.ENABLE: True`` - the filter ignores ``delta_t``, so a
+reverse pass would run a forward-time motion model; no shipped config combines them.
+
+Not covered (DetZeroHipError naming it): DISTANCE_METHOD IoU2D.  It is unusable in the reference itself: ``one_stage`` hands
+``IoU2D_dis_mat`` seven columns and it asserts four (distance.py:76).
 """
 import os
 import pickle
@@ -50,6 +65,8 @@ from .lib import DetZeroHipError
 
 ROW_WORDS = ops.TRACK_ROW_WORDS
 ROW_SCORE, ROW_HIT, ROW_NPTS, ROW_ID, ROW_CLS, ROW_FRAME = 9, 10, 11, 12, 13, 14      # include/detzero_hip.h: the row buffer's words
+ROW_AB3D = 15                                            # AB3DMOT log rows: ops.TRACK_AB3D_ROW_DROP | ops.TRACK_AB3D_ROW_BIRTH
+FILTERS = ('KalmanFilter', 'AB3DMOT')
 AFF_IOU_BEV, AFF_IOU3D, AFF_GIOU3D = ops.TRACK_AFF_IOU_BEV, ops.BOXM_IOU3D, ops.BOXM_GIOU3D
 # ('GIoU3D_dis_mat' is the key data_association/__init__.py:14 registers for GIoU3D_dis_mat)
 METRICS = {'IoUBEV': AFF_IOU_BEV, 'IoU3D': AFF_IOU3D, 'GIoU3D': AFF_GIOU3D, 'GIoU3D_dis_mat': AFF_GIOU3D}
@@ -110,11 +127,21 @@ class HipTrackOps:
       compact(merged, death_age) -> new n
       log(frame)                   info() of every live track
       fetch_log() -> (rows (L,16) int32 host array, handle)
+
+    ``filter='AB3DMOT'`` (csrc/track_ab3dmot.h; no ``ext``, no 'ext' spawn): the same calls, with
+      set_detections(rows, boxes64)                 boxes64 = the (D,7) float64 measurements of the rows
+      update(match, r) / spawn('det', idx, ids, p, q, dt)     r, p, q, dt and the stage column are ignored, as in the reference
+      log(frame, frame_id, birth_age, death_age)    frame_id = the frame's key as an integer; the output rule marks word 15
+      fetch_log()                                   the rows that passed the output rule only
+      fetch_log_boxes() -> (L,9) float64            the boxes of the rows the last fetch_log returned
     """
 
-    def __init__(self, device=None, init_cap=256):
+    def __init__(self, device=None, init_cap=256, filter='KalmanFilter'):
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         self.init_cap = init_cap
+        if filter not in FILTERS:
+            raise DetZeroHipError('HipTrackOps: filter %s (%s)' % (filter, ', '.join(FILTERS)))
+        self.ab3d = filter == 'AB3DMOT'
         self.start_pass()
 
     def _dev(self, a, dtype=np.int32):
@@ -128,11 +155,24 @@ class HipTrackOps:
         self.ext = ext
         self.det = None
         self.removed = None
+        if self.ab3d:
+            if ext is not None:
+                raise DetZeroHipError('HipTrackOps: the AB3DMOT filter has no reverse pass')
+            self.ftable, self.fspare = ops.TrackAb3dTable(self.init_cap, self.device), ops.TrackAb3dTable(self.init_cap, self.device)
+            self.log64 = torch.zeros((4 * self.init_cap, 9), dtype=torch.float64, device=self.device)
+            self.det64 = None
+            self.kept = None
 
-    def set_detections(self, rows):
+    def set_detections(self, rows, boxes64=None):
         self.det = self._dev(rows) if len(rows) else torch.zeros((0, ROW_WORDS), dtype=torch.int32, device=self.device)
+        if self.ab3d:
+            if boxes64 is None or np.shape(boxes64) != (len(rows), 7):
+                raise DetZeroHipError('track set_detections: the AB3DMOT filter takes the (D,7) float64 measurements beside the rows')
+            self.det64 = self._dev(boxes64, np.float64).reshape(-1, 7)
 
     def predict(self, gate_class):
+        if self.ab3d:
+            return ops.track_ab3d_predict_nosync(self.table, self.ftable, self.n)
         ops.track_predict_nosync(self.table, self.n, gate_class)
 
     def affinity(self, row_idx, col_idx, metric, distinguish_class, thr):
@@ -148,20 +188,31 @@ class HipTrackOps:
         return out.cpu().numpy()
 
     def update(self, match, r):
-        if len(match):
+        if len(match) and self.ab3d:
+            if np.min(match[:, 1]) < 0 or np.max(match[:, 1]) >= self.det.shape[0] or np.min(match[:, 0]) < 0 or np.max(match[:, 0]) >= self.n:
+                raise DetZeroHipError('track update: a match outside the table (%d) / the frame (%d)' % (self.n, self.det.shape[0]))
+            ops.track_ab3d_update_nosync(self.table, self.ftable, self.n, self.det, self.det64, self._dev(match))
+        elif len(match):
             ops.track_update_nosync(self.table, self.n, self.det, self._dev(match), r)
 
     def spawn(self, source, idx, ids, p, q, dt):
         m = len(idx)
         if m == 0:
             return
+        if self.ab3d and source != 'det':
+            raise DetZeroHipError('track spawn: the AB3DMOT filter spawns from detections only')
         src = self.det if source == 'det' else self.ext
         if src is None or np.min(idx) < 0 or np.max(idx) >= src.shape[0]:
             raise DetZeroHipError('track spawn: source row outside its buffer')
         grown = self.table.grown(self.n, self.n + m)
         if grown is not self.table:
             self.table, self.spare = grown, ops.TrackTable(grown.cap, self.device)
-        ops.track_spawn_nosync(self.table, self.n, src, self._dev(idx), self._dev(ids), p, q, dt)
+            if self.ab3d:
+                self.ftable, self.fspare = self.ftable.grown(self.n, self.n + m), ops.TrackAb3dTable(grown.cap, self.device)
+        if self.ab3d:
+            ops.track_ab3d_spawn_nosync(self.table, self.ftable, self.n, src, self.det64, self._dev(idx), self._dev(ids))
+        else:
+            ops.track_spawn_nosync(self.table, self.n, src, self._dev(idx), self._dev(ids), p, q, dt)
         self.n += m
 
     def merge(self, thr):
@@ -170,12 +221,17 @@ class HipTrackOps:
     def compact(self, merged, death_age):
         if self.n == 0:
             return 0
-        d_count = ops.track_compact_nosync(self.table, self.n, self.removed if merged else None, death_age, self.spare)
+        if self.ab3d:
+            d_count = ops.track_ab3d_compact_nosync(self.table, self.ftable, self.n, self.removed if merged else None, death_age, self.spare,
+                                                    self.fspare)
+            self.ftable, self.fspare = self.fspare, self.ftable
+        else:
+            d_count = ops.track_compact_nosync(self.table, self.n, self.removed if merged else None, death_age, self.spare)
         self.table, self.spare = self.spare, self.table
         self.n = int(d_count.item())
         return self.n
 
-    def log(self, frame):
+    def log(self, frame, frame_id=None, birth_age=None, death_age=None):
         if self.log_n + self.n > self.log_buf.shape[0]:
             rows = self.log_buf.shape[0]
             while rows < self.log_n + self.n:
@@ -183,12 +239,29 @@ class HipTrackOps:
             new = torch.zeros((rows, ROW_WORDS), dtype=torch.int32, device=self.device)
             new[:self.log_n].copy_(self.log_buf[:self.log_n])
             self.log_buf = new
-        ops.track_log_nosync(self.table, self.n, frame, self.log_buf, self.log_n)
+            if self.ab3d:
+                new64 = torch.zeros((rows, 9), dtype=torch.float64, device=self.device)
+                new64[:self.log_n].copy_(self.log64[:self.log_n])
+                self.log64 = new64
+        if self.ab3d:
+            if frame_id is None or birth_age is None or death_age is None:
+                raise DetZeroHipError('track log: the AB3DMOT filter takes the frame id and the BIRTH_AGE / DEATH_AGE of its output rule')
+            ops.track_ab3d_log_nosync(self.table, self.ftable, self.n, frame, frame_id, birth_age, death_age, self.log_buf, self.log64,
+                                      self.log_n)
+        else:
+            ops.track_log_nosync(self.table, self.n, frame, self.log_buf, self.log_n)
         self.log_n += self.n
 
     def fetch_log(self):
         handle = self.log_buf[:self.log_n]
-        return handle.cpu().numpy(), handle
+        rows = handle.cpu().numpy()
+        if self.ab3d:       # the rows that fail the output rule are dropped here: no extra read while the pass runs
+            self.kept = (rows[:, ROW_AB3D] & ops.TRACK_AB3D_ROW_DROP) == 0
+            return rows[self.kept], None
+        return rows, handle
+
+    def fetch_log_boxes(self):
+        return self.log64[:self.log_n].cpu().numpy()[self.kept]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -205,12 +278,16 @@ class SeqPack:
       seq_frame        (S + 1,) first frame of every sequence
       max_det[s]       the largest frame of the sequence
       dtypes[s]        the result dtypes of score / num_points (TrackManager._note_dtypes)
+    With the AB3DMOT filter also
+      boxes64          (N,7) float64: the measurements of the rows
+      frame_ids        (frames,) int32: every frame's key as an integer (the output rule reads it, not the ordinal)
     """
 
     def __init__(self, mgr, data_dicts):
         self.data_dicts = data_dicts
         self.frame_lists = [sorted(list(dd.keys()), key=int) for dd in data_dicts]
         rows, flags, frame_row, seq_frame = [], [], [0], [0]
+        boxes64, frame_ids = [], []
         self.max_det, self.dtypes = [], []
         for dd, frame_list in zip(data_dicts, self.frame_lists):
             dtypes = {'score': np.float32, 'num_points': np.int64}
@@ -225,6 +302,9 @@ class SeqPack:
                     f = np.asarray(first).astype(np.int32).reshape(-1) | (np.asarray(enough).astype(np.int32).reshape(-1) << 1)
                 rows.append(r)
                 flags.append(f)
+                if mgr.ab3dmot:
+                    boxes64.append(mgr._frame_boxes64(det))
+                    frame_ids.append(int(frm_id))
                 frame_row.append(frame_row[-1] + len(cls))
                 biggest = max(biggest, len(cls))
                 mgr._note_dtypes(dtypes, det)
@@ -235,6 +315,8 @@ class SeqPack:
         self.flags = np.concatenate(flags) if flags else np.zeros(0, dtype=np.int32)
         self.frame_row = np.array(frame_row, dtype=np.int64)
         self.seq_frame = np.array(seq_frame, dtype=np.int64)
+        self.boxes64 = np.concatenate(boxes64, axis=0) if boxes64 else np.zeros((0, 7), dtype=np.float64)
+        self.frame_ids = np.array(frame_ids, dtype=np.int32)
 
     def frames_of(self, s):
         return range(int(self.seq_frame[s]), int(self.seq_frame[s + 1]))
@@ -257,6 +339,15 @@ class SeqPack:
                 np.concatenate(flags) if flags else np.zeros(0, dtype=np.int32), np.array(frame_row, dtype=np.int32),
                 np.array(seq_frame, dtype=np.int32))
 
+    def subset64(self, seqs):
+        """AB3DMOT: (boxes64, frame_ids) of the listed sequences, in the order of ``subset``."""
+        boxes, ids = [np.zeros((0, 7), dtype=np.float64)], [np.zeros(0, dtype=np.int32)]
+        for s in seqs:
+            f0, f1 = int(self.seq_frame[s]), int(self.seq_frame[s + 1])
+            boxes.append(self.boxes64[self.frame_row[f0]:self.frame_row[f1]])
+            ids.append(self.frame_ids[f0:f1])
+        return np.concatenate(boxes, axis=0), np.concatenate(ids)
+
 
 class HipSeqTrackOps:
     """forward_batch's two passes on csrc/track_seq.hip.
@@ -270,12 +361,16 @@ class HipSeqTrackOps:
     Capacities (tracks and log rows per sequence) start from the detections' counts, or from ``track_cap`` / ``log_cap``; a sequence
     that runs out of one sets its overflow word and is rerun, alone with the others that overflowed, with that capacity doubled
     (tracks: up to ops.TRACK_SEQ_MAX_TRACKS, which is tried before a sequence is given up; ``reruns`` counts the extra launches).
-    Per pass and launch: one upload of the packed buffers, one read of the counts and overflow words, one read of the log rows."""
+    Per pass and launch: one upload of the packed buffers, one read of the counts and overflow words, one read of the log rows.
+
+    With the AB3DMOT filter (the manager's choice; forward pass only) the rows that fail the output rule are dropped from what
+    forward_pass returns, and ``boxes64[s]`` holds the (L,9) float64 boxes of the rows returned for sequence s."""
 
     def __init__(self, device=None, track_cap=None, log_cap=None):
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         self.track_cap, self.log_cap = track_cap, log_cap
         self.reruns = 0
+        self.boxes64 = {}
 
     def _dev(self, a):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
@@ -285,7 +380,8 @@ class HipSeqTrackOps:
         two = mgr.stage == 'two_stage'
         return ops.track_seq_params(mgr.metric, mgr.distinguish_class, mgr.gate_class, len(mgr.class_names), two, mgr.merge_enable,
                                     mgr.death_age, mgr.init_track_id, mgr.dist_thr, mgr.second_dist_thr if two else None,
-                                    mgr.merge_thr if mgr.merge_enable else None, mgr.p, mgr.q, mgr.r, mgr.delta_t)
+                                    mgr.merge_thr if mgr.merge_enable else None, mgr.p, mgr.q, mgr.r, mgr.delta_t,
+                                    ops.TRACK_FILTER_AB3DMOT if mgr.ab3dmot else ops.TRACK_FILTER_KALMAN, mgr.birth_age)
 
     def _run(self, mgr, pack, seqs, track_cap, log_cap, reverse_of=None):
         """Launch until no sequence overflows: {s: rows or None}.  reverse_of(sub) -> (the reverse pass's device lists, extra rows)."""
@@ -299,15 +395,28 @@ class HipSeqTrackOps:
             rows, flags, frame_row, seq_frame = pack.subset(todo)
             det_cap = max([pack.max_det[s] for s in todo] + [1])
             reverse, extra = reverse_of(todo) if reverse_of is not None else (None, 0)
-            log, count, overflow = ops.track_seq_pass_nosync(params, self._dev(rows).reshape(-1, ROW_WORDS), self._dev(flags), self._dev(frame_row),
-                                                             self._dev(seq_frame), track_cap, track_cap + extra, det_cap, log_cap, reverse)
+            log64 = None
+            if mgr.ab3dmot:
+                boxes64, frame_ids = pack.subset64(todo)
+                ab3d = (torch.from_numpy(np.ascontiguousarray(boxes64)).to(self.device),
+                        self._dev(frame_ids if len(frame_ids) else np.zeros(1, dtype=np.int32)))
+                log, count, overflow, log64 = ops.track_seq_pass_nosync(params, self._dev(rows).reshape(-1, ROW_WORDS), self._dev(flags),
+                                                                        self._dev(frame_row), self._dev(seq_frame), track_cap, track_cap + extra,
+                                                                        det_cap, log_cap, reverse, ab3d)
+            else:
+                log, count, overflow = ops.track_seq_pass_nosync(params, self._dev(rows).reshape(-1, ROW_WORDS), self._dev(flags), self._dev(frame_row),
+                                                                 self._dev(seq_frame), track_cap, track_cap + extra, det_cap, log_cap, reverse)
             state = torch.stack([count, overflow]).cpu().numpy()
             keep = torch.from_numpy((np.arange(log_cap)[None, :] < state[0][:, None]).reshape(-1)).to(self.device)
             got = log.reshape(-1, ROW_WORDS)[keep].cpu().numpy()
+            got64 = log64.reshape(-1, 9)[keep].cpu().numpy() if log64 is not None else None
             at, again, grow_tracks, grow_log = 0, [], False, False
             for k, s in enumerate(todo):
                 n, ovf = int(state[0, k]), int(state[1, k])
-                if ovf == 0:
+                if ovf == 0 and got64 is not None:
+                    passed = (got[at:at + n, ROW_AB3D] & ops.TRACK_AB3D_ROW_DROP) == 0
+                    out[s], self.boxes64[s] = got[at:at + n][passed], got64[at:at + n][passed]
+                elif ovf == 0:
                     out[s] = got[at:at + n]
                 elif ovf & (ops.TRACK_SEQ_OVF_LSA | ops.TRACK_SEQ_OVF_DESC):
                     out[s] = None
@@ -330,6 +439,7 @@ class HipSeqTrackOps:
         return out
 
     def forward_pass(self, mgr, pack, seqs):
+        self.boxes64 = {}
         if not seqs:
             return {}
         most = max([pack.max_det[s] for s in seqs] + [1])
@@ -393,10 +503,15 @@ class TrackManager:
         self.fallbacks = 0          # ... and those it handed to forward (beyond a limit, or an assignment stopped with a status)
 
         flt = _lower(model_cfg.FILTER)
-        if flt['name'] != 'KalmanFilter':
-            raise DetZeroHipError('FILTER.NAME %s is not provided by the HIP tracker (KalmanFilter only)' % flt['name'])
+        if flt['name'] not in FILTERS:
+            raise DetZeroHipError('FILTER.NAME %s is not provided by the HIP tracker (%s)' % (flt['name'], ', '.join(FILTERS)))
+        self.filter_name = flt['name']
+        self.ab3dmot = self.filter_name == 'AB3DMOT'
+        # (AB3DMOT's own dimensions are 10 / 7 whatever the config says; the shipped waymo_ab3dmot.yaml carries 5 / 3 as the other one)
         if flt.get('x_dim', 5) != 5 or flt.get('z_dim', 3) != 3:
-            raise DetZeroHipError('KalmanFilter with X_DIM %s / Z_DIM %s (5 / 3 only)' % (flt.get('x_dim'), flt.get('z_dim')))
+            raise DetZeroHipError('%s with X_DIM %s / Z_DIM %s (5 / 3 only)' % (self.filter_name, flt.get('x_dim'), flt.get('z_dim')))
+        if self.ab3dmot and ops_factory is None:
+            self.ops_factory = lambda: HipTrackOps(filter='AB3DMOT')
         self.p, self.q = tuple(flt.get('p', [1, 1])), tuple(flt.get('q', [1, 1]))
         self.r, self.delta_t = float(flt.get('r', 1)), float(flt.get('delta_t', 0.1))
 
@@ -435,6 +550,9 @@ class TrackManager:
                 raise DetZeroHipError('TRACK_MERGE has no threshold for %s' % ', '.join(missing))
             self.merge_thr = [float(by_name[n]) for n in self.class_names]
         self.reverse_enable = bool(_lower(model_cfg.REVERSE_TRACKING)['enable'])
+        if self.ab3dmot and self.reverse_enable:
+            raise DetZeroHipError('FILTER.NAME AB3DMOT with REVERSE_TRACKING.ENABLE: the filter ignores delta_t, so a reverse pass would '
+                                  'run a forward-time motion model; the HIP tracker provides AB3DMOT on the forward pass only')
 
     # ---- a frame's detections ------------------------------------------------------------------
     def _codes(self, names):
@@ -453,9 +571,20 @@ class TrackManager:
         npts = np.zeros(len(cls), dtype=np.int32) if one else det_data['num_points']
         return cls, det_rows(det_data['boxes_global'], cls, det_data['score'], npts)
 
+    @staticmethod
+    def _frame_boxes64(det_data):
+        """AB3DMOT: the frame's measurements, (D,7) float64 (a copy: the caller's array is never written)."""
+        d = len(det_data['name'])
+        if d == 0:
+            return np.zeros((0, 7), dtype=np.float64)
+        return np.array(np.asarray(det_data['boxes_global'], dtype=np.float64).reshape(d, -1)[:, :7], dtype=np.float64)
+
     def _upload(self, ops, det_data):
         cls, rows = self._frame_rows(det_data)
-        ops.set_detections(rows)
+        if self.ab3dmot:
+            ops.set_detections(rows, self._frame_boxes64(det_data))
+        else:
+            ops.set_detections(rows)
         return cls
 
     # ---- association (data_association.py) -------------------------------------------------------
@@ -502,13 +631,19 @@ class TrackManager:
         return second, trk_free, second_det[det_free]
 
     # ---- the two per-frame modules ---------------------------------------------------------------
-    def _merge_and_log(self, ops, ordinal):
+    def _merge_and_log(self, ops, ordinal, frm_id=None):
         if self.merge_enable and ops.n:
             ops.merge(self.merge_thr)
             ops.compact(True, -1)
-        ops.log(ordinal)        # every live track: the BIRTH_AGE / DEATH_AGE output rule of track_manager.py:202-205 is AB3DMOT's
+        if self.ab3dmot:        # the BIRTH_AGE / DEATH_AGE output rule of track_manager.py:202-205 reads int(frame id), not the ordinal
+            ops.log(ordinal, int(frm_id), self.birth_age, self.death_age)
+        else:
+            ops.log(ordinal)    # every live track
 
-    def online_track_module(self, ops, ordinal, det_data, track_id_count):
+    def online_track_module(self, ops, ordinal, det_data, track_id_count, frm_id=None):
+        """``frm_id``: the frame's key in the sequence dict (AB3DMOT's output rule needs it; the ordinal otherwise)."""
+        if frm_id is None:
+            frm_id = ordinal
         n = ops.n
         ops.predict(self.gate_class)
         cls = self._upload(ops, det_data)
@@ -521,7 +656,7 @@ class TrackManager:
         ops.update(np.concatenate((matched, stage[:, None]), axis=1), self.r)
         ids = np.arange(track_id_count, track_id_count + len(det_unmatch))
         ops.spawn('det', det_unmatch, ids, self.p, self.q, self.delta_t)
-        self._merge_and_log(ops, ordinal)
+        self._merge_and_log(ops, ordinal, frm_id)
         if self.death_age != -1:
             ops.compact(False, self.death_age)
         return track_id_count + len(det_unmatch)
@@ -543,8 +678,9 @@ class TrackManager:
         ops.spawn('ext', fwd_rows[fwd_start], fwd_ids[fwd_start], self.p, self.q, REVERSE_DELTA_T)
 
     # ---- log rows -> the reference's object-level structure -------------------------------------------
-    def _tracks_of(self, rows, frame_list, data_dict, dtypes):
-        """{track id: dict} in the order in which the ids first appear in the log."""
+    def _tracks_of(self, rows, frame_list, data_dict, dtypes, boxes64=None):
+        """{track id: dict} in the order in which the ids first appear in the log.  ``boxes64`` (AB3DMOT): the (L,9) float64 boxes of
+        the rows - the results' boxes_global; num_points is then the reference's Python -1 (int64)."""
         out = {}
         if len(rows) == 0:
             return out
@@ -555,13 +691,19 @@ class TrackManager:
             sel = np.flatnonzero(ids == ids[at])
             r = rows[sel]
             frames = [frame_list[o] for o in r[:, ROW_FRAME]]
+            if boxes64 is None:
+                boxes = r[:, :9].copy().view(np.float32)
+            elif np.all(r[:, ROW_AB3D] & ops.TRACK_AB3D_ROW_BIRTH):       # np.array of the constructor's float32 bbox alone
+                boxes = boxes64[sel].astype(np.float32)
+            else:
+                boxes = boxes64[sel].copy()
             out[int(ids[at])] = {
-                'boxes_global': r[:, :9].copy().view(np.float32),
+                'boxes_global': boxes,
                 'name': np.array([names[c] for c in r[:, ROW_CLS]]),
                 'score': r[:, ROW_SCORE].copy().view(np.float32).astype(dtypes['score']),
                 'sample_idx': np.array(frames),
                 'hit': r[:, ROW_HIT].astype(np.int64),
-                'num_points': r[:, ROW_NPTS].astype(dtypes['num_points']),
+                'num_points': r[:, ROW_NPTS].astype(dtypes['num_points'] if boxes64 is None else np.int64),
                 'obj_ids': r[:, ROW_ID].astype(np.int64),
                 'pose': np.array([data_dict[f]['pose'] for f in frames]),
             }
@@ -606,10 +748,10 @@ class TrackManager:
         track_id_count = self.init_track_id
         dtypes = {'score': np.float32, 'num_points': np.int64}
         for ordinal, frm_id in enumerate(frame_list):
-            track_id_count = self.online_track_module(ops, ordinal, data_dict[frm_id], track_id_count)
+            track_id_count = self.online_track_module(ops, ordinal, data_dict[frm_id], track_id_count, frm_id)
             self._note_dtypes(dtypes, data_dict[frm_id])
         rows, handle = ops.fetch_log()
-        tk_result = self._tracks_of(rows, frame_list, data_dict, dtypes)
+        tk_result = self._tracks_of(rows, frame_list, data_dict, dtypes, ops.fetch_log_boxes() if self.ab3dmot else None)
         if not self.reverse_enable:
             return tk_result
 
@@ -637,7 +779,8 @@ class TrackManager:
         seqs = [s for s in range(len(data_dicts)) if pack.max_det[s] <= ops.TRACK_SEQ_MAX_DET]
         fwd = self.seq_ops.forward_pass(self, pack, seqs)
         seqs = [s for s in seqs if fwd[s] is not None]
-        results = {s: self._tracks_of(fwd[s], pack.frame_lists[s], data_dicts[s], pack.dtypes[s]) for s in seqs}
+        results = {s: self._tracks_of(fwd[s], pack.frame_lists[s], data_dicts[s], pack.dtypes[s],
+                                      self.seq_ops.boxes64[s] if self.ab3dmot else None) for s in seqs}
         if self.reverse_enable:
             groups = {s: self._regroup(fwd[s], len(pack.frame_lists[s])) for s in seqs}
             back = self.seq_ops.reverse_pass(self, pack, seqs, fwd, groups)

@@ -1008,6 +1008,54 @@ int dz_track_compact(const dz_track_table *src, int n, const int *removed, int d
 int dz_track_log(const dz_track_table *t, int n, int frame, int *log, long log_n, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The AB3DMOT filter (kalman_filter/ab3dmot.py:9-149 over filterpy's KalmanFilter(dim_x=10, dim_z=7)) on the same table, float64.
+ * dz_track_ab3d is the companion of a dz_track_table: the same rows, the filter's float64 state beside them.  Its arrays are laid
+ * out with the TRACK INDEX FASTEST: element k of track i is at [k * stride + i] (a wave's accesses coalesce); `stride` is the
+ * number of rows allocated.  The dz_track_table beside it carries box (the float32 rounding of the float64 box: what
+ * dz_track_affinity and dz_track_merge read), cls, score, update_score, num_points (-1), hit, miss, id; its x / P / Q / dt are not used.
+ *   state [x y z l w h theta vx vy vz]; F = I + ones at (0,7), (1,8), (2,9); H = the first seven states; R = I;
+ *   P0 = diag(10 x7, 10000 x3); Q = diag(1 x7, 0.01 x3).  The config's P, Q, R and DELTA_T are not read, as in the reference.
+ * Detections come as a row buffer (score, class, the float32 box) plus a row-major (rows, 7) float64 array of the measurements;
+ * the log is a row buffer plus a row-major (rows, 9) float64 array of the boxes.  Word 15 of a log row: bit 0
+ * (DZ_TRACK_AB3D_ROW_DROP) = the row fails the output rule of track_manager.py:202-205 and is not part of the results, bit 1
+ * (DZ_TRACK_AB3D_ROW_BIRTH) = the row is the track's birth row (its box is the detection rounded to float32). */
+#define DZ_TRACK_FILTER_KALMAN 0
+#define DZ_TRACK_FILTER_AB3DMOT 1
+#define DZ_TRACK_AB3D_WORK 170      /* update's working matrices per track: K (10,7) and (I - K H) P (10,10) */
+#define DZ_TRACK_AB3D_ROW_DROP 1
+#define DZ_TRACK_AB3D_ROW_BIRTH 2
+typedef struct {
+    double *x;           /* (10, stride)  */
+    double *P;           /* (100, stride) row-major 10 x 10 per track */
+    double *box;         /* (9, stride)   the box info() reports: x[0:9], or the birth row's float32 detection */
+    double *work;        /* (DZ_TRACK_AB3D_WORK, stride) scratch of dz_track_ab3d_update; not carried by compact */
+    int *hits;           /* (stride)      updates + 1 */
+    int stride;
+} dz_track_ab3d;
+/* AB3DMOT.predict (ab3dmot.py:88-109) on rows [0, n): x = F x, P = F P F^T + Q as three row adds and three column adds, theta
+ * wrapped once into [-pi, pi), miss += 1, hit = 0, box = x[0:9]. */
+int dz_track_ab3d_predict(const dz_track_table *t, const dz_track_ab3d *a, int n, void *stream);
+/* AB3DMOT.update (ab3dmot.py:111-149) for m matches, one thread each: match (m,3) int32 [table row, det row, stage]; the stage is
+ * ignored (an update is always a full update, hit = 1).  hits += 1, miss = 0, score and class from the row; theta of state and
+ * measurement wrapped, the obtuse-angle flip and the >= 3 pi / 2 branch; then y = z - H x, S = H P H^T + R (the leading 7 x 7 block
+ * plus I, factored by Cholesky), K = P H^T S^-1, x += K y, P = (I - K H) P (I - K H)^T + K K^T; theta wrapped; box = x[0:9].
+ * det64 (n_det, 7) float64 row-major: the measurements.  A table row may appear in one match only. */
+int dz_track_ab3d_update(const dz_track_table *t, const dz_track_ab3d *a, int n, const int *det, const double *det64, int n_det,
+                         const int *match, int m, void *stream);
+/* Append m tracks at rows [n, n + m) (ab3dmot.py:13-86): x = [src64 row, 0, 0, 0], P = P0, hits = 1, hit = 1, miss = 0,
+ * num_points = -1, score / class from the row, id = ids[k], box = the row's float32 box with two zero columns. */
+int dz_track_ab3d_spawn(const dz_track_table *t, const dz_track_ab3d *a, int n, const int *src, const double *src64, int n_src,
+                        const int *src_idx, const int *ids, int m, void *stream);
+/* dz_track_compact that carries x, P, box and hits of the companion too (adst: another companion, never asrc). */
+int dz_track_ab3d_compact(const dz_track_table *src, const dz_track_ab3d *asrc, int n, const int *removed, int death_age,
+                          const dz_track_table *dst, const dz_track_ab3d *adst, int *d_count, void *stream);
+/* dz_track_log plus the float64 boxes into rows [log_n, log_n + n) of log64 (rows, 9), and word 15: DZ_TRACK_AB3D_ROW_DROP unless
+ * (hits >= birth_age or frame_id < birth_age) and miss < death_age (frame_id = the frame's key as an integer, `frame` its
+ * ordinal), DZ_TRACK_AB3D_ROW_BIRTH on a birth row. */
+int dz_track_ab3d_log(const dz_track_table *t, const dz_track_ab3d *a, int n, int frame, int frame_id, int birth_age, int death_age,
+                      int *log, double *log64, long log_n, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A pass of a sequence as one workgroup (csrc/track_seq.hip): grid = sequences; a workgroup walks its sequence's frames in order
  * and performs per frame what TrackManager.online_track_module (forward) / reverse_tracking_module (reverse = 1) perform through
  * the entry points above, with the assignment on the device (dz_lsa_batch's core): predict, the cost matrices, the index
@@ -1032,7 +1080,10 @@ int dz_track_log(const dz_track_table *t, int n, int frame, int *log, long log_n
  * Limits: classes <= DZ_TRACK_MAX_CLASSES, track_cap <= DZ_TRACK_SEQ_MAX_TRACKS (the sweep's sets in LDS: 2 x 64 words),
  * det_cap <= DZ_TRACK_SEQ_MAX_DET, row_cap <= 2 x DZ_TRACK_SEQ_MAX_TRACKS (cost slice row_cap x det_cap x 4 <= 32 MiB per sequence);
  * beyond them, and where 32-bit offsets would overflow: DZ_ERR_UNSUPPORTED.  The workgroup keeps 45 KiB of LDS: rect_overlap's
- * scratch, the assignment's vectors up to 512 x 512 (larger ones in ws), the sweep's sets. */
+ * scratch, the assignment's vectors up to 512 x 512 (larger ones in ws), the sweep's sets.
+ * filter = DZ_TRACK_FILTER_AB3DMOT (forward pass only; reverse = 1 is DZ_ERR_UNSUPPORTED): predict / update / spawn / log / the two
+ * removals are those of dz_track_ab3d_* (csrc/track_ab3dmot.h) on io->ab3d beside `tables`, with io->det64, io->frame_id and
+ * io->log64; the log rows carry dz_track_ab3d_log's word 15. */
 #define DZ_TRACK_SEQ_MAX_TRACKS 4096
 #define DZ_TRACK_SEQ_MAX_DET 1024
 #define DZ_TRACK_SEQ_OVF_TRACKS 1
@@ -1050,6 +1101,8 @@ typedef struct {
     int init_track_id;
     float thr_first[DZ_TRACK_MAX_CLASSES], thr_second[DZ_TRACK_MAX_CLASSES], thr_merge[DZ_TRACK_MAX_CLASSES];
     float p0, p1, q0, q1, r, dt;
+    int filter;              /* DZ_TRACK_FILTER_KALMAN (0), DZ_TRACK_FILTER_AB3DMOT: the bodies of dz_track_ab3d_*; forward pass only */
+    int birth_age;           /* AB3DMOT: the output rule of dz_track_ab3d_log */
 } dz_track_seq_params;
 typedef struct {
     const int *det;          /* (n_det_rows, DZ_TRACK_ROW_WORDS) */
@@ -1066,6 +1119,11 @@ typedef struct {
     const int *start_at;     /* (n_frames + 1) */
     const int *start_idx;    /* (n_start) */
     int ext_cap, n_going, n_start;
+    /* AB3DMOT only */
+    const double *det64;     /* (n_det_rows, 7) the measurements of `det`'s rows */
+    const int *frame_id;     /* (n_frames) every frame's key as an integer */
+    double *log64;           /* (n_seq, log_cap, 9) the float64 boxes of `log`'s rows */
+    dz_track_ab3d ab3d;      /* companion of `tables`: stride >= 2 x track_cap x n_seq, sequence s at the same rows */
 } dz_track_seq_io;
 size_t dz_track_seq_ws_bytes(int n_seq, int track_cap, int row_cap, int det_cap);
 int dz_track_seq_pass(const dz_track_seq_params *p, const dz_track_seq_io *io, int reverse, const dz_track_table *tables, int *log,
