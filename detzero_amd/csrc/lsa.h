@@ -13,6 +13,10 @@
 // Every thread makes the same calls in the same order: all branches around them depend on values every thread holds alike.
 // HostCtx below is the one-thread form; csrc/lsa.hip has the workgroup form.  This header includes nothing of HIP.
 //
+// The row step is a function of its own (lsa_augment_row) with two drivers: lsa_assign, GNN_assignment as described above, and
+// lsa_assign_prefix, which takes the cost as a functor, never transposes and shows its caller the assignment after every row
+// (csrc/eval_match.hip reads the matching of every score cutoff off one solve that way).
+//
 // Bounds (no loop here waits on data): at most R = min(rows, cols) augmentations, at most C = max(rows, cols) column scans per
 // augmentation (a scan marks one more column), at most R steps back along a path.  A problem that would pass one of them, or that
 // has no finite column left (a NaN cost), stops with a status and all of its rows unmatched.
@@ -76,6 +80,101 @@ DZ_LSA_HD inline double lsa_cost_at(const float *cost, int cols, bool transposed
     return c >= threshold ? LSA_MASKED : c;
 }
 
+// The same cost as a functor (row, column) -> double of the solver's R x C problem: what lsa_assign hands to lsa_augment_row.
+struct LsaMatrixCost {
+    const float *cost;
+    int cols;
+    bool transposed;
+    double threshold;
+    DZ_LSA_HD double operator()(int i, int j) const { return lsa_cost_at(cost, cols, transposed, i, j, threshold); }
+};
+
+// Zero duals, nothing assigned: the state before row 0 enters.  Ends on a sync.
+template <class Ctx>
+DZ_LSA_HD void lsa_reset(Ctx &cx, int R, int C, LsaWork w) {
+    for (int j = cx.tid; j < C; j += cx.n) { w.v[j] = 0.0; w.row4col[j] = -1; w.scanned[j] = 0; }
+    for (int i = cx.tid; i < R; i += cx.n) { w.u[i] = 0.0; w.col4row[i] = -1; }
+    cx.sync();
+}
+
+// One augmentation: row `cur` enters an optimal assignment of rows 0..cur-1 (rows >= cur are unassigned) over C columns, and an
+// optimal assignment of rows 0..cur is left in w.col4row / w.row4col.  cost_of(i, j) is the solver-space cost.  `word` is one int
+// every thread can read and thread 0 writes (the path walk's verdict goes through it).  Returns the status, the same in every
+// thread; the last thing every thread did is a sync.
+template <class Ctx, class Cost>
+DZ_LSA_HD int lsa_augment_row(Ctx &cx, const Cost &cost_of, int cur, int C, LsaWork w, int *word) {
+    const int mark = cur + 1;
+    for (int j = cx.tid; j < C; j += cx.n) w.spc[j] = LSA_INF;
+    cx.sync();
+    int i = cur, sink = -1;
+    double min_val = 0.0;
+    for (int step = 0; step < C; ++step) {
+        const double ui = w.u[i];
+        double best = LSA_INF;
+        int key = 0x7FFFFFFF;
+        for (int j = cx.tid; j < C; j += cx.n) {        // a thread owns its columns: spc / path are written by the owner only
+            if (w.scanned[j] == mark) continue;
+            const double r = min_val + cost_of(i, j) - ui - w.v[j];
+            double s = w.spc[j];
+            if (r < s) { w.path[j] = i; w.spc[j] = r; s = r; }
+            const int k = j | (w.row4col[j] == -1 ? 0 : LSA_KEY_ASSIGNED);      // among equals: a free column first (scipy), then the lowest
+            if (s < best || (s == best && k < key)) { best = s; key = k; }
+        }
+        cx.argmin(best, key);
+        if (!(best < LSA_INF)) return LSA_INFEASIBLE;
+        min_val = best;
+        const int j = key & (LSA_KEY_ASSIGNED - 1);
+        const int owner = w.row4col[j];                 // (written between augmentations only)
+        if (cx.tid == 0) w.scanned[j] = mark;           // argmin met every thread after its scan: nobody reads scanned[] now
+        cx.sync();
+        if (owner == -1) { sink = j; break; }
+        i = owner;
+    }
+    if (sink < 0) return LSA_BOUND;
+    // duals: SR = {cur} and the owners of the scanned columns, SC = the scanned columns (the sink's term is zero)
+    for (int j = cx.tid; j < C; j += cx.n) {
+        if (w.scanned[j] != mark) continue;
+        const double d = min_val - w.spc[j];
+        if (j != sink) w.u[w.row4col[j]] += d;          // col4row[that row] == j: one column per row
+        w.v[j] -= d;
+    }
+    cx.sync();
+    if (cx.tid == 0) {
+        w.u[cur] += min_val;
+        int j = sink, done = 0;
+        for (int k = 0; k <= cur; ++k) {                // the path holds at most cur + 1 rows
+            const int r = w.path[j];
+            w.row4col[j] = r;
+            const int prev = w.col4row[r];
+            w.col4row[r] = j;
+            j = prev;
+            if (r == cur) { done = 1; break; }
+        }
+        *word = done ? LSA_OK : LSA_BOUND;
+    }
+    cx.sync();
+    const int status = *word;
+    cx.sync();
+    return status;
+}
+
+// Rows enter in order and the caller looks at every prefix: after row n - 1 the state is an optimal assignment of rows 0..n-1
+// (the invariant of the shortest-augmenting-path method), so one solve passes through the optimum of every leading row set.
+// cost_of(row, col) -> double; never transposed: the caller guarantees rows <= cols, and `w` is lsa_work_at(base, rows, cols).
+// After each row on_prefix(cx, rows_done, col4row) is called from every thread, behind a sync; col4row[0..rows_done) is then
+// that prefix's assignment (every row has a column).  on_prefix may sync, alike in every thread, and must not write `w`.
+// Returns the status, the same in every thread; rows after a failed one are not entered.
+template <class Ctx, class Cost, class OnPrefix>
+DZ_LSA_HD int lsa_assign_prefix(Ctx &cx, const Cost &cost_of, int rows, int cols, LsaWork w, int *word, OnPrefix &on_prefix) {
+    lsa_reset(cx, rows, cols, w);
+    int status = LSA_OK;
+    for (int cur = 0; cur < rows && status == LSA_OK; ++cur) {
+        status = lsa_augment_row(cx, cost_of, cur, cols, w, word);
+        if (status == LSA_OK) on_prefix(cx, cur + 1, (const int *)w.col4row);
+    }
+    return status;
+}
+
 // cost (rows, cols) fp32 row-major.  Outputs: row_to_col (rows) = matched column or -1; unmatched_rows (rows) / unmatched_cols
 // (cols): ascending lists, their lengths in counts[1] / counts[2]; counts[0] = matched pairs; counts[3] = status.
 // Returns the status (the same in every thread).
@@ -85,67 +184,12 @@ DZ_LSA_HD int lsa_assign(Ctx &cx, const float *cost, int rows, int cols, double 
     const bool transposed = rows > cols;
     const int R = transposed ? cols : rows, C = transposed ? rows : cols;
     int status = LSA_OK;
+    const LsaMatrixCost cost_of{cost, cols, transposed, threshold};
 
-    for (int j = cx.tid; j < C; j += cx.n) { w.v[j] = 0.0; w.row4col[j] = -1; w.scanned[j] = 0; }
-    for (int i = cx.tid; i < R; i += cx.n) { w.u[i] = 0.0; w.col4row[i] = -1; }
     for (int i = cx.tid; i < rows; i += cx.n) row_to_col[i] = -1;
-    cx.sync();
+    lsa_reset(cx, R, C, w);
 
-    for (int cur = 0; cur < R && status == LSA_OK; ++cur) {
-        const int mark = cur + 1;
-        for (int j = cx.tid; j < C; j += cx.n) w.spc[j] = LSA_INF;
-        cx.sync();
-        int i = cur, sink = -1;
-        double min_val = 0.0;
-        for (int step = 0; step < C; ++step) {
-            const double ui = w.u[i];
-            double best = LSA_INF;
-            int key = 0x7FFFFFFF;
-            for (int j = cx.tid; j < C; j += cx.n) {        // a thread owns its columns: spc / path are written by the owner only
-                if (w.scanned[j] == mark) continue;
-                const double r = min_val + lsa_cost_at(cost, cols, transposed, i, j, threshold) - ui - w.v[j];
-                double s = w.spc[j];
-                if (r < s) { w.path[j] = i; w.spc[j] = r; s = r; }
-                const int k = j | (w.row4col[j] == -1 ? 0 : LSA_KEY_ASSIGNED);      // among equals: a free column first (scipy), then the lowest
-                if (s < best || (s == best && k < key)) { best = s; key = k; }
-            }
-            cx.argmin(best, key);
-            if (!(best < LSA_INF)) { status = LSA_INFEASIBLE; break; }
-            min_val = best;
-            const int j = key & (LSA_KEY_ASSIGNED - 1);
-            const int owner = w.row4col[j];                 // (written between augmentations only)
-            if (cx.tid == 0) w.scanned[j] = mark;           // argmin met every thread after its scan: nobody reads scanned[] now
-            cx.sync();
-            if (owner == -1) { sink = j; break; }
-            i = owner;
-        }
-        if (status != LSA_OK) break;
-        if (sink < 0) { status = LSA_BOUND; break; }
-        // duals: SR = {cur} and the owners of the scanned columns, SC = the scanned columns (the sink's term is zero)
-        for (int j = cx.tid; j < C; j += cx.n) {
-            if (w.scanned[j] != mark) continue;
-            const double d = min_val - w.spc[j];
-            if (j != sink) w.u[w.row4col[j]] += d;          // col4row[that row] == j: one column per row
-            w.v[j] -= d;
-        }
-        cx.sync();
-        if (cx.tid == 0) {
-            w.u[cur] += min_val;
-            int j = sink, done = 0;
-            for (int k = 0; k <= cur; ++k) {                // the path holds at most cur + 1 rows
-                const int r = w.path[j];
-                w.row4col[j] = r;
-                const int prev = w.col4row[r];
-                w.col4row[r] = j;
-                j = prev;
-                if (r == cur) { done = 1; break; }
-            }
-            counts[3] = done ? LSA_OK : LSA_BOUND;
-        }
-        cx.sync();
-        status = counts[3];
-        cx.sync();
-    }
+    for (int cur = 0; cur < R && status == LSA_OK; ++cur) status = lsa_augment_row(cx, cost_of, cur, C, w, counts + 3);
 
     // GNN_assignment's filter, in the original orientation; path becomes column -> row
     for (int j = cx.tid; j < cols; j += cx.n) w.path[j] = -1;

@@ -306,6 +306,9 @@ _SIGS = {
     'dz_lsa_ws_bytes': (c_size_t, [c_int, c_int]),
     'dz_lsa_batch': (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, ctypes.c_longlong,
                              c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dz_eval_match_ws_bytes': (c_size_t, [c_int, c_int]),
+    'dz_eval_match_counts': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

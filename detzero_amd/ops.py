@@ -2040,6 +2040,92 @@ def linear_assignment_batch(costs, threshold=1.):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# detection matching at every score cutoff (csrc/eval_match.hip): the count table behind Waymo-style AP / APH
+# ------------------------------------------------------------------------------------------------
+EVAL_CUTOFFS = 101                 # DZ_EVAL_CUTOFFS
+EVAL_IOU_THR = (0., .7, .5, .5, .5)               # waymo_eval_detection.py:111-115, indexed by object type
+EVAL_BOX_TYPES = {'3d': 0, 'bev': 1}              # DZ_EVAL_BOX_*
+EVAL_SCHEMES = {'atomic': 0, 'slots': 1}          # DZ_EVAL_ACC_*
+EVAL_STATUS = {1: 'a descriptor leaves its buffers or a limit', 2: 'a solve stopped at a loop bound',
+               3: 'a descriptor leaves its buffers or a limit; a solve stopped at a loop bound'}
+EVAL_HA_ONE = float(1 << 32)                      # the table's HA column is fixed point with 32 fraction bits
+
+
+def eval_match_counts_nosync(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shards, box_type='3d', iou_thr=EVAL_IOU_THR,
+                             scheme='atomic', table=None, ws_bytes=None):
+    """pred_box (Np,7) f32 / pred_score (Np,) f32: the predictions grouped by problem, in descending score order inside each;
+    gt_box (Ng,7) f32 / gt_difficulty (Ng,) i32 grouped by problem.  desc: host int64 array (n,6) of
+    [first prediction, P, first ground truth, G, shard, object type] - the workspace offsets are added here - or a device tensor
+    (n,7) in the library's layout with ``ws_bytes`` given.  -> (table (n_shards,2,101,4) int64 [TP, FP, FN, HA * 2^32], status (1,)
+    i32) on the device; ``table`` (zeros when None) is added to.  No host read: the caller looks at status."""
+    lib = L.load()
+    L.require_cuda(pred_box, pred_score, gt_box, gt_difficulty)
+    if pred_box.dtype != torch.float32 or pred_box.dim() != 2 or pred_box.shape[1] != 7 or gt_box.dtype != torch.float32 or \
+            gt_box.dim() != 2 or gt_box.shape[1] != 7:
+        raise L.DetZeroHipError('eval_match_counts: boxes are (N,7) float32, got %s %s / %s %s'
+                                % (tuple(pred_box.shape), pred_box.dtype, tuple(gt_box.shape), gt_box.dtype))
+    if pred_score.dtype != torch.float32 or tuple(pred_score.shape) != (pred_box.shape[0],) or gt_difficulty.dtype != torch.int32 or \
+            tuple(gt_difficulty.shape) != (gt_box.shape[0],):
+        raise L.DetZeroHipError('eval_match_counts: pred_score is (Np,) float32 and gt_difficulty (Ng,) int32')
+    if box_type not in EVAL_BOX_TYPES or scheme not in EVAL_SCHEMES or len(iou_thr) != 5:
+        raise L.DetZeroHipError('eval_match_counts: box_type %r / scheme %r / %d thresholds' % (box_type, scheme, len(iou_thr)))
+    dev = pred_box.device
+    if torch.is_tensor(desc):
+        L.require_cuda(desc)
+        if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 7 or ws_bytes is None:
+            raise L.DetZeroHipError('eval_match_counts: a device descriptor table is (n,7) int64 and comes with ws_bytes')
+        d_desc, n, max_dim = desc, desc.shape[0], 0
+    else:
+        desc = np.asarray(desc, dtype=np.int64).reshape(-1, 6)
+        n = desc.shape[0]
+        dims = desc[:, 1] + desc[:, 3]
+        max_dim = int(dims.max()) if n else 0
+        full = np.zeros((n, 7), dtype=np.int64)
+        full[:, :6] = desc
+        if max_dim <= LSA_MAX_DIM and n and desc[:, [1, 3]].min() >= 0:        # (a larger problem is refused below by the library)
+            # the library's size, vectorised: weights, cutoff indices and (beyond 1024 columns) the solver's vectors, to 256 bytes
+            p, g = desc[:, 1], desc[:, 3]
+            c = p + g
+            work = np.where(c > 1024, ((2 * c + p) * 8 + (3 * c + p) * 4 + 15) // 16 * 16, 0)
+            need = np.where(p > 0, ((p * g * 4 + 15) // 16 * 16 + (p * 4 + 15) // 16 * 16 + work + 255) // 256 * 256, 0)
+            full[:, 6] = np.cumsum(need) - need
+            ws_bytes = int(need.sum())
+        else:
+            ws_bytes = 0
+        d_desc = torch.from_numpy(full).to(dev) if n else None
+    if table is None:
+        table = torch.zeros((max(int(n_shards), 1), 2, EVAL_CUTOFFS, 4), dtype=torch.int64, device=dev)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (int(n_shards), 2, EVAL_CUTOFFS, 4) or not table.is_cuda or not table.is_contiguous():
+        raise L.DetZeroHipError('eval_match_counts: table is a contiguous (n_shards,2,101,4) int64 device tensor')
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ws = _ws(ws_bytes)
+    slots = torch.empty((max(n, 1) * 2 * EVAL_CUTOFFS * 4,), dtype=torch.int64, device=dev) if scheme == 'slots' else None
+    thr = (ctypes.c_float * 5)(*[float(t) for t in iou_thr])
+
+    def launch():
+        rc = lib.dz_eval_match_counts(L.ptr(pred_box), L.ptr(pred_score), pred_box.shape[0], L.ptr(gt_box), L.ptr(gt_difficulty), gt_box.shape[0],
+                                      L.ptr(d_desc), n, max_dim, int(n_shards), EVAL_BOX_TYPES[box_type], thr, EVAL_SCHEMES[scheme],
+                                      L.ptr(table), L.ptr(slots), L.ptr(status), L.ptr(ws), int(ws_bytes), L.stream())
+        L.check(rc, 'dz_eval_match_counts')
+
+    if PROFILER is None:
+        launch()
+    else:
+        PROFILER.wrap('eval_match[%s,%s]' % (box_type, scheme), 0., 0., launch)
+    return table, status
+
+
+def eval_match_counts(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shards, box_type='3d', iou_thr=EVAL_IOU_THR, scheme='atomic'):
+    """eval_match_counts_nosync, then one host read: the table as a host int64 array (n_shards,2,101,4); raises when the status
+    word is set."""
+    table, status = eval_match_counts_nosync(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shards, box_type, iou_thr, scheme)
+    st = int(status.item())
+    if st != 0:
+        raise L.DetZeroHipError('eval_match_counts: %s' % EVAL_STATUS.get(st, st))
+    return table.cpu().numpy()[:int(n_shards)]
+
+
 PROFILER = None
 
 

@@ -208,9 +208,21 @@ class WaymoDetectionDataset(torch.utils.data.Dataset):
     def evaluation(self, det_annos, class_names, **kwargs):
         """waymo_dataset.py:104-131.  Without ground truth in the infos the reference returns early; with it, it calls the
         TensorFlow / waymo_open_dataset metrics, which are outside this backend (recall statistics come from the model's
-        generate_recall_record)."""
+        generate_recall_record).  A dataset config with ``EVAL_ON_DEVICE: True`` gets this backend's AP / APH instead, in the
+        reference's return format; without the key the answer is the one below."""
         if not self.infos or 'annos' not in self.infos[0]:
             return 'No ground-truth boxes for evaluation', {}
+        if self.dataset_cfg.get('EVAL_ON_DEVICE', False):
+            # :108-128 with this backend's own statement of the metrics (waymo_eval.py, DESIGN.md 7n) in place of the official tool
+            from .waymo_eval import WaymoDetectionMetricsEstimator
+            ap_dict = WaymoDetectionMetricsEstimator().waymo_evaluation(
+                copy.deepcopy(det_annos), [copy.deepcopy(info['annos']) for info in self.infos], class_name=class_names,
+                distance_thresh=1000, fake_gt_infos=self.dataset_cfg.get('INFO_WITH_FAKELIDAR', False))
+            ap_result_str = '\n'
+            for key in ap_dict:
+                ap_dict[key] = ap_dict[key][0]
+                ap_result_str += '%s: %.4f \n' % (key, ap_dict[key])
+            return ap_result_str, ap_dict
         return 'Official Waymo metrics (waymo_open_dataset / TensorFlow) are not provided by the HIP backend', {}
 
     collate_batch = staticmethod(dataset_utils.collate_batch)

@@ -1193,6 +1193,50 @@ int dz_lsa_batch(const float *cost, long long cost_len, const long long *desc, i
                  int *row_to_col, int *unmatched_rows, long long rows_len, int *unmatched_cols, long long cols_len, int *counts, void *ws,
                  size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Waymo-style detection matching on the device (csrc/eval_match.hip): the count table behind AP / APH at every score cutoff, one
+ * workgroup per problem.  This is the project's own statement of the protocol; it is not pinned to the official tool.
+ *
+ * A problem is one (frame, shard): P predictions in descending score order and G ground truths of one object type.
+ *   Cutoffs: c_k = (float)(k * 0.01) for k = 0..99, c_100 = 1; a prediction is in cutoff k when score >= c_k; n_k of them are.
+ *   Weight: w(p, g) = IoU(p, g) when IoU >= iou_thr[type], else 0.  box_type DZ_EVAL_BOX_3D: the value of dz_boxes_metric's
+ *   DZ_BOXM_IOU3D; DZ_EVAL_BOX_BEV: the rotated BEV IoU of the same code.
+ *   Matching M_k: a maximum-total-weight matching between the first n_k predictions and all ground truths (cost 1 - w for a pair,
+ *   1 for "unmatched", every prediction assigned), pairs with w == 0 then discarded.  The rows enter the shortest-augmenting-path
+ *   solver of csrc/lsa.h in score order; after row n - 1 its state is an optimal assignment of rows 0..n-1, so ONE solve passes
+ *   through M_k of every cutoff.
+ *   Counts per (shard, level L in {1, 2}, k), summed over the problems of the shard:
+ *     TP = pairs of M_k whose ground truth has difficulty <= L;  FP = n_k - |M_k|;  FN = #{g: difficulty <= L} - TP;
+ *     HA = sum over the TP pairs of 1 - |d| / pi, d = the heading difference wrapped to [-pi, pi], in fixed point with 32
+ *     fraction bits, each term rounded to nearest.
+ *
+ *   pred_box (n_pred, 7) f32, pred_score (n_pred) f32, gt_box (n_gt, 7) f32, gt_difficulty (n_gt) i32.
+ *   desc (n_problems, DZ_EVAL_DESC_WORDS) int64 on the device, per problem:
+ *     [0] first prediction  [1] P  [2] first ground truth  [3] G  [4] shard  [5] object type, 0..4 (indexes iou_thr)
+ *     [6] byte offset of its slice in ws, a multiple of 16; the slice has dz_eval_match_ws_bytes(P, G) bytes
+ *   iou_thr: 5 floats on the host.
+ *   table (n_shards, 2, 101, 4) int64 [TP, FP, FN, HA]: ADDED to (the caller zeroes it); all terms are integers, so the table is
+ *   bit-identical whatever order the workgroups finish in.
+ *   scheme DZ_EVAL_ACC_ATOMIC: 64-bit integer atomics on the table.  DZ_EVAL_ACC_SLOTS: each problem fills its own
+ *   (2, 101, 4) slot of `slots` (n_problems * 808 int64, zeroed by the call) and a second kernel adds the slots of a shard in
+ *   problem order.  slots may be NULL for DZ_EVAL_ACC_ATOMIC.
+ *   status (1) i32: OR of DZ_EVAL_ST_DESC (a descriptor leaves its buffers or a limit: that problem contributes nothing, the
+ *   others finish) and DZ_EVAL_ST_SOLVER (a solve stopped at a loop bound: its cutoffs from there on are missing).
+ * Limits: P + G <= DZ_LSA_MAX_DIM (max_dim = the largest P + G of the batch; beyond it DZ_ERR_UNSUPPORTED), n_pred, n_gt < 2^31 / 7.
+ * Every kernel loop is bounded by the problem size or by 101. */
+#define DZ_EVAL_DESC_WORDS 7
+#define DZ_EVAL_CUTOFFS 101
+#define DZ_EVAL_BOX_3D 0
+#define DZ_EVAL_BOX_BEV 1
+#define DZ_EVAL_ACC_ATOMIC 0
+#define DZ_EVAL_ACC_SLOTS 1
+#define DZ_EVAL_ST_DESC 1
+#define DZ_EVAL_ST_SOLVER 2
+size_t dz_eval_match_ws_bytes(int n_pred, int n_gt);
+int dz_eval_match_counts(const float *pred_box, const float *pred_score, long long n_pred, const float *gt_box, const int *gt_difficulty,
+                         long long n_gt, const long long *desc, int n_problems, int max_dim, int n_shards, int box_type, const float *iou_thr,
+                         int scheme, long long *table, long long *slots, int *status, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
