@@ -309,6 +309,12 @@ _SIGS = {
     'dz_eval_match_ws_bytes': (c_size_t, [c_int, c_int]),
     'dz_eval_match_counts': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int,
                                      c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dz_mot_chain_ws_bytes': (c_size_t, [ctypes.c_longlong, ctypes.c_longlong, c_int]),
+    'dz_mot_weights': (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p,
+                               c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p]),
+    'dz_mot_chain_counts': (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong,
+                                    c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -2126,6 +2126,131 @@ def eval_match_counts(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shard
     return table.cpu().numpy()[:int(n_shards)]
 
 
+# ------------------------------------------------------------------------------------------------
+# tracking metrics at every score cutoff (csrc/mot_chain.hip): the count table behind Waymo-style MOTA / MOTP
+# ------------------------------------------------------------------------------------------------
+MOT_COUNTS = 5                     # DZ_MOT_COUNTS: TP, FP, MISS, MISMATCH, COST * 2^32
+MOT_LDS_DIM = 192                  # DZ_MOT_LDS_DIM
+MOT_MAPPINGS = {'wave': 0, 'workgroup': 1}        # DZ_MOT_MAP_*
+MOT_COST_ONE = float(1 << 32)
+
+
+def mot_problem_desc(desc):
+    """Host (n,5) [first prediction, P, first ground truth, G, object type] -> (n,6) int64 with the weight offsets (floats, back to
+    back), and the length of the weight buffer."""
+    desc = np.asarray(desc, dtype=np.int64).reshape(-1, 5)
+    full = np.zeros((desc.shape[0], 6), dtype=np.int64)
+    full[:, :5] = desc
+    size = np.maximum(desc[:, 1], 0) * np.maximum(desc[:, 3], 0)
+    full[:, 5] = np.cumsum(size) - size
+    return full, int(size.sum())
+
+
+def mot_chain_ws_bytes(n_pred_ids, n_gt_ids, max_dim):
+    """dz_mot_chain_ws_bytes: the workspace slice of one (sequence, shard) descriptor, all 101 cutoffs; 0 for sizes the library refuses."""
+    return int(L.load().dz_mot_chain_ws_bytes(int(n_pred_ids), int(n_gt_ids), int(min(max(int(max_dim), -1), 1 << 30))))
+
+
+def mot_weights(pred_box, pred_score, gt_box, pdesc, w_len, box_type='3d', iou_thr=EVAL_IOU_THR):
+    """pred_box (Np,7) f32 / pred_score (Np,) f32 grouped by problem, in descending score order inside each; gt_box (Ng,7) f32
+    grouped by problem; pdesc: host (n,6) int64 of mot_problem_desc.  -> (weights (w_len,) f32, cut (Np,) i32) on the device: the
+    thresholded IoU of every pair of every problem and each prediction's highest cutoff (-1 = none).  One host read (the status)."""
+    lib = L.load()
+    L.require_cuda(pred_box, pred_score, gt_box)
+    if pred_box.dtype != torch.float32 or pred_box.dim() != 2 or pred_box.shape[1] != 7 or gt_box.dtype != torch.float32 or \
+            gt_box.dim() != 2 or gt_box.shape[1] != 7 or pred_score.dtype != torch.float32 or tuple(pred_score.shape) != (pred_box.shape[0],):
+        raise L.DetZeroHipError('mot_weights: boxes are (N,7) float32 and pred_score (Np,) float32')
+    if box_type not in EVAL_BOX_TYPES or len(iou_thr) != 5:
+        raise L.DetZeroHipError('mot_weights: box_type %r / %d thresholds' % (box_type, len(iou_thr)))
+    dev = pred_box.device
+    pdesc = np.asarray(pdesc, dtype=np.int64).reshape(-1, 6)
+    n = pdesc.shape[0]
+    max_dim = int((pdesc[:, 1] + pdesc[:, 3]).max()) if n else 0
+    weights = torch.empty((max(int(w_len), 1),), dtype=torch.float32, device=dev)
+    cut = torch.full((max(pred_box.shape[0], 1),), -1, dtype=torch.int32, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    d_desc = torch.from_numpy(pdesc).to(dev) if n else None
+    thr = (ctypes.c_float * 5)(*[float(t) for t in iou_thr])
+
+    def launch():
+        rc = lib.dz_mot_weights(L.ptr(pred_box), L.ptr(pred_score), pred_box.shape[0], L.ptr(gt_box), gt_box.shape[0], L.ptr(d_desc), n,
+                                max_dim, EVAL_BOX_TYPES[box_type], thr, L.ptr(weights), int(w_len), L.ptr(cut), L.ptr(status), L.stream())
+        L.check(rc, 'dz_mot_weights')
+
+    if PROFILER is None:
+        launch()
+    else:
+        PROFILER.wrap('mot_weights[%s]' % box_type, 0., 0., launch)
+    st = int(status.item())
+    if st != 0:
+        raise L.DetZeroHipError('mot_weights: %s' % EVAL_STATUS.get(st, st))
+    return weights[:int(w_len)], cut[:pred_box.shape[0]]
+
+
+def mot_chain_counts_nosync(weights, cut, pred_id, gt_id, gt_difficulty, pdesc, cdesc, frames, n_shards, mapping='wave', merge=True,
+                            table=None):
+    """weights (w_len,) f32 and cut (Np,) i32 as mot_weights gives them (or made by the caller); pred_id (Np,) / gt_id (Ng,) i32
+    dense per (sequence, side); gt_difficulty (Ng,) i32; pdesc host (n,6) of mot_problem_desc; cdesc host (c,6) per (sequence,
+    shard) of [first entry in frames, number of frames, shard, prediction ids, ground-truth ids, largest P + G] - the workspace
+    offsets are added here; frames: host int64 problem indices in walking order.  ``merge=False`` (tests) runs the chain of every
+    cutoff instead of one per distinct prediction set.  -> (table (n_shards,2,101,5) int64 [TP, FP, MISS, MISMATCH, COST * 2^32],
+    status (1,) i32) on the device; ``table`` (zeros when None) is added to.  No host read: the caller looks at status."""
+    lib = L.load()
+    L.require_cuda(weights, cut, pred_id, gt_id, gt_difficulty)
+    if weights.dtype != torch.float32 or weights.dim() != 1 or any(t.dtype != torch.int32 or t.dim() != 1 for t in (cut, pred_id, gt_id, gt_difficulty)):
+        raise L.DetZeroHipError('mot_chain_counts: weights are (w_len,) float32; cut, ids and difficulties (N,) int32')
+    if cut.shape != pred_id.shape or gt_id.shape != gt_difficulty.shape:
+        raise L.DetZeroHipError('mot_chain_counts: %d cutoff indices for %d prediction ids, %d difficulties for %d ground-truth ids'
+                                % (cut.shape[0], pred_id.shape[0], gt_difficulty.shape[0], gt_id.shape[0]))
+    if mapping not in MOT_MAPPINGS:
+        raise L.DetZeroHipError('mot_chain_counts: mapping %r' % (mapping,))
+    dev = weights.device
+    pdesc = np.asarray(pdesc, dtype=np.int64).reshape(-1, 6)
+    cdesc = np.asarray(cdesc, dtype=np.int64).reshape(-1, 6)
+    frames = np.ascontiguousarray(np.asarray(frames, dtype=np.int64).reshape(-1))
+    n, nc = pdesc.shape[0], cdesc.shape[0]
+    max_dim = int((pdesc[:, 1] + pdesc[:, 3]).max()) if n else 0
+    full = np.zeros((nc, 7), dtype=np.int64)
+    full[:, :6] = cdesc
+    ws_bytes = 0
+    for i in range(nc):                                 # (a bad descriptor gets no room: the kernel refuses it by its own check)
+        full[i, 6] = ws_bytes
+        ws_bytes += mot_chain_ws_bytes(cdesc[i, 3], cdesc[i, 4], cdesc[i, 5])
+    if table is None:
+        table = torch.zeros((max(int(n_shards), 1), 2, EVAL_CUTOFFS, MOT_COUNTS), dtype=torch.int64, device=dev)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (int(n_shards), 2, EVAL_CUTOFFS, MOT_COUNTS) or not table.is_cuda or \
+            not table.is_contiguous():
+        raise L.DetZeroHipError('mot_chain_counts: table is a contiguous (n_shards,2,101,5) int64 device tensor')
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ws = _ws(ws_bytes)
+    d_pdesc = torch.from_numpy(pdesc).to(dev) if n else None
+    d_cdesc = torch.from_numpy(full).to(dev) if nc else None
+    d_frames = torch.from_numpy(frames).to(dev) if frames.size else None
+
+    def launch():
+        rc = lib.dz_mot_chain_counts(L.ptr(weights), weights.shape[0], L.ptr(cut), L.ptr(pred_id), pred_id.shape[0], L.ptr(gt_id),
+                                     L.ptr(gt_difficulty), gt_id.shape[0], L.ptr(d_pdesc), n, L.ptr(d_cdesc), nc, L.ptr(d_frames),
+                                     frames.size, max_dim, int(n_shards), MOT_MAPPINGS[mapping], 1 if merge else 0, L.ptr(table),
+                                     L.ptr(status), L.ptr(ws), int(ws_bytes), L.stream())
+        L.check(rc, 'dz_mot_chain_counts')
+
+    if PROFILER is None:
+        launch()
+    else:
+        PROFILER.wrap('mot_chain[%s]' % mapping, 0., 0., launch)
+    return table, status
+
+
+def mot_chain_counts(weights, cut, pred_id, gt_id, gt_difficulty, pdesc, cdesc, frames, n_shards, mapping='wave', merge=True):
+    """mot_chain_counts_nosync, then one host read: the table as a host int64 array (n_shards,2,101,5); raises when the status
+    word is set."""
+    table, status = mot_chain_counts_nosync(weights, cut, pred_id, gt_id, gt_difficulty, pdesc, cdesc, frames, n_shards, mapping, merge)
+    st = int(status.item())
+    if st != 0:
+        raise L.DetZeroHipError('mot_chain_counts: %s' % EVAL_STATUS.get(st, st))
+    return table.cpu().numpy()[:int(n_shards)]
+
+
 PROFILER = None
 
 

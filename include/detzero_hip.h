@@ -1237,6 +1237,69 @@ int dz_eval_match_counts(const float *pred_box, const float *pred_score, long lo
                          long long n_gt, const long long *desc, int n_problems, int max_dim, int n_shards, int box_type, const float *iou_thr,
                          int scheme, long long *table, long long *slots, int *status, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Waymo-style tracking metrics on the device (csrc/mot_chain.hip): the count table behind MOTA / MOTP at every score cutoff.  This is
+ * the project's own statement of the protocol; it is not pinned to the official tool.
+ *
+ * A prediction is (sequence, frame, object id, box7, type, score), a ground truth (sequence, frame, object id, box7, type,
+ * difficulty in {1, 2}).  Types, cutoffs c_k, iou_thr, the weight w(p, g), the box types and the shards are those of
+ * dz_eval_match_counts above.  An object id is unique within a frame and side; the host maps ids to dense indices per (sequence, side)
+ * and walks the frames of a sequence in ascending frame id.  A problem is one (sequence, frame, shard).
+ *   Chain (sequence, shard, cutoff k): its state `last` is a partial bijection between ground-truth ids and prediction ids, empty at
+ *   the sequence's first frame and never reset.  Per frame, with P_t the problem's predictions of score >= c_k and G_t its ground truths:
+ *     1. carry: for every g in G_t with q = last[g.id] defined, a p in P_t of id q and w(p, g) > 0: the pair (p, g) is kept and both
+ *        leave the pools;
+ *     2. match: a maximum-total-weight matching of the remaining predictions and ground truths (cost 1 - w, "unmatched" costs 1,
+ *        zero-weight pairs discarded), the predictions entering csrc/lsa.h's solver as rows in input order (descending score);
+ *     3. update: every new pair (p, g) of step 2 whose last[g.id] is defined and differs from p.id is one mismatch on g, judged on
+ *        `last` as the frame found it; then whatever g.id and p.id were paired with is unpaired (through the prediction's side this
+ *        is no mismatch) and last[g.id] = p.id.
+ *   Counts per (shard, level L in {1, 2}, k), summed over frames and sequences, M = the kept and the new pairs:
+ *     TP = #{(p, g) in M: difficulty(g) <= L};  FP = |P_t| - |M|;  MISS = #{g: difficulty <= L} - TP;  MISMATCH = the mismatches on
+ *     ground truths of difficulty <= L;  COST = sum over the TP pairs of 1 - w in fixed point with 32 fraction bits, each term
+ *     evaluated in double and rounded to nearest.  One chain serves both levels.
+ *   Cutoffs that hold the same predictions in every frame of a (sequence, shard) are one chain: with `merge` the kernel runs the
+ *   cutoffs some prediction reaches exactly (and the last one) and adds each result to every cutoff down to the next such value.
+ *
+ * dz_mot_weights: w of every pair of every problem, once for all cutoffs, and each prediction's highest cutoff.
+ *   pred_box (n_pred, 7) f32, pred_score (n_pred) f32, gt_box (n_gt, 7) f32, grouped by problem, predictions in descending score.
+ *   pdesc (n_problems, DZ_MOT_PDESC_WORDS) int64 on the device, per problem:
+ *     [0] first prediction  [1] P  [2] first ground truth  [3] G  [4] object type, 0..4 (indexes iou_thr)
+ *     [5] offset of its (P, G) row-major weights in `weights`, in floats
+ *   weights (w_len) f32 out, cut (n_pred) i32 out: the highest k with score >= c_k, -1 = none.
+ *   status (1) i32: DZ_EVAL_ST_DESC is ORed in when a descriptor leaves its buffers (that problem writes nothing, the others finish).
+ * dz_mot_chain_counts: the chains.
+ *   pred_id (n_pred) i32 / gt_id (n_gt) i32: dense ids per (sequence, side); gt_difficulty (n_gt) i32.
+ *   cdesc (n_chains, DZ_MOT_CDESC_WORDS) int64 on the device, per (sequence, shard):
+ *     [0] first entry in `frames`  [1] number of frames  [2] shard  [3] prediction ids of the sequence  [4] ground-truth ids
+ *     [5] the largest P + G of its frames  [6] byte offset of its slice in ws, a multiple of 16, dz_mot_chain_ws_bytes([3], [4], [5]) long
+ *   frames (n_frames) int64: problem indices, the frames of a chain in walking order (frames without a member are left out).
+ *   mapping DZ_MOT_MAP_WAVE: one wavefront per chain; DZ_MOT_MAP_WORKGROUP: 256 threads per chain.  Both give the same bits.
+ *   table (n_shards, 2, 101, DZ_MOT_COUNTS) int64 [TP, FP, MISS, MISMATCH, COST * 2^32]: ADDED to with 64-bit integer atomics, zero
+ *   terms skipped, so it is bit-identical whatever order the chains finish in.
+ *   status (1) i32: OR of DZ_EVAL_ST_DESC (a descriptor or id leaves its buffers or a limit: every descriptor and id of a chain is
+ *   checked before anything is followed, such a chain adds nothing and the others finish) and DZ_EVAL_ST_SOLVER (a solve stopped at a
+ *   loop bound: the chain adds nothing).
+ *   The slice holds, per cutoff, `last` in both directions and the id -> row table of the current frame; when [5] is above
+ *   DZ_MOT_LDS_DIM also the per-frame lists and the solver's vectors, which otherwise live in LDS.
+ * Limits: per frame P + G <= DZ_LSA_MAX_DIM (max_dim = the largest of the call; beyond it DZ_ERR_UNSUPPORTED, as are 2^31 predictions,
+ * ground truths or frame-list entries in one call).  Every kernel loop is
+ * bounded by a frame count, a problem size or 101. */
+#define DZ_MOT_PDESC_WORDS 6
+#define DZ_MOT_CDESC_WORDS 7
+#define DZ_MOT_COUNTS 5
+#define DZ_MOT_LDS_DIM 192
+#define DZ_MOT_MAP_WAVE 0
+#define DZ_MOT_MAP_WORKGROUP 1
+size_t dz_mot_chain_ws_bytes(long long n_pred_ids, long long n_gt_ids, int max_dim);
+int dz_mot_weights(const float *pred_box, const float *pred_score, long long n_pred, const float *gt_box, long long n_gt, const long long *pdesc,
+                   int n_problems, int max_dim, int box_type, const float *iou_thr, float *weights, long long w_len, int *cut, int *status,
+                   void *stream);
+int dz_mot_chain_counts(const float *weights, long long w_len, const int *cut, const int *pred_id, long long n_pred, const int *gt_id,
+                        const int *gt_difficulty, long long n_gt, const long long *pdesc, int n_problems, const long long *cdesc, int n_chains,
+                        const long long *frames, long long n_frames, int max_dim, int n_shards, int mapping, int merge, long long *table,
+                        int *status, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
