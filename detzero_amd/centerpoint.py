@@ -91,6 +91,15 @@ class CenterPoint(nn.Module):
             batch_dict = cur_module(batch_dict)
         return self.post_processing(batch_dict)
 
+    def get_training_loss(self):
+        """centerpoint.py:41-50, first stage: (loss, tb_dict, disp_dict) of the dense head after a forward on a batch with
+        ``gt_boxes`` (inference mode: a validation loss, or the gradient at the head maps).  The PDV head's losses are not built."""
+        if self.second_stage or self.model_cfg.get('ROI_HEAD', None) is not None:
+            raise DetZeroHipError('CenterPoint.get_training_loss: the PDV head\'s losses (ROI_HEAD) are not built; only the '
+                                  'first-stage CenterHead loss is provided')
+        loss, tb_dict = self.dense_head.get_loss()
+        return loss, tb_dict, {}
+
     def post_processing(self, batch_dict):
         """centerpoint.py:283-307 (one-stage branch; with TTA the copies' boxes are restored and fused, :298-306)."""
         post_process_cfg = self.model_cfg.POST_PROCESSING

@@ -100,6 +100,7 @@ def centerpoint_1sweep_cfg(voxel_size=(0.1, 0.1, 0.15), max_voxels_test=200000):
                 },
                 'TARGET_ASSIGNER_CONFIG': {'FEATURE_MAP_STRIDE': 8, 'NUM_MAX_OBJS': 500, 'GAUSSIAN_OVERLAP': 0.1,
                                            'MIN_RADIUS': 2},
+                'LOSS_CONFIG': {'LOSS_WEIGHTS': {'cls_weight': 1.0, 'loc_weight': 2.0, 'code_weights': [1.0] * 8}},
                 'POST_PROCESSING': {
                     'SCORE_THRESH': 0.03, 'POST_CENTER_LIMIT_RANGE': [-80, -80, -10.0, 80, 80, 10.0],
                     'MAX_OBJ_PER_SAMPLE': 500,

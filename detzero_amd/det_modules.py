@@ -1325,6 +1325,48 @@ class CenterHead(_Cached):
         self.input_channels = input_channels
         # engine of the 3 x 3 stride-1 layers in the exact-fp32 mode: 'mfma32' (default) | 'bf16x3' (csrc/conv3x3_t.hip, opt-in: DESIGN.md 2a)
         self.f32_dense_engine = os.environ.get('DZ_TUNE_DENSE_F32_ENGINE', 'mfma32')
+        # forward's target assignment: False = the host route (target_assign.py), True = csrc/head_loss.hip
+        self.targets_on_device = False
+        self.build_losses()
+
+    def build_losses(self):
+        """center_head.py:107-109: the two parameter-free loss modules (no parameters, no buffers: the state dict does not move)."""
+        from .head_loss import FocalLossCenterNet, RegLossCenterNet
+        self.add_module('hm_loss_func', FocalLossCenterNet())
+        self.add_module('reg_loss_func', RegLossCenterNet())
+
+    def get_loss(self, tb_dict=None):
+        """center_head.py:266-313 over all heads on the device -> (loss, tb_dict): ``loss`` a 0-dim device tensor, ``tb_dict`` the
+        reference's keys (hm_loss_head_i, loc_loss_head_i, center_loss_head_i, center_z_loss_head_i, dim_loss_head_i,
+        rot_loss_head_i, iou_loss_head_i when IOU_WEIGHT > 0, rpn_loss) as floats read with ONE device-to-host copy of the heads'
+        records.  Unlike the reference it does not overwrite ``pred_dicts[i]['hm']`` with its sigmoid (the clamped sigmoid is part of
+        the kernel), so calling it twice gives the same result.  Targets of either route of ``assign_targets`` are accepted."""
+        from .head_loss import head_losses, head_map_of
+        pred_dicts = self.forward_ret_dict.get('pred_dicts', None)
+        target_dicts = self.forward_ret_dict.get('target_dicts', None)
+        if pred_dicts is None or target_dicts is None:
+            raise DetZeroHipError('CenterHead.get_loss: forward_ret_dict has no %s (run forward on a batch that carries gt_boxes)'
+                                  % ('pred_dicts' if pred_dicts is None else 'target_dicts'))
+        tb_dict = {} if tb_dict is None else tb_dict
+        heads, h, w = [], 0, 0
+        for pred_dict in pred_dicts:
+            head, _, h, w = head_map_of(pred_dict['hm'])
+            heads.append(head)
+        totals, recs = head_losses(self, heads, target_dicts, h, w)
+        loss = totals[0] if len(totals) == 1 else torch.stack(totals).sum()
+        host = torch.stack(recs).cpu().numpy()               # the one host read
+        for idx in range(len(heads)):
+            r = host[idx]
+            tb_dict['center_loss_head_%d' % idx] = float(r[1] + r[2])
+            tb_dict['center_z_loss_head_%d' % idx] = float(r[3])
+            tb_dict['dim_loss_head_%d' % idx] = float(r[4] + r[5] + r[6])
+            tb_dict['rot_loss_head_%d' % idx] = float(r[7] + r[8])
+            if self.iou_weight > 0:
+                tb_dict['iou_loss_head_%d' % idx] = float(r[10])
+            tb_dict['hm_loss_head_%d' % idx] = float(r[0])
+            tb_dict['loc_loss_head_%d' % idx] = float(r[9])
+        tb_dict['rpn_loss'] = float(host[:, 11].sum())
+        return loss, tb_dict
 
     def plan(self):
         if self._plan is not None:
@@ -1475,8 +1517,12 @@ class CenterHead(_Cached):
         return ops.head_at_candidates(shared, cand, ncand, k, w1, s1, b1, w2, s2, b2, hp_['final']['g_cout'][:4], hp_['final']['g_ooff'][:4],
                                       head, self.math)
 
-    def assign_targets(self, gt_boxes, feature_map_size=None, **kwargs):
-        """center_head.py:202-260 (host-side, like the reference's)."""
+    def assign_targets(self, gt_boxes, feature_map_size=None, on_device=False, **kwargs):
+        """center_head.py:202-260: host-side like the reference's, or with ``on_device`` by csrc/head_loss.hip (the same
+        dictionary plus the count records the loss reads)."""
+        if on_device:
+            from .head_loss import device_targets
+            return device_targets(self, gt_boxes, feature_map_size)
         from .target_assign import assign_targets
         return assign_targets(self, gt_boxes, feature_map_size)
 
@@ -1548,7 +1594,8 @@ class CenterHead(_Cached):
                 preds.append({n: head.view(head.shape[0], h, w, 12)[..., o:o + (len(names) if n == 'hm' else c)].permute(0, 3, 1, 2)
                               for n, (o, c) in self.COLS.items()})
             if data_dict.get('gt_boxes', None) is not None:              # center_head.py:448-453
-                self.forward_ret_dict['target_dicts'] = self.assign_targets(data_dict['gt_boxes'], feature_map_size=(h, w))
+                self.forward_ret_dict['target_dicts'] = self.assign_targets(data_dict['gt_boxes'], feature_map_size=(h, w),
+                                                                            on_device=self.targets_on_device)
             self.forward_ret_dict['pred_dicts'] = preds
             pred_dicts = self.generate_predicted_boxes(heads, h, w)
             data_dict['final_box_dicts'] = pred_dicts

@@ -315,6 +315,13 @@ _SIGS = {
     'dz_mot_chain_counts': (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong,
                                     c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dz_centerhead_targets': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, ctypes.c_double,
+                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int, ctypes.c_double, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dz_centerhead_loss_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'dz_centerhead_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                                   ctypes.POINTER(ctypes.c_double), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -2251,6 +2251,123 @@ def mot_chain_counts(weights, cut, pred_id, gt_id, gt_difficulty, pdesc, cdesc, 
     return table.cpu().numpy()[:int(n_shards)]
 
 
+# ------------------------------------------------------------------------------------------------
+# CenterHead targets and losses (csrc/head_loss.hip)
+# ------------------------------------------------------------------------------------------------
+HEAD_LOSS_MAX_OBJS = 1024          # DZ_HEAD_LOSS_MAX_OBJS
+HEAD_LOSS_REC = 12                 # DZ_HEAD_LOSS_REC: hm, eight regression components, loc, iou, total
+HEAD_LOSS_KEYS = ('hm', 'center_x', 'center_y', 'center_z', 'dim_x', 'dim_y', 'dim_z', 'rot_cos', 'rot_sin', 'loc', 'iou', 'total')
+
+
+def _dbl(values):
+    return (ctypes.c_double * len(values))(*[float(v) for v in values])
+
+
+def centerhead_targets(gt_boxes, cls_table, ncls, feat_h, feat_w, stride, pc_range, voxel_size, num_max_objs=500, gaussian_overlap=0.1,
+                       min_radius=2):
+    """center_head.py:111-161 for ONE head and the whole batch on the device.  gt_boxes (B, M, 8) f32 [x, y, z, dx, dy, dz, heading,
+    1-based global class (0 = padding)]; cls_table[g - 1] = the head's 1-based class of global class g, 0 = not this head.
+    -> heatmap (B, ncls, H, W) f32, target_boxes (B, NMAX, 8) f32, inds (B, NMAX) i64, masks (B, NMAX) i64, rec (2,) i32
+    [num_pos, num].  No host read."""
+    lib = L.load()
+    L.require_cuda(gt_boxes)
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3:
+        raise L.DetZeroHipError('centerhead_targets: gt_boxes is (B, M, 8) float32, got %s %s' % (tuple(gt_boxes.shape), gt_boxes.dtype))
+    b, m, cols = gt_boxes.shape
+    dev = gt_boxes.device
+    nmax, ncls = int(num_max_objs), int(ncls)
+    shape_ok = 1 <= ncls <= 3 and 1 <= nmax <= HEAD_LOSS_MAX_OBJS and b > 0 and feat_h > 0 and feat_w > 0 and cols == 8
+    heat = torch.empty((b, ncls, feat_h, feat_w) if shape_ok else (1,), dtype=torch.float32, device=dev)
+    tb = torch.empty((b, nmax, 8) if shape_ok else (8,), dtype=torch.float32, device=dev)
+    inds = torch.empty((b, nmax) if shape_ok else (1,), dtype=torch.int64, device=dev)
+    masks = torch.empty((b, nmax) if shape_ok else (1,), dtype=torch.int64, device=dev)
+    rec = torch.empty((2,), dtype=torch.int32, device=dev)
+    table = (ctypes.c_int * max(len(cls_table), 1))(*[int(v) for v in cls_table])
+
+    def launch():
+        rc = lib.dz_centerhead_targets(L.ptr(gt_boxes), b, m, cols, table, len(cls_table), ncls, int(feat_h), int(feat_w), float(stride),
+                                       _dbl(pc_range[0:2]), _dbl(voxel_size[0:2]), nmax, float(gaussian_overlap), int(min_radius),
+                                       L.ptr(heat), L.ptr(tb), L.ptr(inds), L.ptr(masks), L.ptr(rec), L.stream())
+        L.check(rc, 'dz_centerhead_targets')
+
+    if PROFILER is None:
+        launch()
+    else:
+        PROFILER.wrap('centerhead_targets', 0., 0., launch)
+    return heat, tb, inds, masks, rec
+
+
+def centerhead_loss_nosync(head, heatmap, target_boxes, inds, masks, rec, feat_h, feat_w, weights, stride, pc_range, voxel_size,
+                           hm_mask=None, want_grad=False):
+    """The launches of centerhead_loss without autograd: -> (record (12,) f64 on the device in HEAD_LOSS_KEYS order, grad_head
+    (B, H*W, 12) f32 or None).  weights = (cls_weight, loc_weight, code_weights[8], iou_weight); rec None: counted by the call."""
+    lib = L.load()
+    L.require_cuda(head, heatmap, target_boxes, inds, masks, rec, hm_mask)
+    if head.dtype != torch.float32 or head.dim() != 3 or head.shape[2] != 12 or head.shape[1] != feat_h * feat_w:
+        raise L.DetZeroHipError('centerhead_loss: head is (B, H*W, 12) float32, got %s %s' % (tuple(head.shape), head.dtype))
+    b = head.shape[0]
+    if heatmap.dtype != torch.float32 or heatmap.dim() != 4 or heatmap.shape[0] != b or tuple(heatmap.shape[2:]) != (feat_h, feat_w):
+        raise L.DetZeroHipError('centerhead_loss: heatmap is (B, ncls, H, W) float32, got %s %s' % (tuple(heatmap.shape), heatmap.dtype))
+    ncls = heatmap.shape[1]
+    if inds.dtype != torch.int64 or masks.dtype != torch.int64 or inds.dim() != 2 or inds.shape[0] != b or masks.shape != inds.shape or \
+            target_boxes.dtype != torch.float32 or tuple(target_boxes.shape) != (b, inds.shape[1], 8):
+        raise L.DetZeroHipError('centerhead_loss: inds / masks are (B, NMAX) int64 and target_boxes (B, NMAX, 8) float32')
+    if rec is not None and (rec.dtype != torch.int32 or rec.numel() != 2):
+        raise L.DetZeroHipError('centerhead_loss: rec is (2,) int32')
+    if hm_mask is not None and (hm_mask.dtype != torch.float32 or tuple(hm_mask.shape) != (b, feat_h, feat_w)):
+        raise L.DetZeroHipError('centerhead_loss: hm_mask is (B, H, W) float32')
+    if len(weights) != 11:
+        raise L.DetZeroHipError('centerhead_loss: 11 weights (cls, loc, eight code weights, iou), got %d' % len(weights))
+    dev = head.device
+    nmax = inds.shape[1]
+    out = torch.empty((HEAD_LOSS_REC,), dtype=torch.float64, device=dev)
+    grad = torch.empty_like(head) if want_grad else None
+    ws_bytes = int(lib.dz_centerhead_loss_ws_bytes(b, int(feat_h), int(feat_w)))
+    ws = _ws(ws_bytes)
+
+    def launch():
+        rc = lib.dz_centerhead_loss(L.ptr(head), L.ptr(heatmap), L.ptr(target_boxes), L.ptr(inds), L.ptr(masks), L.ptr(rec), L.ptr(hm_mask),
+                                    b, int(feat_h), int(feat_w), ncls, nmax, _dbl(weights), float(stride), _dbl(pc_range[0:2]),
+                                    _dbl(voxel_size[0:2]), L.ptr(out), L.ptr(grad), L.ptr(ws), ws_bytes, L.stream())
+        L.check(rc, 'dz_centerhead_loss')
+
+    if PROFILER is None:
+        launch()
+    else:
+        PROFILER.wrap('centerhead_loss', 0., 0., launch)
+    return out, grad
+
+
+class _CenterHeadLoss(torch.autograd.Function):
+    """total and record of one head; the fused pass has already formed d total / d head when backward asks for it."""
+
+    @staticmethod
+    def forward(ctx, head, args):
+        rec, grad = centerhead_loss_nosync(head.detach(), *args, want_grad=True)     # (only applied to a head map that requires grad)
+        ctx.grad_head = grad
+        ctx.mark_non_differentiable(rec)
+        return rec[HEAD_LOSS_REC - 1].to(torch.float32), rec
+
+    @staticmethod
+    def backward(ctx, grad_total, _grad_rec):
+        if ctx.grad_head is None:
+            raise L.DetZeroHipError('centerhead_loss: the head map did not require grad when the loss was formed')
+        return ctx.grad_head * grad_total, None
+
+
+def centerhead_loss(head, heatmap, target_boxes, inds, masks, rec, feat_h, feat_w, weights, stride, pc_range, voxel_size, hm_mask=None):
+    """Losses of ONE head (center_head.py:266-313 for one `idx`): head (B, H*W, 12) f32 channel-last as CenterHead.run_head writes
+    it, the targets as centerhead_targets gives them.  -> (total, record): total a 0-dim f32 tensor, record (12,) f64 in
+    HEAD_LOSS_KEYS order, both on the device.  With a head map that requires grad, total.backward() delivers grad_head * grad_output
+    (the gradient buffer is filled by the same pass; without one it is not allocated).  No host read."""
+    args = (heatmap, target_boxes, inds, masks, rec, int(feat_h), int(feat_w), tuple(float(w) for w in weights), float(stride),
+            tuple(pc_range), tuple(voxel_size), hm_mask)
+    if head.requires_grad and torch.is_grad_enabled():
+        return _CenterHeadLoss.apply(head, args)
+    out, _ = centerhead_loss_nosync(head.detach(), *args, want_grad=False)
+    return out[HEAD_LOSS_REC - 1].to(torch.float32), out
+
+
 PROFILER = None
 
 

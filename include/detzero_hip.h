@@ -1300,6 +1300,55 @@ int dz_mot_chain_counts(const float *weights, long long w_len, const int *cut, c
                         const long long *frames, long long n_frames, int max_dim, int n_shards, int mapping, int merge, long long *table,
                         int *status, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CenterHead targets and losses on the device (csrc/head_loss.hip).  Reference: center_head.py:107-313,
+ * utils/loss_utils.py:143-243, utils/centernet_utils.py:11-71.  One call serves ONE head; every buffer is the caller's.
+ *
+ * dz_centerhead_targets: heat map, regression targets, cell indices and masks of one head from the batch's ground truth.
+ *   gt_boxes (B, M, 8) f32 [x, y, z, dx, dy, dz, heading, class]: class is the 1-based global class, 0 = padding row.
+ *     gt_cols != 8 (a `vel` head): DZ_ERR_UNSUPPORTED.
+ *   cls_table (n_classes) i32 on the HOST: cls_table[g - 1] = the head's 1-based class of global class g, 0 = not this head.
+ *   feat_w x feat_h: the map (x by y); stride = FEATURE_MAP_STRIDE; range_xy = POINT_CLOUD_RANGE[0:2]; voxel_xy = VOXEL_SIZE[0:2].
+ *   heatmap (B, ncls, H, W) f32, target_boxes (B, nmax, 8) f32, inds (B, nmax) i64, masks (B, nmax) i64: all four are cleared by the call.
+ *   rec (2) i32: [num_pos = cells of the heat map equal to 1.0 over the whole batch, num = sum of masks]; cleared by the call.
+ *   Slot k of a frame is the k-th box of this head in gt_boxes order; slots at or beyond min(nmax, count) do not exist; a box with
+ *   dx <= 0 or dy <= 0 leaves its slot zero (mask 0) and the slots behind it stay where they are.  Coordinates, the clamp to
+ *   [0, size - 0.5], the truncation and gaussian_radius are float32 with every operation rounded on its own; the Gaussian is evaluated
+ *   in float64 (sigma = (2r + 1) / 6, values below eps * max cut), rounded to float32 once, clipped to the map and max-accumulated by
+ *   integer atomicMax on the bit pattern (exact, order independent).  target_boxes = [cx - int(cx), cy - int(cy), z, log dx, log dy,
+ *   log dz, cos, sin]; log / cos / sin are evaluated in float64 and rounded once.
+ *   Limits: 1 <= ncls <= 3, 1 <= nmax <= DZ_HEAD_LOSS_MAX_OBJS, 1 <= n_classes <= DZ_HEAD_LOSS_MAX_CLASSES, B * ncls * H * W < 2^31.
+ *
+ * dz_centerhead_loss: the head's losses and, optionally, their gradient with respect to the head map.
+ *   head (B, H*W, 12) f32 channel-last: center 0:2, center_z 2, dim 3:6, rot 6:8, iou 8, hm 9:9+ncls.  Columns 9+ncls..11 are never read.
+ *   heatmap / target_boxes / inds / masks / rec: as dz_centerhead_targets writes them (targets of any origin with that layout will do;
+ *     a slot whose index is outside [0, H*W) counts as masked out).  rec may be NULL: the call then counts num_pos and num itself.
+ *   hm_mask (B, H, W) f32 or NULL: the optional mask of neg_loss_cornernet; with it num_pos is the masked count, summed by the call.
+ *   weights (11) doubles on the HOST: [cls_weight, loc_weight, code_weights[8], iou_weight].
+ *   out_rec (DZ_HEAD_LOSS_REC) doubles on the device: [0] hm_loss * cls_weight, [1..8] the regression components * code_weights,
+ *     [9] loc_loss = loc_weight * sum of [1..8], [10] iou_loss (unweighted; 0 when iou_weight <= 0), [11] total = [0] + [9] +
+ *     iou_weight * [10].
+ *   grad_head (B, H*W, 12) f32 or NULL: d total / d head, every column written (unwritten head columns get 0).
+ *   Focal term: neg_loss_cornernet on p = clamp(sigmoid(x), 1e-4, 1 - 1e-4) (float32 bounds), positives where the target is 1,
+ *   negatives weighted (1 - g)^4, divided by num_pos, or -neg undivided when num_pos == 0; the gradient is 0 where the clamp is active.
+ *   Regression term: L1 of (pred - target) at inds over the masked slots per component / max(num, 1); gradient sign(.), sign(0) = 0,
+ *   slots that share a cell add up.  IoU term (iou_weight > 0): _iou_target - boxes decoded from the prediction at inds and from the
+ *   targets, heading atan2(column 6, column 7) on both sides, the paired DZ_BOXM_IOU3D value - L1 against column 8 / max(num, 1).
+ *   Every sum is formed in float64 in a fixed order (per-workgroup partials, then a fixed-order pass): two calls give the same bytes.
+ *   ws: dz_centerhead_loss_ws_bytes(B, feat_h, feat_w) bytes.  Limits as above.  Nothing is launched when an argument is refused. */
+#define DZ_HEAD_LOSS_MAX_OBJS 1024
+#define DZ_HEAD_LOSS_MAX_CLASSES 32
+#define DZ_HEAD_LOSS_REC 12
+int dz_centerhead_targets(const float *gt_boxes, int batch, int max_boxes, int gt_cols, const int *cls_table, int n_classes, int ncls,
+                          int feat_h, int feat_w, double stride, const double *range_xy, const double *voxel_xy, int nmax,
+                          double gaussian_overlap, int min_radius, float *heatmap, float *target_boxes, long long *inds, long long *masks,
+                          int *rec, void *stream);
+size_t dz_centerhead_loss_ws_bytes(int batch, int feat_h, int feat_w);
+int dz_centerhead_loss(const float *head, const float *heatmap, const float *target_boxes, const long long *inds, const long long *masks,
+                       const int *rec, const float *hm_mask, int batch, int feat_h, int feat_w, int ncls, int nmax, const double *weights,
+                       double stride, const double *range_xy, const double *voxel_xy, double *out_rec, float *grad_head, void *ws,
+                       size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
