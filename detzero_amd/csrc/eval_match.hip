@@ -5,8 +5,8 @@
 // reference; include/detzero_hip.h and DESIGN.md 7n state the protocol this kernel computes.
 //
 // Three phases per problem, P predictions (descending score) x G ground truths:
-//   1. weights: one thread per pair, the thresholded IoU into the problem's workspace slice (box_geom.h's pair body with its
-//      per-thread LDS columns), and each prediction's highest cutoff;
+//   1. weights: one thread per pair, the thresholded IoU into the problem's workspace slice, and each prediction's highest cutoff
+//      (eval_pairs.h, shared with k_mot_weights);
 //   2. solve: lsa_assign_prefix over G + P columns - column j < G costs 1 - w, the P others cost 1 ("unmatched") - so rows <= columns
 //      always holds; the per-column vectors reuse phase 1's LDS when G + P <= 1024, else they live in the slice;
 //   3. (inside 2, after each row) at a cutoff boundary the workgroup counts the valid pairs of the current prefix and adds them to
@@ -17,6 +17,7 @@
 #pragma clang fp contract(off)
 
 #include "box_geom.h"
+#include "eval_pairs.h"
 #include "lsa_wg.h"
 
 namespace dz {
@@ -24,12 +25,10 @@ namespace dz {
 constexpr int EVM_THREADS = 256;
 constexpr int EVM_WAVES = EVM_THREADS / 64;
 constexpr int EVM_LDS_DIM = 1024;                                   // columns whose vectors fit phase 1's LDS (40 bytes each)
-constexpr int EVM_LDS_DOUBLES = 24 * EVM_THREADS;                   // 16 P2 + 16 float per thread = 192 bytes = 24 doubles: 48 KiB
-constexpr int EVM_K = DZ_EVAL_CUTOFFS;
+constexpr int EVM_LDS_DOUBLES = EvalPairLds<EVM_THREADS>::DOUBLES;  // 48 KiB
+constexpr int EVM_K = EVAL_K;
 constexpr int EVM_SLOT = 2 * EVM_K * 4;                             // int64 words of one shard (or one problem's slot)
 static_assert(5 * EVM_LDS_DIM <= EVM_LDS_DOUBLES, "the solver's LDS vectors reuse the pair columns");
-
-typedef unsigned long long u64;
 
 struct EvmArgs {
     const float *pred_box, *pred_score, *gt_box;
@@ -42,8 +41,6 @@ struct EvmArgs {
     int *status;
     char *ws;
 };
-
-__host__ __device__ inline float evm_cutoff(int k) { return k >= 100 ? 1.0f : (float)((double)k * 0.01); }
 
 // bytes of the three parts of a slice: weights (P, G) f32, the predictions' cutoff index (P) i32, the solver's vectors
 __host__ __device__ inline size_t evm_weight_bytes(int P, int G) { return ((size_t)P * G * sizeof(float) + 15) / 16 * 16; }
@@ -93,17 +90,13 @@ struct EvmEmit {
             d -= 6.283185307179586 * floor((d + 3.141592653589793) / 6.283185307179586);
             double acc_h = 1.0 - fabs(d) / 3.141592653589793;
             acc_h = acc_h >= 0.0 && acc_h <= 1.0 ? acc_h : 0.0;  // (a NaN heading adds nothing)
-            const u64 h = (u64)llrint(acc_h * 4294967296.0);
+            const u64 h = (u64)llrint(acc_h * EVAL_FIXED_ONE);
             const int diff = gt_diff[g];
             ++m;
             if (diff <= 1) { ++tp1; ha1 += h; }
             if (diff <= 2) { ++tp2; ha2 += h; }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            m += __shfl_xor(m, off, 64); tp1 += __shfl_xor(tp1, off, 64); tp2 += __shfl_xor(tp2, off, 64);
-            ha1 += __shfl_xor(ha1, off, 64); ha2 += __shfl_xor(ha2, off, 64);
-        }
+        m = eval_wave_sum(m); tp1 = eval_wave_sum(tp1); tp2 = eval_wave_sum(tp2); ha1 = eval_wave_sum(ha1); ha2 = eval_wave_sum(ha2);
         if ((cx.tid & 63) == 0) {
             atomicAdd(acc + 0, m); atomicAdd(acc + 1, tp1); atomicAdd(acc + 2, tp2); atomicAdd(acc + 3, ha1); atomicAdd(acc + 4, ha2);
         }
@@ -128,9 +121,8 @@ __global__ __launch_bounds__(EVM_THREADS) void k_eval_match(EvmArgs a) {
     const long long *d = a.desc + (size_t)blockIdx.x * DZ_EVAL_DESC_WORDS;
     const long long p0 = d[0], P = d[1], g0 = d[2], G = d[3], shard = d[4], type = d[5], ws_off = d[6];
     // a descriptor that leaves its buffers is not followed (uniform: every thread reads the same words)
-    bool ok = p0 >= 0 && P >= 0 && g0 >= 0 && G >= 0 && P <= DZ_LSA_MAX_DIM && G <= DZ_LSA_MAX_DIM && P + G <= DZ_LSA_MAX_DIM &&
-              p0 <= a.n_pred && P <= a.n_pred - p0 && g0 <= a.n_gt && G <= a.n_gt - g0 && shard >= 0 && shard < a.n_shards && type >= 0 &&
-              type <= 4 && ws_off >= 0 && (ws_off & 15) == 0 && ws_off <= a.ws_bytes;
+    bool ok = eval_desc_ok(p0, P, g0, G, type, a.n_pred, a.n_gt) && shard >= 0 && shard < a.n_shards && ws_off >= 0 && (ws_off & 15) == 0 &&
+              ws_off <= a.ws_bytes;
     if (ok) ok = (long long)evm_slice_bytes((int)P, (int)G) <= a.ws_bytes - ws_off;
     if (!ok) {
         if (tid == 0) atomicOr(a.status, DZ_EVAL_ST_DESC);
@@ -148,25 +140,8 @@ __global__ __launch_bounds__(EVM_THREADS) void k_eval_match(EvmArgs a) {
     if (tid < 3) word_s[tid] = 0;
     __syncthreads();
     {
-        P2 *cp = (P2 *)lds_s + tid;
-        float *ang = (float *)((P2 *)lds_s + 16 * EVM_THREADS) + tid;
-        const float thr = a.thr[type];
-        const int total = np * ng;                      // <= 2048 * 2048
-        for (int idx = tid; idx < total; idx += EVM_THREADS) {
-            const int i = idx / ng, j = idx - i * ng;
-            float A[7], B[7];
-#pragma unroll
-            for (int q = 0; q < 7; ++q) { A[q] = pb[(size_t)i * 7 + q]; B[q] = gb[(size_t)j * 7 + q]; }
-            const float iou = a.box_type == DZ_EVAL_BOX_BEV ? rect_iou(A, B, cp, ang, EVM_THREADS)
-                                                            : pair_metric_ld<DZ_BOXM_IOU3D>(A, B, cp, ang, EVM_THREADS);
-            w[idx] = iou >= thr ? iou : 0.f;            // (NaN: 0)
-        }
-        for (int i = tid; i < np; i += EVM_THREADS) {
-            const float s = ps[i];
-            int k = -1;
-            for (int q = 0; q < EVM_K; ++q) k = s >= evm_cutoff(q) ? q : k;
-            cut[i] = k;
-        }
+        eval_pair_weights<EVM_THREADS>(pb, np, gb, ng, a.box_type, a.thr[type], lds_s, w);
+        eval_pred_cuts<EVM_THREADS>(ps, np, cut);
         int n1 = 0, n2 = 0;
         for (int j = tid; j < ng; j += EVM_THREADS) { n1 += gd[j] <= 1; n2 += gd[j] <= 2; }
         if (n1) atomicAdd(&word_s[1], n1);

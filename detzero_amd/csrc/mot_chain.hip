@@ -5,8 +5,8 @@
 // cutoffs, difficulty levels 1 and 2).  The metric core behind that file is not part of the reference; include/detzero_hip.h and
 // DESIGN.md 7o state the protocol these kernels compute.
 //
-// k_mot_weights: one workgroup per problem, one thread per pair - the thresholded IoU (box_geom.h's pair body with its per-thread LDS
-// columns, as phase 1 of k_eval_match) and each prediction's highest cutoff.  The weights serve all cutoffs.
+// k_mot_weights: one workgroup per problem, one thread per pair - the thresholded IoU and each prediction's highest cutoff, by the
+// functions of eval_pairs.h that phase 1 of k_eval_match calls too.  The weights serve all cutoffs.
 //
 // k_mot_chain<WAVES>: workgroup (chain descriptor c, cutoff k), WAVES * 64 threads.
 //   pass 0  every descriptor and id of the chain is range-checked before anything is followed; the same pass finds whether a
@@ -23,22 +23,18 @@
 #pragma clang fp contract(off)
 
 #include "box_geom.h"
+#include "eval_pairs.h"
 #include "lsa_wg.h"
 
 namespace dz {
 
 constexpr int MOTW_THREADS = 256;
-constexpr int MOTW_LDS_DOUBLES = 24 * MOTW_THREADS;                 // 16 P2 + 16 float per thread: 48 KiB
-constexpr int MOT_K = DZ_EVAL_CUTOFFS;
+constexpr int MOT_K = EVAL_K;
 constexpr int MOT_LDS_DIM = DZ_MOT_LDS_DIM;                         // P + G of a frame whose lists and solver vectors fit LDS
 constexpr int MOT_LIST_INTS = 4;                                    // per unit of P + G: colmatch / remC (G), rowflag / remR (P), twice over
 constexpr int MOT_WORK_BYTES = 40;                                  // per column: lsa_work_bytes(r, c) <= 40 c for r <= c
 constexpr int MOT_LDS_BYTES = MOT_LDS_DIM * (MOT_WORK_BYTES + MOT_LIST_INTS * 4);
 constexpr int MOT_SLOT = 2 * MOT_K * DZ_MOT_COUNTS;                 // int64 words of one shard
-
-typedef unsigned long long u64;
-
-__host__ __device__ inline float mot_cutoff(int k) { return k >= 100 ? 1.0f : (float)((double)k * 0.01); }
 
 // bytes of one cutoff's part of a chain slice: last (gt -> pred, pred -> gt), the id -> row table, and beyond the LDS bound the
 // per-frame lists and the solver's vectors
@@ -60,39 +56,20 @@ struct MotwArgs {
 };
 
 __global__ __launch_bounds__(MOTW_THREADS) void k_mot_weights(MotwArgs a) {
-    __shared__ double lds_s[MOTW_LDS_DOUBLES];          // rect_overlap's vertex and angle columns
+    __shared__ double lds_s[EvalPairLds<MOTW_THREADS>::DOUBLES];        // rect_overlap's vertex and angle columns: 48 KiB
     const int tid = threadIdx.x;
     const long long *d = a.pdesc + (size_t)blockIdx.x * DZ_MOT_PDESC_WORDS;
     const long long p0 = d[0], P = d[1], g0 = d[2], G = d[3], type = d[4], w_off = d[5];
     // a descriptor that leaves its buffers is not followed (uniform: every thread reads the same words)
-    const bool ok = p0 >= 0 && P >= 0 && g0 >= 0 && G >= 0 && P + G <= DZ_LSA_MAX_DIM && p0 <= a.n_pred && P <= a.n_pred - p0 &&
-                    g0 <= a.n_gt && G <= a.n_gt - g0 && type >= 0 && type <= 4 && w_off >= 0 && w_off <= a.w_len && P * G <= a.w_len - w_off;
+    const bool ok = eval_desc_ok(p0, P, g0, G, type, a.n_pred, a.n_gt) && w_off >= 0 && w_off <= a.w_len && P * G <= a.w_len - w_off;
     if (!ok) {
         if (tid == 0) atomicOr(a.status, DZ_EVAL_ST_DESC);
         return;
     }
     const int np = (int)P, ng = (int)G;
-    const float *pb = a.pred_box + (size_t)p0 * 7, *ps = a.pred_score + p0, *gb = a.gt_box + (size_t)g0 * 7;
-    float *w = a.weights + w_off;
-    P2 *cp = (P2 *)lds_s + tid;
-    float *ang = (float *)((P2 *)lds_s + 16 * MOTW_THREADS) + tid;
-    const float thr = a.thr[type];
-    const int total = np * ng;                          // <= 2048 * 2048
-    for (int idx = tid; idx < total; idx += MOTW_THREADS) {
-        const int i = idx / ng, j = idx - i * ng;
-        float A[7], B[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) { A[q] = pb[(size_t)i * 7 + q]; B[q] = gb[(size_t)j * 7 + q]; }
-        const float iou = a.box_type == DZ_EVAL_BOX_BEV ? rect_iou(A, B, cp, ang, MOTW_THREADS)
-                                                        : pair_metric_ld<DZ_BOXM_IOU3D>(A, B, cp, ang, MOTW_THREADS);
-        w[idx] = iou >= thr ? iou : 0.f;                // (NaN: 0)
-    }
-    for (int i = tid; i < np; i += MOTW_THREADS) {
-        const float s = ps[i];
-        int k = -1;
-        for (int q = 0; q < MOT_K; ++q) k = s >= mot_cutoff(q) ? q : k;
-        a.cut[p0 + i] = k;
-    }
+    eval_pair_weights<MOTW_THREADS>(a.pred_box + (size_t)p0 * 7, np, a.gt_box + (size_t)g0 * 7, ng, a.box_type, a.thr[type], lds_s,
+                                    a.weights + w_off);
+    eval_pred_cuts<MOTW_THREADS>(a.pred_score + p0, np, a.cut + p0);
 }
 
 struct MotArgs {
@@ -164,9 +141,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_mot_chain(MotArgs a) {
             const long long pr = fr[t];
             if (pr < 0 || pr >= a.n_problems) { bad = 1; break; }                                    // (uniform)
             const long long *d = a.pdesc + (size_t)pr * DZ_MOT_PDESC_WORDS;
-            const long long p0 = d[0], P = d[1], g0 = d[2], G = d[3], w_off = d[5];
-            if (!(p0 >= 0 && P >= 0 && g0 >= 0 && G >= 0 && P + G <= max_dim && p0 <= a.n_pred && P <= a.n_pred - p0 && g0 <= a.n_gt &&
-                  G <= a.n_gt - g0 && w_off >= 0 && w_off <= a.w_len && P * G <= a.w_len - w_off)) { bad = 1; break; }
+            const long long p0 = d[0], P = d[1], g0 = d[2], G = d[3], type = d[4], w_off = d[5];
+            if (!(eval_desc_ok(p0, P, g0, G, type, a.n_pred, a.n_gt) && P + G <= max_dim && w_off >= 0 && w_off <= a.w_len &&
+                  P * G <= a.w_len - w_off)) { bad = 1; break; }
             for (int r = tid; r < (int)P; r += NT) {
                 const int id = a.pred_id[p0 + r], ck = a.cut[p0 + r];
                 bad |= id < 0 || id >= n_pid;
@@ -266,7 +243,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mot_chain(MotArgs a) {
             const int df = gd[g], r = colmatch[g];
             n1 += df <= 1; n2 += df <= 2;
             if (r < 0) continue;
-            const u64 cst = (u64)llrint((1.0 - (double)w[(size_t)r * G + g]) * 4294967296.0);
+            const u64 cst = (u64)llrint((1.0 - (double)w[(size_t)r * G + g]) * EVAL_FIXED_ONE);
             ++m;
             if (df <= 1) { ++tp1; c1 += cst; }
             if (df <= 2) { ++tp2; c2 += cst; }
@@ -282,8 +259,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mot_chain(MotArgs a) {
     u64 v[9] = {tp1, tp2, n_in - m, n1 - tp1, n2 - tp2, mm1, mm2, c1, c2};     // (FP, MISS: per-thread parts, whole after the sum mod 2^64)
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, 64);
+        v[q] = eval_wave_sum(v[q]);
         if ((tid & 63) == 0 && v[q]) atomicAdd(&acc_s[q], v[q]);
     }
     __syncthreads();

@@ -2049,7 +2049,42 @@ EVAL_BOX_TYPES = {'3d': 0, 'bev': 1}              # DZ_EVAL_BOX_*
 EVAL_SCHEMES = {'atomic': 0, 'slots': 1}          # DZ_EVAL_ACC_*
 EVAL_STATUS = {1: 'a descriptor leaves its buffers or a limit', 2: 'a solve stopped at a loop bound',
                3: 'a descriptor leaves its buffers or a limit; a solve stopped at a loop bound'}
-EVAL_HA_ONE = float(1 << 32)                      # the table's HA column is fixed point with 32 fraction bits
+EVAL_FIXED_ONE = float(1 << 32)                   # the tables' HA and COST columns are fixed point with 32 fraction bits
+EVAL_HA_ONE = EVAL_FIXED_ONE
+
+
+def _eval_boxes(what, pred_box, pred_score, gt_box):
+    """The box and score arguments the evaluation ops share: (N,7) float32 boxes on the device, one float32 score per prediction."""
+    L.require_cuda(pred_box, pred_score, gt_box)
+    if any(b.dtype != torch.float32 or b.dim() != 2 or b.shape[1] != 7 for b in (pred_box, gt_box)):
+        raise L.DetZeroHipError('%s: boxes are (N,7) float32, got %s %s / %s %s'
+                                % (what, tuple(pred_box.shape), pred_box.dtype, tuple(gt_box.shape), gt_box.dtype))
+    if pred_score.dtype != torch.float32 or tuple(pred_score.shape) != (pred_box.shape[0],):
+        raise L.DetZeroHipError('%s: pred_score is (Np,) float32' % what)
+
+
+def _eval_thr(what, box_type, iou_thr):
+    """-> the five per-type IoU thresholds as the library takes them."""
+    if box_type not in EVAL_BOX_TYPES or len(iou_thr) != 5:
+        raise L.DetZeroHipError('%s: box_type %r / %d thresholds' % (what, box_type, len(iou_thr)))
+    return (ctypes.c_float * 5)(*[float(t) for t in iou_thr])
+
+
+def _eval_table(table, n_shards, width, dev, what):
+    """The (n_shards,2,101,width) int64 count table an op adds to: zeros when None, else the caller's, checked."""
+    if table is None:
+        return torch.zeros((max(int(n_shards), 1), 2, EVAL_CUTOFFS, width), dtype=torch.int64, device=dev)
+    if table.dtype != torch.int64 or tuple(table.shape) != (int(n_shards), 2, EVAL_CUTOFFS, width) or not table.is_cuda or \
+            not table.is_contiguous():
+        raise L.DetZeroHipError('%s: table is a contiguous (n_shards,2,101,%d) int64 device tensor' % (what, width))
+    return table
+
+
+def _eval_raise(status, what):
+    """One host read of a status word; raises when it is set."""
+    st = int(status.item())
+    if st != 0:
+        raise L.DetZeroHipError('%s: %s' % (what, EVAL_STATUS.get(st, st)))
 
 
 def eval_match_counts_nosync(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shards, box_type='3d', iou_thr=EVAL_IOU_THR,
@@ -2060,16 +2095,13 @@ def eval_match_counts_nosync(pred_box, pred_score, gt_box, gt_difficulty, desc, 
     (n,7) in the library's layout with ``ws_bytes`` given.  -> (table (n_shards,2,101,4) int64 [TP, FP, FN, HA * 2^32], status (1,)
     i32) on the device; ``table`` (zeros when None) is added to.  No host read: the caller looks at status."""
     lib = L.load()
-    L.require_cuda(pred_box, pred_score, gt_box, gt_difficulty)
-    if pred_box.dtype != torch.float32 or pred_box.dim() != 2 or pred_box.shape[1] != 7 or gt_box.dtype != torch.float32 or \
-            gt_box.dim() != 2 or gt_box.shape[1] != 7:
-        raise L.DetZeroHipError('eval_match_counts: boxes are (N,7) float32, got %s %s / %s %s'
-                                % (tuple(pred_box.shape), pred_box.dtype, tuple(gt_box.shape), gt_box.dtype))
-    if pred_score.dtype != torch.float32 or tuple(pred_score.shape) != (pred_box.shape[0],) or gt_difficulty.dtype != torch.int32 or \
-            tuple(gt_difficulty.shape) != (gt_box.shape[0],):
-        raise L.DetZeroHipError('eval_match_counts: pred_score is (Np,) float32 and gt_difficulty (Ng,) int32')
-    if box_type not in EVAL_BOX_TYPES or scheme not in EVAL_SCHEMES or len(iou_thr) != 5:
-        raise L.DetZeroHipError('eval_match_counts: box_type %r / scheme %r / %d thresholds' % (box_type, scheme, len(iou_thr)))
+    _eval_boxes('eval_match_counts', pred_box, pred_score, gt_box)
+    L.require_cuda(gt_difficulty)
+    if gt_difficulty.dtype != torch.int32 or tuple(gt_difficulty.shape) != (gt_box.shape[0],):
+        raise L.DetZeroHipError('eval_match_counts: gt_difficulty is (Ng,) int32')
+    thr = _eval_thr('eval_match_counts', box_type, iou_thr)
+    if scheme not in EVAL_SCHEMES:
+        raise L.DetZeroHipError('eval_match_counts: scheme %r' % (scheme,))
     dev = pred_box.device
     if torch.is_tensor(desc):
         L.require_cuda(desc)
@@ -2094,14 +2126,10 @@ def eval_match_counts_nosync(pred_box, pred_score, gt_box, gt_difficulty, desc, 
         else:
             ws_bytes = 0
         d_desc = torch.from_numpy(full).to(dev) if n else None
-    if table is None:
-        table = torch.zeros((max(int(n_shards), 1), 2, EVAL_CUTOFFS, 4), dtype=torch.int64, device=dev)
-    elif table.dtype != torch.int64 or tuple(table.shape) != (int(n_shards), 2, EVAL_CUTOFFS, 4) or not table.is_cuda or not table.is_contiguous():
-        raise L.DetZeroHipError('eval_match_counts: table is a contiguous (n_shards,2,101,4) int64 device tensor')
+    table = _eval_table(table, n_shards, 4, dev, 'eval_match_counts')
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     ws = _ws(ws_bytes)
     slots = torch.empty((max(n, 1) * 2 * EVAL_CUTOFFS * 4,), dtype=torch.int64, device=dev) if scheme == 'slots' else None
-    thr = (ctypes.c_float * 5)(*[float(t) for t in iou_thr])
 
     def launch():
         rc = lib.dz_eval_match_counts(L.ptr(pred_box), L.ptr(pred_score), pred_box.shape[0], L.ptr(gt_box), L.ptr(gt_difficulty), gt_box.shape[0],
@@ -2120,9 +2148,7 @@ def eval_match_counts(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shard
     """eval_match_counts_nosync, then one host read: the table as a host int64 array (n_shards,2,101,4); raises when the status
     word is set."""
     table, status = eval_match_counts_nosync(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shards, box_type, iou_thr, scheme)
-    st = int(status.item())
-    if st != 0:
-        raise L.DetZeroHipError('eval_match_counts: %s' % EVAL_STATUS.get(st, st))
+    _eval_raise(status, 'eval_match_counts')
     return table.cpu().numpy()[:int(n_shards)]
 
 
@@ -2132,7 +2158,7 @@ def eval_match_counts(pred_box, pred_score, gt_box, gt_difficulty, desc, n_shard
 MOT_COUNTS = 5                     # DZ_MOT_COUNTS: TP, FP, MISS, MISMATCH, COST * 2^32
 MOT_LDS_DIM = 192                  # DZ_MOT_LDS_DIM
 MOT_MAPPINGS = {'wave': 0, 'workgroup': 1}        # DZ_MOT_MAP_*
-MOT_COST_ONE = float(1 << 32)
+MOT_COST_ONE = EVAL_FIXED_ONE
 
 
 def mot_problem_desc(desc):
@@ -2156,12 +2182,8 @@ def mot_weights(pred_box, pred_score, gt_box, pdesc, w_len, box_type='3d', iou_t
     grouped by problem; pdesc: host (n,6) int64 of mot_problem_desc.  -> (weights (w_len,) f32, cut (Np,) i32) on the device: the
     thresholded IoU of every pair of every problem and each prediction's highest cutoff (-1 = none).  One host read (the status)."""
     lib = L.load()
-    L.require_cuda(pred_box, pred_score, gt_box)
-    if pred_box.dtype != torch.float32 or pred_box.dim() != 2 or pred_box.shape[1] != 7 or gt_box.dtype != torch.float32 or \
-            gt_box.dim() != 2 or gt_box.shape[1] != 7 or pred_score.dtype != torch.float32 or tuple(pred_score.shape) != (pred_box.shape[0],):
-        raise L.DetZeroHipError('mot_weights: boxes are (N,7) float32 and pred_score (Np,) float32')
-    if box_type not in EVAL_BOX_TYPES or len(iou_thr) != 5:
-        raise L.DetZeroHipError('mot_weights: box_type %r / %d thresholds' % (box_type, len(iou_thr)))
+    _eval_boxes('mot_weights', pred_box, pred_score, gt_box)
+    thr = _eval_thr('mot_weights', box_type, iou_thr)
     dev = pred_box.device
     pdesc = np.asarray(pdesc, dtype=np.int64).reshape(-1, 6)
     n = pdesc.shape[0]
@@ -2170,7 +2192,6 @@ def mot_weights(pred_box, pred_score, gt_box, pdesc, w_len, box_type='3d', iou_t
     cut = torch.full((max(pred_box.shape[0], 1),), -1, dtype=torch.int32, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     d_desc = torch.from_numpy(pdesc).to(dev) if n else None
-    thr = (ctypes.c_float * 5)(*[float(t) for t in iou_thr])
 
     def launch():
         rc = lib.dz_mot_weights(L.ptr(pred_box), L.ptr(pred_score), pred_box.shape[0], L.ptr(gt_box), gt_box.shape[0], L.ptr(d_desc), n,
@@ -2181,9 +2202,7 @@ def mot_weights(pred_box, pred_score, gt_box, pdesc, w_len, box_type='3d', iou_t
         launch()
     else:
         PROFILER.wrap('mot_weights[%s]' % box_type, 0., 0., launch)
-    st = int(status.item())
-    if st != 0:
-        raise L.DetZeroHipError('mot_weights: %s' % EVAL_STATUS.get(st, st))
+    _eval_raise(status, 'mot_weights')
     return weights[:int(w_len)], cut[:pred_box.shape[0]]
 
 
@@ -2216,11 +2235,7 @@ def mot_chain_counts_nosync(weights, cut, pred_id, gt_id, gt_difficulty, pdesc, 
     for i in range(nc):                                 # (a bad descriptor gets no room: the kernel refuses it by its own check)
         full[i, 6] = ws_bytes
         ws_bytes += mot_chain_ws_bytes(cdesc[i, 3], cdesc[i, 4], cdesc[i, 5])
-    if table is None:
-        table = torch.zeros((max(int(n_shards), 1), 2, EVAL_CUTOFFS, MOT_COUNTS), dtype=torch.int64, device=dev)
-    elif table.dtype != torch.int64 or tuple(table.shape) != (int(n_shards), 2, EVAL_CUTOFFS, MOT_COUNTS) or not table.is_cuda or \
-            not table.is_contiguous():
-        raise L.DetZeroHipError('mot_chain_counts: table is a contiguous (n_shards,2,101,5) int64 device tensor')
+    table = _eval_table(table, n_shards, MOT_COUNTS, dev, 'mot_chain_counts')
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     ws = _ws(ws_bytes)
     d_pdesc = torch.from_numpy(pdesc).to(dev) if n else None
@@ -2245,9 +2260,7 @@ def mot_chain_counts(weights, cut, pred_id, gt_id, gt_difficulty, pdesc, cdesc, 
     """mot_chain_counts_nosync, then one host read: the table as a host int64 array (n_shards,2,101,5); raises when the status
     word is set."""
     table, status = mot_chain_counts_nosync(weights, cut, pred_id, gt_id, gt_difficulty, pdesc, cdesc, frames, n_shards, mapping, merge)
-    st = int(status.item())
-    if st != 0:
-        raise L.DetZeroHipError('mot_chain_counts: %s' % EVAL_STATUS.get(st, st))
+    _eval_raise(status, 'mot_chain_counts')
     return table.cpu().numpy()[:int(n_shards)]
 
 

@@ -14,19 +14,18 @@ the pair weights once (``ops.mot_weights``) and walks one chain per (sequence, s
         [--evaluate_metrics object range] [--iou_type 3d|bev] [--class_name ...] [--info_with_fakelidar] [--human_study]
 """
 import argparse
-import copy
-import os
 import pickle
 import sys
-from collections import defaultdict
 
 import numpy as np
 
+from . import waymo_eval
 from .lib import DetZeroHipError
-from .waymo_eval import (HUMAN_STUDY_LIST, IOU_THRESHOLDS, N_CUTOFFS, RANGE_NAMES, breakdown_names, limit_period, score_cutoffs, shard_ids,
+from .ops import EVAL_FIXED_ONE
+from .waymo_eval import (CATEGORY_LABELS, CATEGORY_TYPES, IOU_THRESHOLDS, N_CUTOFFS, RANGE_NAMES, box7, breakdown_names, build_config,
+                         check_count_table, detzero_eval_main, format_table, gt_frame, limit_period, normalise_scores, rows_by_shard,
                          shard_type)
 
-COST_ONE = 4294967296.0
 METRIC_KEYS = ('MOTA', 'MOTP', 'MISS', 'MISMATCH', 'FP')
 # The `last` arrays of a group's chains (101 cutoffs each) and its weights stay under this many bytes.  A 200-frame sequence of
 # tools/bench_waymo_track_eval.py needs about 2 MiB of both with ['object', 'range'] (1.7 MiB of it `last`), so a group holds on
@@ -40,15 +39,7 @@ def metrics_from_mot_counts(table, config_type=None):
     [value]} in float64: the values of the cutoff with the highest MOTA (the lowest k among equals); N = TP + MISS = 0 gives zeros.
     config_type defaults by the shard count: 4 = ['object'], 12 = ['range'], 16 = both."""
     table = np.asarray(table)
-    if table.ndim != 4 or table.shape[1:] != (2, N_CUTOFFS, 5):
-        raise DetZeroHipError('metrics_from_mot_counts: a (n_shards, 2, 101, 5) table, got %s' % (table.shape,))
-    if config_type is None:
-        config_type = {4: ['object'], 12: ['range'], 16: ['object', 'range']}.get(table.shape[0])
-        if config_type is None:
-            raise DetZeroHipError('metrics_from_mot_counts: %d shards name no configuration' % table.shape[0])
-    names = breakdown_names(config_type)
-    if len(names) != table.shape[0]:
-        raise DetZeroHipError('metrics_from_mot_counts: %d shards for %s' % (table.shape[0], list(config_type)))
+    names, config_type = check_count_table(table, 5, config_type, 'metrics_from_mot_counts')
     t = table.astype(np.float64)
     out = {}
     for s, name in enumerate(names):
@@ -59,7 +50,7 @@ def metrics_from_mot_counts(table, config_type=None):
             if n[0] > 0:
                 mota = 1.0 - (miss + mm + fp) / n
                 k = int(np.argmax(mota))                        # the first of the maxima
-                values = [mota[k], cost[k] / COST_ONE / tp[k] if tp[k] > 0 else 0.0, miss[k] / n[k], mm[k] / n[k], fp[k] / n[k]]
+                values = [mota[k], cost[k] / EVAL_FIXED_ONE / tp[k] if tp[k] > 0 else 0.0, miss[k] / n[k], mm[k] / n[k], fp[k] / n[k]]
             for key, v in zip(METRIC_KEYS, values):
                 out['%s_LEVEL_%d/%s' % (name, lv + 1, key)] = [float(v)]
     return out
@@ -94,19 +85,9 @@ def chain_arrays(config_type, pd, gt):
         if np.unique(pairs).size != pairs.size:
             raise DetZeroHipError('waymo_evaluation: a %s object id appears twice in one frame' % what)
         dense, n_ids = _dense_per_sequence(seq, oid, len(names))           # (the other side may hold sequences this one lacks)
-        boxes = np.asarray(boxes, dtype=np.float32).reshape(len(frame), -1) if len(frame) else np.zeros((0, 7), dtype=np.float32)
-        if boxes.shape[1] != 7:                                 # [x, y, dx, dy, heading]: z = 0, dz = 1 (the BEV IoU reads neither)
-            b = np.zeros((len(boxes), 7), dtype=np.float32)
-            b[:, [0, 1, 3, 4, 6]] = boxes
-            b[:, 5] = 1.0
-            boxes = b
-        keys, rows = [], []
-        for ids in shard_ids(config_type, obj_type, boxes):
-            at = np.flatnonzero(ids >= 0)
-            keys.append((seq[at] * n_shards + ids[at]) * n_frames + frame[at])
-            rows.append(at)
-        keys = np.concatenate(keys) if keys else np.zeros((0,), np.int64)
-        rows = np.concatenate(rows) if rows else np.zeros((0,), np.int64)
+        boxes = box7(boxes)
+        rows, shards = rows_by_shard(config_type, obj_type, boxes)
+        keys = (seq[rows] * n_shards + shards) * n_frames + frame[rows]
         return keys, boxes[rows], dense[rows].astype(np.int32), np.asarray(col).astype(dtype)[rows], n_ids
 
     pk, pb, pi, ps, n_pid = side('prediction', pd[0], pd[1], pd[2], pd[3], pd[4], pd[5], np.float32)
@@ -191,9 +172,7 @@ def chain_counts(arrays, box_type='3d', mapping='wave', merge=True, cap=WORKSPAC
     finally:
         ops.PROFILER = saved
     for status in statuses:
-        st = int(status.item())
-        if st != 0:
-            raise DetZeroHipError('mot_chain_counts: %s' % ops.EVAL_STATUS.get(st, st))
+        ops._eval_raise(status, 'mot_chain_counts')
     return table.cpu().numpy()
 
 
@@ -203,32 +182,17 @@ class WaymoTrackingMetricsEstimator:
     def generate_waymo_type_results(self, infos, class_names, is_gt=False, fake_gt_infos=True):
         """waymo_eval_tracking.py:20-101, on copies: the caller's dicts are not written (the reference rewrites ``difficulty`` and
         ``gt_boxes_lidar`` in place).  A ground-truth info is the whole info (with 'annos') or the annos with 'sequence_name'."""
-        def boxes3d_kitti_fakelidar_to_lidar(boxes3d_lidar):
-            boxes3d_lidar = np.array(boxes3d_lidar, copy=True)
-            w, l, h, r = boxes3d_lidar[:, 3:4], boxes3d_lidar[:, 4:5], boxes3d_lidar[:, 5:6], boxes3d_lidar[:, 6:7]
-            boxes3d_lidar[:, 2] += h[:, 0] / 2
-            return np.concatenate([boxes3d_lidar[:, 0:3], l, w, h, -(r + np.pi / 2)], axis=-1)
-
         frame_id, sequence_id, object_id, boxes3d, obj_type, score, overlap_nlz, difficulty, speed = [], [], [], [], [], [], [], [], []
         sequence_id_dict, object_id_dict = {}, {}
         for frame_index, info in enumerate(infos):
             sequence_name = info['sequence_name']
             if is_gt:
                 annos = info['annos'] if 'annos' in info else info
-                box_mask = np.array([n in class_names for n in annos['name']], dtype=np.bool_)
-                if 'num_points_in_gt' not in annos:
-                    raise NotImplementedError('Please provide the num_points_in_gt for evaluating on Waymo Dataset (infos created '
-                                              'before 20201126 lack it: re-create the validation infos)')
-                diff = np.array(annos['difficulty'], copy=True)
-                zero_difficulty_mask = diff == 0
-                diff[(annos['num_points_in_gt'] > 5) & zero_difficulty_mask] = 1
-                diff[(annos['num_points_in_gt'] <= 5) & zero_difficulty_mask] = 2
-                box_mask = box_mask & (annos['num_points_in_gt'] > 0)
+                box_mask, diff, gt_boxes = gt_frame(annos, class_names, fake_gt_infos)
                 num_boxes = box_mask.sum()
                 box_name = annos['name'][box_mask]
                 difficulty.append(diff[box_mask])
                 score.append(np.ones(num_boxes))
-                gt_boxes = boxes3d_kitti_fakelidar_to_lidar(annos['gt_boxes_lidar']) if fake_gt_infos else np.asarray(annos['gt_boxes_lidar'])
                 boxes3d.append(gt_boxes[box_mask][:, :7])
                 speed.append(gt_boxes[box_mask][:, 7:])
                 ids = np.asarray(annos['obj_ids'])[box_mask]
@@ -267,15 +231,7 @@ class WaymoTrackingMetricsEstimator:
     def build_config(self, config_type):
         """waymo_eval_tracking.py:103-137 as a plain dict; 'bev' alone selects the BEV IoU as in the detection mirror (the reference's
         tracking configuration is always TYPE_3D)."""
-        breakdowns = [b for b, key in (('OBJECT_TYPE', 'object'), ('RANGE', 'range')) if key in config_type]
-        return {
-            'breakdown_generator_ids': breakdowns,
-            'difficulties': [[1, 2] for _ in breakdowns],
-            'matcher_type': 'TYPE_HUNGARIAN',
-            'iou_thresholds': list(IOU_THRESHOLDS),
-            'box_type': 'TYPE_2D' if ('bev' in config_type and '3d' not in config_type) else 'TYPE_3D',
-            'score_cutoffs': score_cutoffs().tolist(),
-        }
+        return build_config(config_type)
 
     def mask_by_distance(self, distance_thresh, boxes_3d, *args):
         """waymo_eval_tracking.py:219-227: the mask passes every box (distance < inf)."""
@@ -295,10 +251,7 @@ class WaymoTrackingMetricsEstimator:
             distance_thresh, pd_boxes3d, pd_frameid, pd_seq, pd_objid, pd_type, pd_score, pd_nlz, pd_speed)
         gt_boxes3d, gt_frameid, gt_seq, gt_objid, gt_type, gt_score, gt_difficulty, gt_speed = self.mask_by_distance(
             distance_thresh, gt_boxes3d, gt_frameid, gt_seq, gt_objid, gt_type, gt_score, gt_difficulty, gt_speed)
-        if len(pd_score) and pd_score.max() > 1:
-            pd_score = 1 / (1 + np.exp(-pd_score))
-            print('Warning: Waymo evaluation only supports normalized scores')
-        return ((pd_frameid, pd_seq, pd_objid, pd_boxes3d, pd_type, pd_score), (gt_frameid, gt_seq, gt_objid, gt_boxes3d, gt_type, gt_difficulty))
+        return ((pd_frameid, pd_seq, pd_objid, pd_boxes3d, pd_type, normalise_scores(pd_score)), (gt_frameid, gt_seq, gt_objid, gt_boxes3d, gt_type, gt_difficulty))
 
     def waymo_evaluation(self, prediction_infos, gt_infos, class_name, config_type=['object'], distance_thresh=100, fake_gt_infos=True,
                          mapping='wave', timings=None):
@@ -324,103 +277,32 @@ class WaymoTrackingMetricsEstimator:
 
 
 def pair_by_frame(det_result, gt_infos, human_study=False):
-    """detzero_eval.py:56-105 with --tracking: the whole ground-truth info (:84) looked up by (sequence_name, frame_id) for every
-    prediction item; frames without a prediction get an empty one.  The pairs are then put in (sequence, frame) order - the
-    estimator walks a sequence's frames in list order - which the reference leaves to the order of the result file."""
-    gt_table, missed = defaultdict(dict), defaultdict(dict)
-    for item in gt_infos:
-        if human_study and item['sequence_name'] not in HUMAN_STUDY_LIST:
-            continue
-        gt_table[item['sequence_name']][item['sample_idx']] = item
-        missed[item['sequence_name']][item['sample_idx']] = item
-    pairs = []
-    for item in det_result:
-        if human_study and item['sequence_name'] not in HUMAN_STUDY_LIST:
-            continue
-        pairs.append((copy.deepcopy(item), copy.deepcopy(gt_table[item['sequence_name']][item['frame_id']])))
-        del missed[item['sequence_name']][item['frame_id']]
-    notes = []
-    for seq in missed:
-        for frame in missed[seq]:
-            notes.append('sequence:{}, frame:{} is missed'.format(seq, frame))
-            pairs.append(({'sequence_name': seq, 'frame_id': frame, 'boxes_lidar': np.array([]).reshape(0, 7), 'score': np.array([]),
-                           'name': np.array([]), 'obj_ids': np.array([])}, missed[seq][frame]))
-    pairs.sort(key=lambda pair: (pair[0]['sequence_name'], pair[0]['frame_id']))
-    return [p for p, _ in pairs], [g for _, g in pairs], notes
+    """detzero_eval.py:56-105 with --tracking: the whole ground-truth info (:84) of every prediction item, the pairs in (sequence,
+    frame) order - the estimator walks a sequence's frames in list order."""
+    return waymo_eval.pair_by_frame(det_result, gt_infos, human_study, whole_info=True, ordered=True)
 
 
 def result_table(mot_dict, evaluate_metrics):
     """detzero_eval.py:164-206: one row per category and level (the reference's range rows read detection keys; here they carry
     the tracking figures too)."""
-    header = ['Category', 'MOTA', 'MOTP', 'MISS', 'MISMATCH', 'FP']
     rows = []
 
     def two(label, name):
         return [(label,) + tuple(mot_dict['%s_LEVEL_%d/%s' % (name, lv, m)][0] for m in METRIC_KEYS) for lv in (1, 2)]
 
-    labels = ('Vehicle', 'Pedestrain', 'Cyclist', 'Sign')                       # detzero_eval.py:166-205 (its spelling)
-    types = ('VEHICLE', 'PEDESTRIAN', 'CYCLIST', 'SIGN')
     if 'object' in evaluate_metrics:
-        for lb, t in zip(labels, types):
+        for lb, t in zip(CATEGORY_LABELS, CATEGORY_TYPES):
             rows += two(lb, 'OBJECT_TYPE_TYPE_%s' % t)
     if 'range' in evaluate_metrics:
-        for t in types:
+        for t in CATEGORY_TYPES:
             for r in RANGE_NAMES:
                 rows += two('%s_%s' % (t.capitalize(), r), 'RANGE_TYPE_%s_%s' % (t, r))
-    try:
-        from tabulate import tabulate
-        return tabulate(rows, headers=header, tablefmt='grid').splitlines()
-    except ImportError:
-        lines = ['%-24s' % header[0] + ''.join('%10s' % h for h in header[1:])]
-        return lines + ['%-24s' % r[0] + ''.join('%10.4f' % v for v in r[1:]) for r in rows]
+    return format_table(['Category'] + list(METRIC_KEYS), rows)
 
 
 def main_detzero_eval(argv=None):
     """The command line of evaluator/detzero_eval.py with --tracking implied."""
-    parser = argparse.ArgumentParser(description='Offline tracking evaluation (MOTA / MOTP) on the device.')
-    parser.add_argument('--det_result_path', type=str, default='', help='path to the tracking result file')
-    parser.add_argument('--gt_info_path', type=str, default='../data/waymo/waymo_infos_val.pkl', help='path to ground-truth info pkl file')
-    parser.add_argument('--evaluate_metrics', nargs='+', default=['object'], help='object, range or both')
-    parser.add_argument('--iou_type', type=str, default='3d', help='3d or bev')
-    parser.add_argument('--class_name', nargs='+', default=['Vehicle', 'Pedestrian', 'Cyclist'])
-    parser.add_argument('--info_with_fakelidar', action='store_true', default=False)
-    parser.add_argument('--distance_thresh', type=int, default=1000)
-    parser.add_argument('--tracking', action='store_true', default=True, help='(implied)')
-    parser.add_argument('--human_study', action='store_true', default=False)
-    args = parser.parse_args(argv)
-    if any(item not in ['object', 'range'] for item in args.evaluate_metrics):
-        raise ValueError('evaluate_metrics error')
-    if args.iou_type not in ('3d', 'bev'):
-        raise KeyError(args.iou_type)
-    log_path = os.path.join(os.path.dirname(os.path.abspath(args.det_result_path)), 'mAP.txt')
-    log_file = open(log_path, 'a')
-
-    def log(line=''):
-        print(line, flush=True)
-        log_file.write(line + '\n')
-
-    log(str(args))
-    with open(args.gt_info_path, 'rb') as f:
-        gt_infos = pickle.load(f)
-    with open(args.det_result_path, 'rb') as f:
-        det_result = pickle.load(f)
-    log('Prediction Set Length: {}, Ground Truth Set Length: {}.'.format(len(det_result), len(gt_infos)))
-    eval_det, eval_gt, notes = pair_by_frame(det_result, gt_infos, args.human_study)
-    for note in notes:
-        log(note)
-    log('\tEvaluation data pair: ' + str(len(eval_gt)))
-    mot_dict = WaymoTrackingMetricsEstimator().waymo_evaluation(
-        eval_det, eval_gt, config_type=args.evaluate_metrics + [args.iou_type], class_name=args.class_name,
-        distance_thresh=args.distance_thresh, fake_gt_infos=args.info_with_fakelidar)
-    log('================= Evaluation Result =================')
-    log(args.det_result_path)
-    for key in mot_dict:
-        log('%s: %.4f ' % (key, mot_dict[key][0]))
-    for line in result_table(mot_dict, args.evaluate_metrics):
-        log(line)
-    log('The whole evaulation process is done.')
-    log_file.close()
-    return mot_dict
+    return detzero_eval_main(argv, tracking=True)
 
 
 def main(argv=None):

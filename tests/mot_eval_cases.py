@@ -129,6 +129,15 @@ def scene(seed):
             'gt_type': np.array([g[4] for g in gt], dtype=np.int64), 'gt_diff': np.array([g[5] for g in gt], dtype=np.int32)}
 
 
+def one_frame_sequences(det):
+    """A detection scene (tests/waymo_eval_cases.py) as a tracking scene: every frame a sequence of its own and every object an id
+    of its own, so nothing is carried and nothing can mismatch."""
+    out = {k: det[k] for k in ('pd_frame', 'pd_box', 'pd_type', 'pd_score', 'gt_frame', 'gt_box', 'gt_type', 'gt_diff')}
+    out.update(pd_seq=det['pd_frame'].copy(), gt_seq=det['gt_frame'].copy(), pd_id=np.arange(len(det['pd_frame']), dtype=np.int64),
+               gt_id=np.arange(len(det['gt_frame']), dtype=np.int64))
+    return out
+
+
 def frames_of(s):
     """The (sequence, frame) pairs of a scene in walking order."""
     return sorted(set(zip(s['pd_seq'].tolist(), s['pd_frame'].tolist())) | set(zip(s['gt_seq'].tolist(), s['gt_frame'].tolist())))

@@ -211,3 +211,26 @@ def test_an_empty_side_through_waymo_evaluation(device, dataset, side, seq):
         assert side == 'gt' or got['OBJECT_TYPE_TYPE_VEHICLE_LEVEL_2/MISS'] == [1.0]
     else:
         assert got['OBJECT_TYPE_TYPE_PEDESTRIAN_LEVEL_2/MISMATCH'][0] > 0
+
+
+@pytest.mark.parametrize('box_type', ['3d', 'bev'])
+def test_one_frame_sequences_count_as_detection(device, box_type):
+    """Where every sequence is one frame, no pair is carried and no mismatch can occur: the tracking table's [TP, FP, MISS] is the
+    detection table's [TP, FP, FN] at every shard, level and cutoff, both from the device (tests/test_waymo_track_eval_cpu.py holds
+    the two restatements to the same identity on this scene)."""
+    import torch
+    from detzero_amd import ops, waymo_eval
+    from tests import waymo_eval_cases as det_cases
+    det = det_cases.scene(*det_cases.SCENES[0])
+    config = ['object', 'range']
+    arrays = waymo_eval.problem_arrays(config, *det_cases.flat(det))
+    want = waymo_eval.match_counts(config, det['n_frames'], *arrays, box_type=box_type, device=device)      # ops.eval_match_counts
+    probs = ref.problems(config, box_type, cases.one_frame_sequences(det))
+    _, _, pid, gid, gd, pdesc, cdesc, frames = cases.device_inputs(probs)
+    pdesc6, w_len = ops.mot_problem_desc(pdesc)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    w, cut = ops.mot_weights(t(np.concatenate([p['pb'] for p in probs])), t(np.concatenate([p['score'] for p in probs])),
+                             t(np.concatenate([p['gb'] for p in probs])), pdesc6, w_len, box_type)
+    got = ops.mot_chain_counts(w, cut, t(pid), t(gid), t(gd), pdesc6, cdesc, frames, 16)
+    assert got.shape[:3] == want.shape[:3] == (16, 2, 101) and want[..., 0].max() > 0 and want[..., 1].max() > 0
+    assert np.array_equal(got[..., :3], want[..., :3]) and not got[..., 3].any()

@@ -232,6 +232,20 @@ def test_scenes_are_what_they_claim(scenes):
         assert ped[0, 4] > sum(int(np.round((1.0 - p['w'][r, c]) * ref.ONE)) for p, m in afresh for r, c in m)
 
 
+@pytest.mark.parametrize('box_type', ['3d', 'bev'])
+def test_one_frame_sequences_count_as_detection(box_type):
+    """Where every sequence is one frame, no pair is carried and no mismatch can occur: the tracking table's [TP, FP, MISS] is the
+    detection table's [TP, FP, FN] at every shard, level and cutoff.  (The scene passes the detection margin conditions, so the
+    optimum's pair set is unique.)"""
+    from tests import waymo_eval_cases as det_cases
+    det = det_cases.scene(*det_cases.SCENES[0])
+    config = ['object', 'range']
+    want = ref.det_ref.counts(config, box_type, *det_cases.flat(det))[0]
+    got = ref.counts(config, box_type, cases.one_frame_sequences(det))
+    assert got.shape[:3] == want.shape[:3] == (16, 2, 101) and want[..., 0].max() > 0 and want[..., 1].max() > 0
+    assert np.array_equal(got[..., :3], want) and not got[..., 3].any()
+
+
 def test_header_symbols_are_in_the_library():
     from detzero_amd import lib as L
     from detzero_amd.build import build
