@@ -100,6 +100,23 @@ class CenterPoint(nn.Module):
         loss, tb_dict = self.dense_head.get_loss()
         return loss, tb_dict, {}
 
+    def head_loss_backward(self, batch_dict):
+        """Head fine-tuning with everything in front of the head frozen: the stages run as in ``forward`` up to the dense head, which then
+        runs ``CenterHead.loss_backward`` on the batch's ``gt_boxes`` - the gradient of the first-stage loss accumulates in the
+        ``.grad`` of ``dense_head``'s parameters.  -> (loss, tb_dict, disp_dict) as ``get_training_loss``.  The model stays in eval
+        mode; after an optimiser step call ``dense_head.invalidate()``."""
+        if self.training:
+            raise DetZeroHipError('CenterPoint: training is out of scope of the HIP backend; call .eval()')
+        if self.second_stage or self.model_cfg.get('ROI_HEAD', None) is not None:
+            raise DetZeroHipError('CenterPoint.head_loss_backward: the PDV head\'s losses (ROI_HEAD) are not built; only the '
+                                  'first-stage CenterHead loss is provided')
+        for cur_module in self.module_list:
+            if cur_module is self.dense_head:
+                break
+            batch_dict = cur_module(batch_dict)
+        loss, tb_dict = self.dense_head.loss_backward(batch_dict)
+        return loss, tb_dict, {}
+
     def post_processing(self, batch_dict):
         """centerpoint.py:283-307 (one-stage branch; with TTA the copies' boxes are restored and fused, :298-306)."""
         post_process_cfg = self.model_cfg.POST_PROCESSING

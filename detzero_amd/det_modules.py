@@ -1341,7 +1341,7 @@ class CenterHead(_Cached):
         rot_loss_head_i, iou_loss_head_i when IOU_WEIGHT > 0, rpn_loss) as floats read with ONE device-to-host copy of the heads'
         records.  Unlike the reference it does not overwrite ``pred_dicts[i]['hm']`` with its sigmoid (the clamped sigmoid is part of
         the kernel), so calling it twice gives the same result.  Targets of either route of ``assign_targets`` are accepted."""
-        from .head_loss import head_losses, head_map_of
+        from .head_loss import head_losses, head_map_of, tb_dict_of
         pred_dicts = self.forward_ret_dict.get('pred_dicts', None)
         target_dicts = self.forward_ret_dict.get('target_dicts', None)
         if pred_dicts is None or target_dicts is None:
@@ -1355,18 +1355,18 @@ class CenterHead(_Cached):
         totals, recs = head_losses(self, heads, target_dicts, h, w)
         loss = totals[0] if len(totals) == 1 else torch.stack(totals).sum()
         host = torch.stack(recs).cpu().numpy()               # the one host read
-        for idx in range(len(heads)):
-            r = host[idx]
-            tb_dict['center_loss_head_%d' % idx] = float(r[1] + r[2])
-            tb_dict['center_z_loss_head_%d' % idx] = float(r[3])
-            tb_dict['dim_loss_head_%d' % idx] = float(r[4] + r[5] + r[6])
-            tb_dict['rot_loss_head_%d' % idx] = float(r[7] + r[8])
-            if self.iou_weight > 0:
-                tb_dict['iou_loss_head_%d' % idx] = float(r[10])
-            tb_dict['hm_loss_head_%d' % idx] = float(r[0])
-            tb_dict['loc_loss_head_%d' % idx] = float(r[9])
-        tb_dict['rpn_loss'] = float(host[:, 11].sum())
-        return loss, tb_dict
+        return loss, tb_dict_of(host, self.iou_weight, tb_dict)
+
+    def loss_backward(self, data_dict):
+        """One backward pass of the head's loss down to the head's parameters, BatchNorm in eval mode (frozen statistics; the module
+        stays in eval mode): from ``spatial_features_2d`` (or the ``_nhwc_*`` keys) and ``gt_boxes`` (B, M, 8) of the batch - an fp32
+        forward of the head (math mode 0, engines off, buffers of its own), device targets, ``ops.centerhead_loss`` on each head map
+        with its gradient, then ``head_backward.head_gradients`` (csrc/head_backward.hip).  The result is accumulated
+        into the ``.grad`` of the head's parameters, created where it is None, as autograd would do.  -> (loss, tb_dict) with the
+        reference's keys, as ``get_loss``.  ``forward`` and ``forward_ret_dict`` are untouched.  After an optimiser step on the
+        parameters call ``invalidate()``: the kernels read the cached plan, not the parameters."""
+        from .head_backward import loss_backward
+        return loss_backward(self, data_dict)
 
     def plan(self):
         if self._plan is not None:

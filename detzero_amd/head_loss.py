@@ -122,3 +122,19 @@ def head_losses(head_module, heads, target_dicts, h, w):
         totals.append(total)
         recs.append(rec)
     return totals, recs
+
+
+def tb_dict_of(host, iou_weight, tb_dict):
+    """The reference's tb_dict keys (center_head.py:266-313) from the heads' (n_heads, 12) records on the host."""
+    for idx in range(host.shape[0]):
+        r = host[idx]
+        tb_dict['center_loss_head_%d' % idx] = float(r[1] + r[2])
+        tb_dict['center_z_loss_head_%d' % idx] = float(r[3])
+        tb_dict['dim_loss_head_%d' % idx] = float(r[4] + r[5] + r[6])
+        tb_dict['rot_loss_head_%d' % idx] = float(r[7] + r[8])
+        if iou_weight > 0:
+            tb_dict['iou_loss_head_%d' % idx] = float(r[10])
+        tb_dict['hm_loss_head_%d' % idx] = float(r[0])
+        tb_dict['loc_loss_head_%d' % idx] = float(r[9])
+    tb_dict['rpn_loss'] = float(host[:, 11].sum())
+    return tb_dict

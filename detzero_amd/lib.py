@@ -322,6 +322,14 @@ _SIGS = {
     'dz_centerhead_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                    ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_double), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dz_conv3x3_wgrad_ws_bytes': (c_size_t, [c_int] * 6),
+    'dz_conv3x3_wgrad': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                                 ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dz_relu_grad_ws_bytes': (c_size_t, [c_int] * 4),
+    'dz_relu_grad': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dz_head_final_backward_ws_bytes': (c_size_t, [c_int] * 5),
+    'dz_head_final_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                                       ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -2381,6 +2381,184 @@ def centerhead_loss(head, heatmap, target_boxes, inds, masks, rec, feat_h, feat_
     return out[HEAD_LOSS_REC - 1].to(torch.float32), out
 
 
+# ------------------------------------------------------------------------------------------------
+# CenterHead: backward through the head's convolutions (csrc/head_backward.hip)
+# ------------------------------------------------------------------------------------------------
+WGRAD_TILE_W = 32                  # DZ_WGRAD_TILE_W: pixel columns of a band
+WGRAD_CHUNK_ROWS = 16              # DZ_WGRAD_CHUNK_ROWS: rows of a workgroup's chunk
+WGRAD_CHUNK_PIXELS = WGRAD_TILE_W * WGRAD_CHUNK_ROWS
+WGRAD_GROUP_PAD = 16               # columns of a group in the grouped layout
+
+
+def _ints(values):
+    return (ctypes.c_int * max(len(values), 1))(*[int(v) for v in values])
+
+
+def _bordered(t, what, c=None):
+    """(B, H, W) of a zero-bordered channel-last (B, H + 2, W + 2, C) float32 image."""
+    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] < 3 or t.shape[2] < 3 or (c is not None and t.shape[3] != c):
+        raise L.DetZeroHipError('%s is a zero-bordered (B, H + 2, W + 2, %s) float32 image, got %s %s'
+                                % (what, 'C' if c is None else c, tuple(t.shape), t.dtype))
+    return t.shape[0], t.shape[1] - 2, t.shape[2] - 2
+
+
+def conv3x3_wgrad(x_img, g_img, cin, cout, groups=1, g_cout=None, g_ooff=None):
+    """Raw weight gradient of a 3 x 3 stride-1 layer: Graw[tap][ci][c] = sum over (b, y, x) of x_img[b, y + ky, x + kx, ci] * g[b, y, x, c].
+    x_img (B, H + 2, W + 2, groups * cin) f32 with its border.  groups == 1: g_img (B, H + 2, W + 2, cout) zero-bordered as relu_grad
+    writes it, or dense (B, H, W, cout) -> (9, cin, cout) f32.  groups > 1: g_img the dense (B, H * W, cout) or (B, H, W, cout) map
+    of which group q reads columns [g_ooff[q], + g_cout[q]) -> (groups, 9, cin, 16) f32, the pad columns 0.  Fixed summation order
+    (split over chunks of WGRAD_CHUNK_PIXELS pixels, added in chunk order).  No host read."""
+    lib = L.load()
+    L.require_cuda(x_img, g_img)
+    cin, cout, groups = int(cin), int(cout), int(groups)
+    b, h, w = _bordered(x_img, 'conv3x3_wgrad: x_img', groups * cin)
+    if g_img.dtype != torch.float32 or g_img.shape[0] != b or g_img.shape[-1] != cout:
+        raise L.DetZeroHipError('conv3x3_wgrad: g_img is float32 with %d frames of %d channels, got %s %s' % (b, cout, tuple(g_img.shape), g_img.dtype))
+    if g_img.dim() == 4 and tuple(g_img.shape[1:3]) == (h + 2, w + 2) and groups == 1:
+        border = 1
+    elif (g_img.dim() == 4 and tuple(g_img.shape[1:3]) == (h, w)) or (g_img.dim() == 3 and g_img.shape[1] == h * w):
+        border = 0
+    else:
+        raise L.DetZeroHipError('conv3x3_wgrad: g_img %s does not match the %d x %d map of x_img' % (tuple(g_img.shape), h, w))
+    g_cout, g_ooff = list(g_cout or []), list(g_ooff or [])
+    if len(g_cout) != len(g_ooff):
+        raise L.DetZeroHipError('conv3x3_wgrad: %d g_cout entries but %d g_ooff entries' % (len(g_cout), len(g_ooff)))
+    dev = x_img.device
+    ws_bytes = int(lib.dz_conv3x3_wgrad_ws_bytes(b, h, w, cin, cout, groups))
+    shape_ok = ws_bytes > 0
+    shape = ((groups, 9, cin, WGRAD_GROUP_PAD) if groups > 1 else (9, cin, cout)) if shape_ok else (4,)
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    ws = _ws(ws_bytes)
+
+    def launch():
+        rc = lib.dz_conv3x3_wgrad(L.ptr(x_img), L.ptr(g_img), border, b, h, w, cin, cout, groups, _ints(g_cout), _ints(g_ooff), len(g_cout),
+                                  L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
+        L.check(rc, 'dz_conv3x3_wgrad')
+
+    if PROFILER is None:
+        launch()
+    else:
+        cols = sum(g_cout) if groups > 1 else cout
+        PROFILER.wrap('k_c3_wgrad', 2.0 * b * h * w * 9 * cin * cols, 4.0 * b * h * w * (groups * cin + cols), launch)
+    return out
+
+
+def relu_grad(g_y, y_img, out=None):
+    """The mask pass between two layers: g = g_y where y_img > 0, else 0 (a select) -> (g_img, sums): g_img the zero-bordered
+    (B, H + 2, W + 2, C) image (`out`, whose interior is written and whose border is left alone, or a fresh zeroed one; `out` may be
+    g_y itself when that is a bordered image), sums (C,) f64 = the channel sums of g in a fixed order.  y_img: the stored activation,
+    zero-bordered; g_y: dense (B, H, W, C) or the interior of a bordered image.  No host read."""
+    lib = L.load()
+    L.require_cuda(g_y, y_img, out)
+    b, h, w = _bordered(y_img, 'relu_grad: y_img')
+    c = y_img.shape[3]
+    if g_y.dtype != torch.float32 or g_y.dim() != 4 or g_y.shape[0] != b or g_y.shape[3] != c or \
+            tuple(g_y.shape[1:3]) not in ((h, w), (h + 2, w + 2)):
+        raise L.DetZeroHipError('relu_grad: g_y is (B, H, W, C) or (B, H + 2, W + 2, C) float32 like y_img %s, got %s %s'
+                                % (tuple(y_img.shape), tuple(g_y.shape), g_y.dtype))
+    border = 1 if g_y.shape[1] == h + 2 else 0
+    if out is not None and (out.dtype != torch.float32 or out.shape != y_img.shape):
+        raise L.DetZeroHipError('relu_grad: out is a float32 image of y_img\'s shape %s, got %s %s' % (tuple(y_img.shape), tuple(out.shape), out.dtype))
+    dev = y_img.device
+    g_img = out if out is not None else torch.zeros(y_img.shape, dtype=torch.float32, device=dev)
+    sums = torch.empty((c,), dtype=torch.float64, device=dev)
+    ws_bytes = int(lib.dz_relu_grad_ws_bytes(b, h, w, c))
+    ws = _ws(ws_bytes)
+
+    def launch():
+        rc = lib.dz_relu_grad(L.ptr(g_y), border, L.ptr(y_img), b, h, w, c, L.ptr(g_img), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream())
+        L.check(rc, 'dz_relu_grad')
+
+    if PROFILER is None:
+        launch()
+    else:
+        PROFILER.wrap('k_relu_grad', 0., 12.0 * b * h * w * c, launch)
+    return g_img, sums
+
+
+def conv3x3_dgrad_weights(w_taps, scale=None):
+    """(9, cin, cout) forward weights -> the (9, cout, cin) weights of the data gradient: flipped in both spatial axes, cin and cout
+    transposed, `scale` (cout,) folded in (w[tap, ci, c] * scale[c]).  Device tensor ops only."""
+    if w_taps.dim() != 3 or w_taps.shape[0] != 9:
+        raise L.DetZeroHipError('conv3x3_dgrad: w_taps is (9, cin, cout), got %s' % (tuple(w_taps.shape),))
+    w = w_taps if scale is None else w_taps * scale.to(w_taps.dtype).reshape(1, 1, -1)
+    return w.flip(0).transpose(1, 2).contiguous()
+
+
+def conv3x3_dgrad(g_img, w_taps, scale=None, out=None):
+    """Data gradient of y = scale * conv3x3(x, w) (stride 1, zero padding 1): g_img (B, H + 2, W + 2, cout) zero-bordered, w_taps
+    (9, cin, cout) f32 forward weights -> (B, H, W, cin) f32 dense, or written into the interior of the zero-bordered `out`
+    (B, H + 2, W + 2, cin).  The weights are flipped and transposed on the device and the layer runs on dz_conv2d_forward (fp32,
+    engines off); cin % 16 == 0 and cout % 16 == 0."""
+    L.require_cuda(g_img, w_taps, scale, out)
+    b, h, w = _bordered(g_img, 'conv3x3_dgrad: g_img')
+    cout = g_img.shape[3]
+    if w_taps.dtype != torch.float32 or w_taps.dim() != 3 or w_taps.shape[0] != 9 or w_taps.shape[2] != cout:
+        raise L.DetZeroHipError('conv3x3_dgrad: w_taps is (9, cin, %d) float32, got %s %s' % (cout, tuple(w_taps.shape), w_taps.dtype))
+    cin = w_taps.shape[1]
+    if cin % 16 or cout % 16:
+        raise L.DetZeroHipError('conv3x3_dgrad: %d -> %d channels (multiples of 16)' % (cin, cout))
+    if scale is not None and scale.numel() != cout:
+        raise L.DetZeroHipError('conv3x3_dgrad: %d scale entries for %d channels' % (scale.numel(), cout))
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (b, h + 2, w + 2, cin)):
+        raise L.DetZeroHipError('conv3x3_dgrad: out is a zero-bordered (%d, %d, %d, %d) float32 image, got %s %s'
+                                % (b, h + 2, w + 2, cin, tuple(out.shape), out.dtype))
+    wt = conv3x3_dgrad_weights(w_taps, scale)
+    res = out if out is not None else torch.empty((b, h, w, cin), dtype=torch.float32, device=g_img.device)
+    pad = 1 if out is not None else 0
+    conv2d(dict(inp=g_img.data_ptr(), out=res.data_ptr(), w=wt.data_ptr(), scale=None, shift=None, batch=b, ho=h, wo=w, in_hp=h + 2,
+                in_wp=w + 2, in_cstride=cout, in_coff=0, cin=cout, kh=3, kw=3, stride=1, in_off=0, out_hp=h + 2 * pad, out_wp=w + 2 * pad,
+                out_cstride=cin, out_coff=0, out_sy=1, out_sx=1, out_dy=pad, out_dx=pad, groups=1, cout_pad=cin, g_cout=[cin], g_ooff=[0],
+                relu=0, phase_groups=0, in_rowidx=None, in_row_channels=0, in_rows=0, in_tiles=None), math=0)
+    return res
+
+
+def head_final_backward(grad_head, w2, hidden_img, g_cout, g_ooff, out=None):
+    """Both halves of the backward of a SeparateHead's grouped output layer (groups slices of c hidden channels -> the head map's 12
+    columns).  grad_head (B, H * W, 12) f32; w2 (groups, 9, c, 16) f32 (plan()['heads'][i]['final']['w']); hidden_img
+    (B, H + 2, W + 2, groups * c) f32 zero-bordered: the hidden layer's stored activation.
+    -> (g_hidden, sums, d_w2, d_bias): g_hidden the zero-bordered image of the gradient at the hidden layer's pre-activation (the
+    layer's ReLU mask applied; `out`, whose border is left alone, or a fresh zeroed image), sums (groups * c,) f64 its channel sums,
+    d_w2 (groups, 9, c, 16) f32 the weight gradient (pad columns 0), d_bias (groups, 16) f64 the column sums of grad_head (pad
+    columns 0).  Columns of grad_head outside the groups' ranges are never read.  No host read."""
+    lib = L.load()
+    L.require_cuda(grad_head, w2, hidden_img, out)
+    b, h, w = _bordered(hidden_img, 'head_final_backward: hidden_img')
+    if grad_head.dtype != torch.float32 or tuple(grad_head.shape) != (b, h * w, 12):
+        raise L.DetZeroHipError('head_final_backward: grad_head is (%d, %d, 12) float32, got %s %s' % (b, h * w, tuple(grad_head.shape), grad_head.dtype))
+    if w2.dtype != torch.float32 or w2.dim() != 4 or w2.shape[1] != 9 or w2.shape[3] != WGRAD_GROUP_PAD or \
+            w2.shape[0] * w2.shape[2] != hidden_img.shape[3]:
+        raise L.DetZeroHipError('head_final_backward: w2 is (groups, 9, c, 16) float32 with groups * c = %d, got %s %s'
+                                % (hidden_img.shape[3], tuple(w2.shape), w2.dtype))
+    groups, c = w2.shape[0], w2.shape[2]
+    g_cout, g_ooff = list(g_cout), list(g_ooff)
+    if len(g_cout) != len(g_ooff):
+        raise L.DetZeroHipError('head_final_backward: %d g_cout entries but %d g_ooff entries' % (len(g_cout), len(g_ooff)))
+    if out is not None and (out.dtype != torch.float32 or out.shape != hidden_img.shape):
+        raise L.DetZeroHipError('head_final_backward: out is a float32 image of hidden_img\'s shape %s, got %s %s'
+                                % (tuple(hidden_img.shape), tuple(out.shape), out.dtype))
+    dev = hidden_img.device
+    g_hidden = out if out is not None else torch.zeros(hidden_img.shape, dtype=torch.float32, device=dev)
+    sums = torch.empty((groups * c,), dtype=torch.float64, device=dev)
+    d_w2 = torch.empty(w2.shape, dtype=torch.float32, device=dev)
+    d_bias = torch.empty((groups, WGRAD_GROUP_PAD), dtype=torch.float64, device=dev)
+    ws_bytes = int(lib.dz_head_final_backward_ws_bytes(b, h, w, c, groups))
+    ws = _ws(ws_bytes)
+
+    def launch():
+        rc = lib.dz_head_final_backward(L.ptr(grad_head), L.ptr(w2), L.ptr(hidden_img), b, h, w, c, groups, _ints(g_cout), _ints(g_ooff),
+                                        len(g_cout), L.ptr(g_hidden), L.ptr(sums), L.ptr(d_w2), L.ptr(d_bias), L.ptr(ws), ws.numel(),
+                                        L.stream())
+        L.check(rc, 'dz_head_final_backward')
+
+    if PROFILER is None:
+        launch()
+    else:
+        cols = sum(g_cout)
+        PROFILER.wrap('head_final_backward', 4.0 * b * h * w * 9 * c * cols, 4.0 * b * h * w * (2 * groups * c + 12), launch)
+    return g_hidden, sums, d_w2, d_bias
+
+
 PROFILER = None
 
 

@@ -1349,6 +1349,57 @@ int dz_centerhead_loss(const float *head, const float *heatmap, const float *tar
                        double stride, const double *range_xy, const double *voxel_xy, double *out_rec, float *grad_head, void *ws,
                        size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CenterHead: backward through the head's 3 x 3 convolutions (csrc/head_backward.hip).  The reference leaves this to
+ * torch autograd.  One layer is y = relu(scale_c * conv(x, w)_c + shift_c); with g = g_y * [y > 0] the raw weight gradient is
+ *   Graw[tap][ci][c] = sum over (b, y, x) of x_img[b, y + ky, x + kx, ci] * g[b, y, x, c],   tap = ky * 3 + kx,
+ * x_img the zero-bordered channel-last input, and S_c = sum g_c; the parameter gradients are formed from those two by the caller.
+ * The data gradient is dz_conv2d_forward on the g image with flipped, transposed weights: there is no kernel for it here.
+ * No floating-point atomics: every sum has a fixed order, two calls give the same bytes whatever the workspace held before.
+ * Every entry refuses, before any launch, null pointers and non-positive sizes (DZ_ERR_INVALID), a workspace that is too small
+ * (DZ_ERR_WORKSPACE), and shapes outside its limits or an image of 2 GiB or more (DZ_ERR_UNSUPPORTED).
+ *
+ * dz_conv3x3_wgrad: Graw of one layer by fp32 MFMA (32x32x2), split over pixel chunks, the chunks' partials added in chunk order.
+ *   x_img (B, h + 2, w + 2, groups * cin) f32 with its border (read as it is); group q reads channels [q * cin, (q + 1) * cin).
+ *   groups == 1: g_img has `cout` channels (cout % 16 == 0); out (9, cin, cout) f32.  g_cout / g_ooff may be NULL (n_g 0).
+ *   groups in 2..8: g_img has `cout` channels in all (the head map's 12), group q reads columns [g_ooff[q], g_ooff[q] + g_cout[q]),
+ *     1 <= g_cout[q] <= 16, inside [0, cout); out (groups, 9, cin, 16) f32, the pad columns written as 0.  g_cout / g_ooff: n_g
+ *     entries on the HOST, n_g == groups.  Columns outside the groups' ranges are never read.
+ *   g_border 1: g_img is (B, h + 2, w + 2, cout), its interior read (as dz_relu_grad writes it); 0: dense (B, h, w, cout).
+ *   Limits: cin % 16 == 0, 16 <= cin <= 512, cout <= 512, x_img and g_img 16-byte aligned (groups == 1).
+ *   A workgroup takes DZ_WGRAD_CHUNK_ROWS rows of a band of DZ_WGRAD_TILE_W pixel columns of one frame (DZ_WGRAD_CHUNK_PIXELS pixels).
+ *   ws: dz_conv3x3_wgrad_ws_bytes(batch, h, w, cin, cout, groups) bytes (0 for a shape that is refused).
+ *
+ * dz_relu_grad: g = g_y where y > 0, else 0 (a select: NaN in y or in a masked g_y does not leak), written into the interior of the
+ *   zero-bordered g_img (B, h + 2, w + 2, c) - the border is never written - and sums[c] = S_c in float64 (per-workgroup partials,
+ *   then one pass in index order).  y_img (B, h + 2, w + 2, c): the stored activation.  g_y: dense (B, h, w, c) (gy_border 0) or the
+ *   interior of a bordered image (gy_border 1; g_img may then be g_y itself).  c % 4 == 0, 4 <= c <= 512.
+ *   ws: dz_relu_grad_ws_bytes(batch, h, w, c) bytes.
+ *
+ * dz_head_final_backward: the grouped output layer (groups hidden slices of c channels -> the head map's 12 columns; no BatchNorm,
+ *   no ReLU) of one SeparateHead, both halves.
+ *   grad_head (B, h * w, 12) f32: d loss / d head map; columns outside the groups' ranges are never read.
+ *   w2 (groups, 9, c, 16) f32: the layer's weights (CenterHead.plan()['heads'][i]['final']['w']).
+ *   hidden (B, h + 2, w + 2, groups * c) f32 zero-bordered: the stored activation of the hidden layer (its ReLU mask).
+ *   g_hidden (B, h + 2, w + 2, groups * c): interior written with
+ *     [hidden > 0] * sum over taps and the group's columns of grad_head[b, y - ky + 1, x - kx + 1, g_ooff + o] * w2[q, tap, ch, o];
+ *   sums_hidden (groups * c) f64 = its channel sums; d_w2 (groups, 9, c, 16) f32 = Graw of the layer (dz_conv3x3_wgrad, grouped);
+ *   d_bias (groups, 16) f64 = the column sums of grad_head, 0 in the pad columns.
+ *   groups in 2..8, c % 16 == 0, 16 <= c <= 128 (and groups * c * 27 * 4 bytes of weights inside 64 KiB of LDS), 1 <= g_cout <= 3.  ws: dz_head_final_backward_ws_bytes(batch, h, w, c, groups). */
+#define DZ_WGRAD_TILE_W 32
+#define DZ_WGRAD_CHUNK_ROWS 16
+#define DZ_WGRAD_CHUNK_PIXELS (DZ_WGRAD_TILE_W * DZ_WGRAD_CHUNK_ROWS)
+size_t dz_conv3x3_wgrad_ws_bytes(int batch, int h, int w, int cin, int cout, int groups);
+int dz_conv3x3_wgrad(const float *x_img, const float *g_img, int g_border, int batch, int h, int w, int cin, int cout, int groups,
+                     const int *g_cout, const int *g_ooff, int n_g, float *out, void *ws, size_t ws_bytes, void *stream);
+size_t dz_relu_grad_ws_bytes(int batch, int h, int w, int c);
+int dz_relu_grad(const float *g_y, int gy_border, const float *y_img, int batch, int h, int w, int c, float *g_img, double *sums, void *ws,
+                 size_t ws_bytes, void *stream);
+size_t dz_head_final_backward_ws_bytes(int batch, int h, int w, int c, int groups);
+int dz_head_final_backward(const float *grad_head, const float *w2, const float *hidden, int batch, int h, int w, int c, int groups,
+                           const int *g_cout, const int *g_ooff, int n_g, float *g_hidden, double *sums_hidden, float *d_w2,
+                           double *d_bias, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
